@@ -10,9 +10,16 @@ already resident in HBM:
                      independent tracking problems; unit = template point               [BASELINE configs[1]]
   --workload trace   ImmaturePoint::traceStereo over a batch of stereo pairs; unit = point [configs[3]]
 
-Contract (one JSON line on rank 0): see the task statement; plus "roofline" (dominant kernel,
-HIP-event timed inside libsdso_hip.so on the stream the kernel runs on) and "cpu_baseline"
-(the oracle port, -O3 -march=native, timed on a bounded sample on this box's host cores).
+Contract (one JSON line on rank 0): metric / value / unit / higher_is_better / dtype / ms_per_step (wall clock of one
+timed step) plus "roofline" (dominant kernel, HIP-event timed inside libsdso_hip.so on the stream the kernel runs on,
+during the timed steps themselves).  A plain run sets up, warms up, times --steps steps, writes --dump-outputs and prints
+that line; the workload's cheap sanity checks of its own state (finite x, shrinking GN steps, trace statuses) stay in it.
+--full adds what takes runs of its own: "cpu_baseline" (the oracle port, -O3 -march=native, timed on a bounded sample on
+the host's cores), the other workloads' side runs, BA's fused-vs-unfused reference solve, its secondary kernels and
+the run without Jacobian records.
+--dump-outputs DIR: after the timed steps, what the last step computed (the arrays a caller of the timed path receives) as
+DIR/<name>.npy in float32 / float64, at most 64 MiB in all (a fixed, seeded sample of rows beyond that).  The inputs are
+seeded, so two builds compare output for output at the same arguments.
 Multi-GPU: one process per GPU (torch.distributed, backend nccl == RCCL).  BA shards the points of
 every window across ranks and all-reduces the packed accumulators once per iteration (weak scaling:
 per-GPU work fixed, windows scale with N); tracker / trace are replicas (no collective).
@@ -55,6 +62,22 @@ def pmc_traffic(workload, config):
 def log(*a):
     if int(os.environ.get("RANK", "0")) == 0:
         print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float64 kept, everything else as float32 (the integer / status outputs are
+    small and exact in float32).  Above 64 MiB in all, every array keeps a fixed, seeded sample of its rows (axis 0)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, np.float64 if a.dtype == np.float64 else np.float32) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for k, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES and len(a) > 1:
+            keep = max(1, len(a) * DUMP_LIMIT_BYTES // total)
+            a = a[np.sort(np.random.RandomState(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -102,6 +125,13 @@ class TrackerWorkload:
 
     def step(self):
         self.ctx.check(self.ctx.L.sdso_track_batch_enqueue(self.ctx.h))
+
+    def outputs(self):
+        abi = self.abi
+        n = self.nprob
+        H = np.zeros((n, 64)); b = np.zeros((n, 8)); res = np.zeros((n, 6)); nw = np.zeros(n, np.int32)
+        self.ctx.check(self.ctx.L.sdso_track_batch_fetch(self.ctx.h, abi.dp(H), abi.dp(b), abi.dp(res), abi.ip(nw)))
+        return {"H": H, "b": b, "res": res, "n_warped": nw}
 
     def verify(self):
         abi = self.abi
@@ -163,6 +193,14 @@ class TraceWorkload:
 
     def step(self):
         self.ctx.check(self.ctx.L.sdso_trace_stereo_enqueue(self.ctx.h))
+
+    def outputs(self):
+        st = np.zeros(self.P.n, np.uint8)
+        self.ctx.check(self.ctx.L.sdso_trace_stereo_fetch(self.ctx.h, C.byref(self.P), self.abi.bp(st)))
+        out = {k: self.d[k].copy() for k in ("idepth_min_stereo", "idepth_max_stereo", "idepth_stereo", "quality", "lastTraceStatus",
+                                             "lastTraceUV", "lastTracePixelInterval")}
+        out["status"] = st
+        return out
 
     def verify(self):
         st = np.zeros(self.P.n, np.uint8)
@@ -235,6 +273,9 @@ class MatchWorkload:
 
     def step(self):
         self.ctx.check(self.ctx.L.sdso_stereo_match_batch(self.ctx.h, 80, 81, self.abi.fp(self.K), self.bl, 1, C.byref(self.M)))
+
+    def outputs(self):
+        return {k: a.copy() for k, a in self.out.items()}
 
     def verify(self):
         sf, sb = self.out["status_fwd"], self.out["status_back"]
@@ -366,7 +407,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default=os.environ.get("SDSO_BENCH_WORKLOAD", "ba"), choices=["ba", "tracker", "trace", "match"])
     ap.add_argument("--batch", type=int, default=0, help="independent problems (frames / windows / pairs) per step and GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the other workloads' side runs, BA's reference solve, secondary kernels and no-Jacobian run")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--scaling", default=os.environ.get("SDSO_BENCH_SCALING", "weak"), choices=["weak", "strong"],
                     help="BA at --gpus N: weak = 2000 points per window and rank (default); strong = BASELINE configs[4], 8000 points per window cut N ways")
     args = ap.parse_args()
@@ -442,6 +486,8 @@ def main():
         units_per_step = float(units.item())
     else:
         units_per_step = float(wl.units_per_step)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl.outputs())
     kms, klaunch = prof_read(wl.kernel)
     extra = wl.verify()
 
@@ -491,11 +537,11 @@ def main():
                              "(profiles/r05_tile_grids_ab.txt)")
                 out["roofline"]["bound_note"] = note
         out["extra"]["host_enqueue_ms_per_step"] = t_enq / args.steps * 1e3
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = wl.cpu_baseline()
             if out["cpu_baseline"].get("value"):
                 out["extra"]["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
-        if args.workload == "ba" and world == 1 and not args.no_cpu_baseline and os.environ.get("SDSO_BENCH_SKIP_OTHERS") != "1":
+        if args.workload == "ba" and world == 1 and args.full and not args.no_cpu_baseline and os.environ.get("SDSO_BENCH_SKIP_OTHERS") != "1":
             # the two other units of BASELINE.json's metric family, measured the same way in short runs (informational; the
             # headline `value` / `roofline` above are the BA workload's)
             out["extra"]["other_workloads"] = {name: side_run(cls, ctx, args, rank) for name, cls in WORKLOADS.items()}

@@ -51,6 +51,7 @@ class BAWorkload:
         t0 = time.time()
         from sdso_amd import dist as sdist
         self.scaling = getattr(args, "scaling", "weak")
+        self.full = bool(getattr(args, "full", False))   # bench.py --full: the reference solve, secondary kernels, no-Jacobian run
         strong = self.scaling == "strong"
         # enough independent windows that the working set is >> the 256 MB MALL.  256 since the end of round 3 (128 before): the
         # serial kernels behind the linearisation are one workgroup per window (k_ba_tail: 87 us for 128 windows on 256 CUs, 95 us for 256)
@@ -282,9 +283,10 @@ class BAWorkload:
             G.ctx.check(G.ctx.L.sdso_ba_batch_solve(G.ctx.h, 1e-5, 0))
 
     def _verify_initial(self):
-        """One GN iteration at the uploaded state: x of every window is finite; window 0's x (fused batch path, summed over the ranks
-        when sharded) equals the x of the UNSHARDED global window solved through the un-fused single-window entry points on this GPU
-        (2e-4 in the whitened metric, the bar of tests/test_ba_gpu.py)."""
+        """One GN iteration at the uploaded state: x of every window is finite; with --full, window 0's x (fused batch path, summed over
+        the ranks when sharded) equals the x of the UNSHARDED global window solved through the un-fused single-window entry points on
+        this GPU (2e-4 in the whitened metric, the bar of tests/test_ba_gpu.py).  The iteration itself runs in every mode: the timed
+        loop starts from the state it leaves."""
         abi = self.abi
         self._one_iteration()
         out = {}
@@ -297,7 +299,7 @@ class BAWorkload:
             if x0 is None:
                 x0 = x[0].copy()
         out["max_abs_x_initial"] = mx
-        if self.rank == 0:
+        if self.rank == 0 and self.full:
             g0, wg, nf = self.groups[0], self.win_global, self.win_global["nf"]
             W, keep = abi.make_ba_window(wg, frame_slots=[1000 + f for f in range(nf)])          # the pyramids of window 0
             g0.ctx.check(g0.ctx.L.sdso_ba_upload_window(g0.ctx.h, 9000, C.byref(W)))
@@ -315,9 +317,27 @@ class BAWorkload:
             assert err <= 2e-4, "x of window 0 differs from the unsharded / un-fused reference solve: %g" % err
         return out
 
+    def outputs(self):
+        """What a caller of the timed step receives after the last one: lastX of every window (sdso_ba_batch_get_x) and, per window,
+        the points' idepths and the residuals' states as they stand (sdso_ba_get_state; the frame states live on the device until
+        sdso_ba_batch_optimize_end, so they are not among them).  Rows in window order."""
+        abi = self.abi
+        np_, nr = self.win["np"], self.win["nr"]
+        xs, idepth, rstate = [], [], []
+        for G in self.groups:
+            x = np.zeros((G.nwin, 8 * self.win["nf"] + 4))
+            G.ctx.check(G.ctx.L.sdso_ba_batch_get_x(G.ctx.h, abi.dp(x)))
+            xs.append(x)
+            for w in G.ids:
+                idp, rs = np.zeros(np_, np.float32), np.zeros(nr, np.uint8)
+                G.ctx.check(G.ctx.L.sdso_ba_get_state(G.ctx.h, int(w), None, abi.fp(idp), abi.bp(rs)))
+                idepth.append(idp); rstate.append(rs)
+        return {"x": np.concatenate(xs), "idepth": np.stack(idepth), "residual_state": np.stack(rstate)}
+
     def verify(self):
         """After the timed steps: x of every window still finite; with state_advances the Gauss-Newton steps must have shrunk
-        (max |x| of the last step against the first iteration's) — the loop really moved the states towards the optimum."""
+        (max |x| of the last step against the first iteration's) — the loop really moved the states towards the optimum.  With --full
+        also the secondary kernels and the run without Jacobian records, in extra steps after the timed loop."""
         abi = self.abi
         out = {"jacobians_materialized": bool(self.materialize)}
         out.update(self.initial_check)
@@ -334,7 +354,8 @@ class BAWorkload:
         # dominant kernel only — two event records per bracket and stream are queue time the step would otherwise pay for nothing)
         ms, n = self.prof_read("k_ba_lin_fused")
         out["k_ba_lin_fused_avg_ms"] = ms / max(n, 1)
-        if os.environ.get("SDSO_BENCH_SECONDARY", "1") == "1":
+        secondary = self.full and os.environ.get("SDSO_BENCH_SECONDARY", "1") == "1"
+        if secondary:
             for G in self.groups:
                 G.ctx.check(G.ctx.L.sdso_prof_enable(G.ctx.h, 2))
             names = ("k_ba_sc", "k_ba_tail", "k_ba_resub", "sdso_ba_allreduce")
@@ -369,7 +390,7 @@ class BAWorkload:
         # The second unit of SURVEY §8d, measured the same way in a few extra steps: the records stay in registers (464 B per point-residual
         # instead of 760: nothing downstream of the linearisation reads RawResidualJacobian — the library's own resident loop,
         # sdso_ba_optimize, runs this way and materialises them in its closing linearizeAll only).  The headline above keeps the 760-B unit.
-        if self.materialize and self.advance and os.environ.get("SDSO_BENCH_SECONDARY", "1") == "1":
+        if self.materialize and self.advance and secondary:
             torch = self.torch
             for G in self.groups:
                 G.ctx.check(G.ctx.L.sdso_ba_batch_set_materialize(G.ctx.h, 0))

@@ -528,7 +528,7 @@ def test_bench_command_two_ranks_advances_the_same_work(scaling):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["SDSO_DIST_BACKEND"] = "gloo_lib"
     env["SDSO_BA_EXCHANGE"] = "scatter" if scaling.endswith("_scatter") else "allreduce"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "3", "--batch", "4",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "3", "--batch", "4", "--full",
            "--scaling", scaling.replace("_scatter", "")]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]

@@ -3,7 +3,7 @@
 # kernels own k CUs (sdso_ctx_partition_cus).  Usage on the GPU box: bash tools/ab_cumask.sh > gpurun_out/r06_cumask_ab.txt
 export SDSO_DEBUG_ENV=1
 run() {
-  env "$@" SDSO_BENCH_SKIP_OTHERS=1 SDSO_BENCH_SECONDARY=${SEC:-1} timeout -k 10 300 python bench.py --steps 30 --no-cpu-baseline 2>/dev/null | python -c "
+  env "$@" SDSO_BENCH_SKIP_OTHERS=1 SDSO_BENCH_SECONDARY=${SEC:-1} timeout -k 10 300 python bench.py --full --steps 30 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); e=d['extra']
 f=lambda v: ('%.3f' % v) if isinstance(v,(int,float)) else str(v)

@@ -6,7 +6,7 @@ tag=${1:?round tag, e.g. r06}
 root=${GRAFT_REPO_ROOT:-/root/repo}
 out=$root/gpurun_out
 cd $root
-python3 bench.py --workload trace --steps 200 --warmup 20 > $out/${tag}_bench_trace.json 2> $out/${tag}_bench_trace.err
+python3 bench.py --full --workload trace --steps 200 --warmup 20 > $out/${tag}_bench_trace.json 2> $out/${tag}_bench_trace.err
 python3 bench.py --workload trace --batch 75000 --steps 100 --warmup 10 --no-cpu-baseline > $out/${tag}_bench_trace_75k.json 2> $out/${tag}_bench_trace_75k.err
 python3 bench.py --workload match --batch 75000 --steps 30 --warmup 5 --no-cpu-baseline > $out/${tag}_bench_match_75k.json 2> $out/${tag}_bench_match_75k.err
 python3 bench.py --workload match --steps 50 --warmup 5 --no-cpu-baseline > $out/${tag}_bench_match_20k.json 2> $out/${tag}_bench_match_20k.err
