@@ -144,7 +144,6 @@ static void free_window(sdso_ctx* ctx, BaWindowDev* W) {
 struct BaLaunch {
   const BaDev* d_arr; int nwin; int max_nblk_res, max_nblk_pts, max_chunks, max_items, nf, n;
   bool any_lin;   // some window holds linearized residuals -> the mode-1 accumulation has work to do
-  bool tiled;     // the windows' t_img are 4x2-tiled level-0 images (same for every window of a launch)
   bool alt;       // the windows' solverMode takes solveSystemF's SVD / orthogonalised-system branches (ba_solve_alt.hip): never the fused tail kernel
   std::vector<BaWindowDev*> Ws;   // the windows behind d_arr (host bookkeeping of a launch: BaWindowDev::l_dirty)
 };
@@ -290,7 +289,6 @@ static int upload_window_impl(sdso_ctx* ctx, int win, const sdso_ba_window_t* Wi
   int rc = sdso_ba_release_window(ctx, win);
   if (rc) return rc;
   mark("release of the old window");
-  const bool use_tiled = dbg_env("SDSO_BA_ROWMAJOR") == nullptr;   // 4x2-tiled level-0 images for the linearisation (default)
 
   BaWindowDev* W = new BaWindowDev();
   ctx->wins[win] = W;
@@ -323,11 +321,9 @@ static int upload_window_impl(sdso_ctx* ctx, int win, const sdso_ba_window_t* Wi
     auto ip = ctx->pyr.find(F.frame_slot);
     SDSO_REQUIRE(ctx, ip != ctx->pyr.end(), "window references a frame slot without an uploaded pyramid");
     SDSO_REQUIRE(ctx, ip->second.w[0] == Win->w && ip->second.h[0] == Win->h, "pyramid level-0 size differs from the window's w/h");
-    if (use_tiled) {
-      int rc = ensure_tiled0(ctx, ip->second);
-      if (rc) return rc;
-      imgs[f] = ip->second.tiled0;
-    } else imgs[f] = ip->second.d[0];
+    int rc = ensure_tiled0(ctx, ip->second);   // 4x2-tiled level-0 images for the linearisation
+    if (rc) return rc;
+    imgs[f] = ip->second.tiled0;
   }
   W->HM.assign((size_t)n * n, 0.0); W->bM.assign(n, 0.0);
   if (Win->HM) std::memcpy(W->HM.data(), Win->HM, sizeof(double) * n * n);
@@ -485,7 +481,7 @@ static int upload_window_impl(sdso_ctx* ctx, int win, const sdso_ba_window_t* Wi
   d.p_rbeg = p_rbeg; d.p_rcnt = p_rcnt; d.p_rlist = p_rlist; d.p_out = p_out;
   d.p_order = p_order; d.p_track = p_track; d.r_isnew = r_isnew;
   d.r_point = r_point; d.r_orig = r_orig; d.r_host = r_host; d.r_target = r_target;
-  d.tiledT = use_tiled ? (Win->w + 3) / 4 : 0;
+  d.tiledT = (Win->w + 3) / 4;
   d.t_precalc = W->dt_precalc; d.t_adHTdelta = W->dt_adHTdelta; d.t_cdelta = W->dt_cdelta; d.t_frameTH = W->dt_frameTH; d.t_img = d_img;
   d.t_adHost = W->dt_adHost; d.t_adTarget = W->dt_adTarget; d.t_xAd = W->dt_xAd; d.t_prior = W->dt_prior; d.t_HM = W->dt_HM; d.t_bM = W->dt_bM; d.t_P = W->dt_P;
   d.chunks = d_chunks; d.pair_chunk_beg = d_pair_beg; d.items = d_items; d.host_item_beg = d_host_beg;
@@ -578,8 +574,7 @@ extern "C" int sdso_ba_keep_projections(sdso_ctx* ctx, int win, int on) {
 namespace sdso {
 static void launch_linearize(sdso_ctx* ctx, const BaLaunch& L) {
   ProfScope ps(ctx, "k_ba_linearize");
-  if (L.tiled) hipLaunchKernelGGL(k_ba_linearize<true>, dim3(L.max_nblk_res, L.nwin), dim3(BA_BLOCK), 0, ctx->stream, L.d_arr);
-  else hipLaunchKernelGGL(k_ba_linearize<false>, dim3(L.max_nblk_res, L.nwin), dim3(BA_BLOCK), 0, ctx->stream, L.d_arr);
+  hipLaunchKernelGGL(k_ba_linearize, dim3(L.max_nblk_res, L.nwin), dim3(BA_BLOCK), 0, ctx->stream, L.d_arr);
 }
 static void launch_apply(sdso_ctx* ctx, const BaLaunch& L) {
   hipLaunchKernelGGL(k_ba_apply, dim3(L.max_nblk_res, L.nwin), dim3(BA_BLOCK), 0, ctx->stream, L.d_arr);
@@ -643,17 +638,9 @@ static bool launch_sc_and_folds(sdso_ctx* ctx, const BaLaunch& L, const uint8_t*
 static bool launch_fused(sdso_ctx* ctx, const BaLaunch& L, bool materialize, int part = 3 /* bit 0: linearize+top, bit 1: Schur+folds */, bool defer_fold = false) {
   const int nf = L.nf;
   if ((part & 1) && L.max_chunks > 0) {
-    {
-#ifdef SDSO_LIN_PERSIST
-      const dim3 g((L.max_chunks + 1) / 2, L.nwin), b(BA_BLOCK);      // A/B: two chunks per (persistent) workgroup
-#else
-      const dim3 g(L.max_chunks, L.nwin), b(BA_BLOCK);
-#endif
-#define LT(K) launch_timed(ctx, "k_ba_lin_fused", 1, K, g, b, (const BaDev*)L.d_arr)
-      if (materialize) { if (L.tiled) LT((k_ba_lin_fused<true, true>)); else LT((k_ba_lin_fused<true, false>)); }
-      else { if (L.tiled) LT((k_ba_lin_fused<false, true>)); else LT((k_ba_lin_fused<false, false>)); }
-#undef LT
-    }
+    const dim3 g(L.max_chunks, L.nwin), b(BA_BLOCK);
+    if (materialize) launch_timed(ctx, "k_ba_lin_fused", 1, k_ba_lin_fused<true>, g, b, (const BaDev*)L.d_arr);
+    else launch_timed(ctx, "k_ba_lin_fused", 1, k_ba_lin_fused<false>, g, b, (const BaDev*)L.d_arr);
     if (L.any_lin) {
       hipLaunchKernelGGL(k_ba_fold_top, dim3(nf * nf, L.nwin), dim3(128), 0, ctx->stream, L.d_arr, 0);
       hipLaunchKernelGGL(k_ba_accum_top, dim3(L.max_chunks, L.nwin), dim3(BA_BLOCK), 0, ctx->stream, L.d_arr, 1, (const uint8_t*)nullptr);
@@ -722,7 +709,6 @@ static BaLaunch single(BaWindowDev* W) {
   L.d_arr = W->d_self; L.nwin = 1; L.max_nblk_res = std::max(W->nblk_res, 1); L.max_nblk_pts = W->nblk_pts;
   L.max_chunks = W->d.nchunks; L.max_items = W->d.nitems; L.nf = W->d.nf; L.n = W->d.n;
   L.any_lin = W->has_lin_cached;
-  L.tiled = W->d.tiledT > 0;
   L.alt = (W->solverMode & (SOLVER_SVD | SOLVER_ORTHOGONALIZE_SYSTEM)) != 0;
   L.Ws = {W};
   return L;
@@ -1363,8 +1349,7 @@ extern "C" int sdso_ba_marginalize_points(sdso_ctx* ctx, int win, const uint8_t*
   BaLaunch L = single(W);
   H2D(W->d_pflag, marg_flag, np);
   hipLaunchKernelGGL(k_ba_reset_flagged, dim3(L.max_nblk_res, 1), dim3(BA_BLOCK), 0, ctx->stream, L.d_arr, W->d_pflag);
-  if (L.tiled) hipLaunchKernelGGL(k_ba_linearize<true>, dim3(L.max_nblk_res, 1), dim3(BA_BLOCK), 0, ctx->stream, L.d_arr);
-  else hipLaunchKernelGGL(k_ba_linearize<false>, dim3(L.max_nblk_res, 1), dim3(BA_BLOCK), 0, ctx->stream, L.d_arr);
+  hipLaunchKernelGGL(k_ba_linearize, dim3(L.max_nblk_res, 1), dim3(BA_BLOCK), 0, ctx->stream, L.d_arr);
   W->j_inplace_last = false;
   launch_apply(ctx, L);
   hipLaunchKernelGGL(k_ba_unmask, dim3(L.max_nblk_res, 1), dim3(BA_BLOCK), 0, ctx->stream, L.d_arr);
@@ -1420,7 +1405,6 @@ extern "C" int sdso_ba_batch_create(sdso_ctx* ctx, int nwin, const int* wins) {
     Ws[i] = find_win(ctx, wins[i]);
     SDSO_REQUIRE(ctx, Ws[i], "unknown window in batch");
     SDSO_REQUIRE(ctx, Ws[i]->d.nf == Ws[0]->d.nf, "batch windows must share nf");
-    SDSO_REQUIRE(ctx, (Ws[i]->d.tiledT > 0) == (Ws[0]->d.tiledT > 0), "batch windows must share the image layout");
     SDSO_REQUIRE(ctx, Ws[i]->solverMode == Ws[0]->solverMode, "batch windows must share solverMode (one lambda per launch)");
     for (int k = 0; k < i; k++) SDSO_REQUIRE(ctx, Ws[k] != Ws[i], "a window may appear only once in a batch");
   }
@@ -1436,7 +1420,7 @@ extern "C" int sdso_ba_batch_create(sdso_ctx* ctx, int nwin, const int* wins) {
   hipMemsetAsync(Bt->d_accum, 0, sizeof(float) * af * nwin, ctx->stream);
   std::vector<BaDev> h(nwin);
   BaLaunch L{};
-  L.nwin = nwin; L.nf = nf; L.n = Ws[0]->d.n; L.tiled = Ws[0]->d.tiledT > 0;
+  L.nwin = nwin; L.nf = nf; L.n = Ws[0]->d.n;
   for (int i = 0; i < nwin; i++) {
     BaWindowDev* W = Ws[i];
     W->d.accum = Bt->d_accum + af * i;   // contiguous accumulators: ONE all-reduce covers the batch
@@ -1862,8 +1846,7 @@ static int opt_step(sdso_ctx* ctx, OptRun& R) {
 static void gated_linearize(sdso_ctx* ctx, OptRun& R, int cond, int which) {
   const int nwin = (int)R.W.size();
   const dim3 g(R.L.max_nblk_res, nwin), b(BA_BLOCK);
-  if (R.L.tiled) hipLaunchKernelGGL(k_ba_linearize<true>, g, b, 0, ctx->stream, R.L.d_arr, cond);
-  else hipLaunchKernelGGL(k_ba_linearize<false>, g, b, 0, ctx->stream, R.L.d_arr, cond);
+  hipLaunchKernelGGL(k_ba_linearize, g, b, 0, ctx->stream, R.L.d_arr, cond);
   mark_linearized(R.W, false);
   const int nblk = R.L.max_chunks + R.L.max_nblk_pts;
   if (nblk > 0) hipLaunchKernelGGL(k_ba_lenergy, dim3(nblk, nwin), b, 0, ctx->stream, R.L.d_arr, R.B->d_lpart, R.lstride, cond);
@@ -1974,8 +1957,7 @@ static int opt_finish(sdso_ctx* ctx, OptRun& R, sdso_ba_opt_result_t* out) {
     if (W->in_batch) H2D(const_cast<BaDev*>(R.L.d_arr) + w, &W->d, sizeof(BaDev));   // the batch's descriptor copy carries the calibration scalars too
     W->accumulated = false;
   }
-  if (R.L.tiled) hipLaunchKernelGGL(k_ba_linearize<true>, dim3(R.L.max_nblk_res, nwin), dim3(BA_BLOCK), 0, ctx->stream, R.L.d_arr);
-  else hipLaunchKernelGGL(k_ba_linearize<false>, dim3(R.L.max_nblk_res, nwin), dim3(BA_BLOCK), 0, ctx->stream, R.L.d_arr);
+  hipLaunchKernelGGL(k_ba_linearize, dim3(R.L.max_nblk_res, nwin), dim3(BA_BLOCK), 0, ctx->stream, R.L.d_arr);
   mark_linearized(R.W, false);
   hipLaunchKernelGGL(k_ba_apply, dim3(R.L.max_nblk_res, nwin), dim3(BA_BLOCK), 0, ctx->stream, R.L.d_arr);
   if ((rc = opt_consume(ctx, R, 1, true, false))) return rc;

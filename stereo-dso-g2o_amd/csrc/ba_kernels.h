@@ -66,7 +66,7 @@ struct BaOptDev {
 
 struct BaDev {
   int nf, np, nr, nrp, w, h, nchunks, nitems, n;
-  int tiledT;               // > 0: t_img are 4x2-tiled level-0 images with tiledT tiles per row; 0: row-major
+  int tiledT;               // t_img are 4x2-tiled level-0 images with tiledT tiles per row
   float wM3, hM3, fxl, fyl, cxl, cyl, fxli, fyli;
   int affA_fixed, affB_fixed;
   int jfix;                 // 1 (default): the fused kernel refreshes EFResidual::J IN PLACE (J[jsel]) instead of writing the other buffer and
@@ -147,17 +147,12 @@ __device__ __forceinline__ bool ba_finished_lin(const BaDev& B) { return B.finis
 // conditional kernels of the energy-gated loop: cond = 0 always, 1 only when the step was accepted, 2 only when it was rejected
 __device__ __forceinline__ bool ba_gate_skip(const BaDev& B, int cond) { return cond != 0 && (ba_finished_lin(B) || B.opt->gate != cond); }
 
-// Float offset of group g (0..18, one float4) of residual i in a RawResidualJacobian buffer of S = nrp residual slots.
-//   blocked (default): the 19 groups of 64 consecutive residuals form ONE contiguous 19 KiB block — a wave of the fused kernel streams
-//                      its records into one stretch of memory instead of into 19 streams 4 S floats apart;
-//   -DSDSO_J_SOA     : group-major over the whole window (rounds 1-2), kept for A/B.
+// Float offset of group g (0..18, one float4) of residual i in a RawResidualJacobian buffer of S = nrp residual slots: the 19 groups
+// of 64 consecutive residuals form ONE contiguous 19 KiB block — a wave of the fused kernel streams its records into one stretch of
+// memory instead of into 19 streams 4 S floats apart (the group-major layout of rounds 1-2).
 __host__ __device__ inline size_t j_off(int S, int i, int g) {
-#ifdef SDSO_J_SOA
-  return (size_t)g * 4 * S + 4 * (size_t)i;
-#else
   (void)S;
   return ((size_t)(i >> 6) * 19 + g) * 256 + (size_t)(i & 63) * 4;
-#endif
 }
 
 __host__ __device__ inline size_t acc_off_topA(int nf) { return 0; }

@@ -14,22 +14,14 @@ namespace sdso {
 
 __constant__ int c_pattern[8][2] = {{0, -2}, {-1, -1}, {1, -1}, {-2, 0}, {0, 0}, {2, 0}, {-1, 1}, {0, 2}};
 
-// Workgroup barrier for exchanges that go through LDS only: waits for this wave's LDS traffic, not for its outstanding global
-// stores (`__syncthreads()` drains vmcnt too — microseconds per barrier while a wave still has Jacobian records in flight).
-template <bool LDS_ONLY>
-__device__ __forceinline__ void wg_barrier() {
-  if (LDS_ONLY) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  else __syncthreads();
-}
-template <bool LDS_ONLY = false>
 __device__ __forceinline__ double block_sum_d(double v, double* lds) {
   v = wave_sum(v);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   if (lane == 0) lds[wv] = v;
-  wg_barrier<LDS_ONLY>();
+  __syncthreads();
   double s = 0;
   for (int w = 0; w < (int)(blockDim.x >> 6); w++) s += lds[w];
-  wg_barrier<LDS_ONLY>();
+  __syncthreads();
   return s;
 }
 
@@ -85,8 +77,8 @@ __device__ __forceinline__ float3 interp33_tiled(const float4* __restrict__ img,
     if (STORE) __builtin_nontemporal_store((te_f4){_q.x, _q.y, _q.z, _q.w}, (te_f4*)&JQ(J, S, i, g)); /* streamed, not re-read this iteration */ \
     if (KEEP == 1 || (KEEP == 2 && ((g) < 6 || (g) > 15))) { jl[4 * (g)] = _q.x; jl[4 * (g) + 1] = _q.y; jl[4 * (g) + 2] = _q.z; jl[4 * (g) + 3] = _q.w; } \
   } while (0)
-template <bool STORE, int KEEP, bool TILED>
-__device__ __forceinline__ double linearize_one(const BaDev& B, int i, int h, int t, float* jl, int& ns_out, float* rs = nullptr, bool inplace = false /* fused kernel with BaDev::jfix */) {
+template <bool STORE, int KEEP>
+__device__ __forceinline__ double linearize_one(const BaDev& B, int i, int h, int t, float* jl, int& ns_out, float* rs = nullptr) {
   B.r_newEnergyWO[i] = -1.f;
   ns_out = 1;
   const uint8_t st = B.r_state[i];
@@ -98,7 +90,7 @@ __device__ __forceinline__ double linearize_one(const BaDev& B, int i, int h, in
   const float4 g = B.p_geo[pt];
   const float pu = g.x, pv = g.y, idepth_scaled = g.z, idepth_zero_scaled = g.w;
   const float4* __restrict__ dIl = B.t_img[t];
-  float* __restrict__ J = STORE ? ((B.r_jsel[i] != 0) != inplace ? B.J[0] : B.J[1]) : nullptr;
+  float* __restrict__ J = STORE ? (B.r_jsel[i] != 0 ? B.J[0] : B.J[1]) : nullptr;   // PointFrameResidual::J: the slot EFResidual::J is not in
   const int S = B.nrp;
   const float fxl = B.fxl, fyl = B.fyl, cxl = B.cxl, cyl = B.cyl, fxli = B.fxli, fyli = B.fyli;
 
@@ -179,7 +171,7 @@ __device__ __forceinline__ double linearize_one(const BaDev& B, int i, int h, in
   for (int hb = 0; hb < 8; hb += 4) {
   float3 hits[4];
 #pragma unroll
-  for (int k = 0; k < 4; k++) hits[k] = TILED ? interp33_tiled(dIl, Kus[hb + k], Kvs[hb + k], B.tiledT) : interp33(dIl, Kus[hb + k], Kvs[hb + k], B.w);
+  for (int k = 0; k < 4; k++) hits[k] = interp33_tiled(dIl, Kus[hb + k], Kvs[hb + k], B.tiledT);
 #pragma unroll
   for (int idx = hb; idx < hb + 4; idx++) {
     const float Ku = Kus[idx], Kv = Kvs[idx];
@@ -259,8 +251,7 @@ __device__ __forceinline__ float quad_bcast(float v) {
 // pattern pixel, corner).  The four corner lanes of a pixel exchange their samples inside the quad and evaluate
 // getInterpolatedElement33 (same expression, same order: bit-identical to interp33); the corner-0 lane parks the result for the
 // residual's own lane.  A residual's image lines are touched by exactly one instruction, so they are fetched once.
-template <bool TILED>
-__device__ __forceinline__ void coop_gather_hits(const float4* __restrict__ img, int Tw, bool dead, const float* Ku, const float* Kv, float* wstage) {
+__device__ __forceinline__ void coop_gather_hits(const float4* __restrict__ img, int T, bool dead, const float* Ku, const float* Kv, float* wstage) {
   const int lane = threadIdx.x & 63;
   float2* coords = (float2*)wstage;
   float* hits = wstage + CG_COORD_FLOATS;
@@ -280,7 +271,7 @@ __device__ __forceinline__ void coop_gather_hits(const float4* __restrict__ img,
       q[r].x = 0; q[r].y = 0; q[r].z = 0;
       if (cx[r].x >= 0) {
         const int x = (int)cx[r].x + (c & 1), y = (int)cx[r].y + (c >> 1);
-        q[r] = *(const px3*)(img + (TILED ? tiled_index(x, y, Tw) : x + y * Tw));
+        q[r] = *(const px3*)(img + tiled_index(x, y, T));
       }
     }
 #pragma unroll
@@ -310,10 +301,8 @@ __device__ __forceinline__ void coop_gather_hits(const float4* __restrict__ img,
   }
   cg_wave_sync();
 }
-// what a persistent workgroup requested for this chunk while it worked on the previous one (SDSO_LIN_PERSIST): r_state, r_point, p_geo
-struct LinPre { int st, pt; float4 geo; };
-template <bool STORE, int KEEP, bool TILED>
-__device__ __forceinline__ double linearize_coop(const BaDev& B, int i, bool live, int h, int t, float* jl, int& ns_out, float* rs, float* wstage, const LinPre* have = nullptr) {
+template <bool STORE, int KEEP>
+__device__ __forceinline__ double linearize_coop(const BaDev& B, int i, bool live, int h, int t, float* jl, int& ns_out, float* rs, float* wstage) {
   ns_out = 1;
   bool dead = !live;
   double ret = 0;
@@ -333,15 +322,11 @@ __device__ __forceinline__ double linearize_coop(const BaDev& B, int i, bool liv
   float* __restrict__ J = nullptr;
   if (!dead) do {
   B.r_newEnergyWO[i] = -1.f;
-  const uint8_t st = have ? (uint8_t)have->st : B.r_state[i];
+  const uint8_t st = B.r_state[i];
   if (st == 1) { B.r_newState[i] = 1; ret = (double)B.r_energy[i]; dead = true; break; }
-  const int pt = have ? have->pt : B.r_point[i];
+  const int pt = B.r_point[i];
   const float* KRKi = pre; const float* Kt = pre + 9; const float* R0 = pre + 12; const float* t0 = pre + 21;
-#if defined(SDSO_LIN_PERSIST) && SDSO_LIN_PERSIST < 2
-  const float4 g = B.p_geo[pt];                  // (light form: only the chunk descriptor, r_state and r_point are requested ahead)
-#else
-  const float4 g = have ? have->geo : B.p_geo[pt];
-#endif
+  const float4 g = B.p_geo[pt];
   const float pu = g.x, pv = g.y, idepth_scaled = g.z, idepth_zero_scaled = g.w;
   J = STORE ? ((B.r_jsel[i] != 0) != (B.jfix != 0) ? B.J[0] : B.J[1]) : nullptr;   // jfix: EFResidual::J refreshed in place (ba_kernels.h)
   const float fxl = B.fxl, fyl = B.fyl, cxl = B.cxl, cyl = B.cyl, fxli = B.fxli, fyli = B.fyli;
@@ -383,7 +368,7 @@ __device__ __forceinline__ double linearize_coop(const BaDev& B, int i, bool liv
   }
   if (oob) { B.r_newState[i] = 1; ret = (double)B.r_energy[i]; dead = true; break; }
   } while (0);
-  coop_gather_hits<TILED>(dIl, TILED ? B.tiledT : B.w, dead, Kus, Kvs, wstage);
+  coop_gather_hits(dIl, B.tiledT, dead, Kus, Kvs, wstage);
   {
   if (!dead) {
   const float* hstage = wstage + CG_COORD_FLOATS + (threadIdx.x & 63);
@@ -399,35 +384,6 @@ __device__ __forceinline__ double linearize_coop(const BaDev& B, int i, bool liv
     energyLeft += wgt * wgt * hw * residual * residual * (2 - hw);
     if (hw < 1) hw = sqrtf(hw);
     hw = hw * wgt;
-#ifdef SDSO_LIN_PK
-    // A/B (round 6, verdict item 5b): the (dx, dy) pairs of the per-pixel sums as two-float vectors -> v_pk_mul_f32 / v_pk_add_f32.  Every product
-    // and every sum is the scalar statement's, in its order (contraction is off: no packed fma): bit-identical.  profiles/r06_lin_pk_ab.txt
-    typedef float pk2 __attribute__((ext_vector_type(2)));
-    pk2 hyz = {hit.y, hit.z};
-    hyz = hyz * hw;
-    hit.y = hyz.x; hit.z = hyz.y;
-    SETQ(6 + idx, residual * hw, hit.y, hit.z, B.affA_fixed ? 0.f : drdA * hw);   // resF, JIdx[0], JIdx[1], JabF[0]
-    jab1[idx] = B.affB_fixed ? 0.f : hw;
-    if (KEEP == 2) {
-      const float ra = residual * hw;
-      const pk2 r01 = (pk2){rs[0], rs[1]} + ra * hyz;
-      rs[0] = r01.x; rs[1] = r01.y;
-      rs[2] += ra * (B.affA_fixed ? 0.f : drdA * hw); rs[3] += ra * jab1[idx];
-      rs[4] += ra * ra;
-    }
-    const pk2 sq = hyz * hyz;
-    const pk2 jj = (pk2){JIdxJIdx_00, JIdxJIdx_11} + sq;
-    JIdxJIdx_00 = jj.x; JIdxJIdx_11 = jj.y;
-    JIdxJIdx_10 += hit.y * hit.z;
-    const pk2 a0 = (pk2){JabJIdx_00, JabJIdx_01} + (drdA * hw) * hyz;
-    JabJIdx_00 = a0.x; JabJIdx_01 = a0.y;
-    const pk2 a1 = (pk2){JabJIdx_10, JabJIdx_11} + hw * hyz;
-    JabJIdx_10 = a1.x; JabJIdx_11 = a1.y;
-    JabJab_00 += drdA * drdA * hw * hw;
-    JabJab_01 += drdA * hw * hw;
-    JabJab_11 += hw * hw;
-    wJI2_sum += hw * hw * (sq.x + sq.y);
-#else
     hit.y *= hw;
     hit.z *= hw;
     SETQ(6 + idx, residual * hw, hit.y, hit.z, B.affA_fixed ? 0.f : drdA * hw);   // resF, JIdx[0], JIdx[1], JabF[0]
@@ -449,7 +405,6 @@ __device__ __forceinline__ double linearize_coop(const BaDev& B, int i, bool liv
     JabJab_01 += drdA * hw * hw;
     JabJab_11 += hw * hw;
     wJI2_sum += hw * hw * (hit.y * hit.y + hit.z * hit.z);
-#endif
   }
   }
   }
@@ -502,7 +457,6 @@ __device__ __forceinline__ double linearize_coop(const BaDev& B, int i, bool liv
 }
 #undef SETQ
 
-template <bool TILED>
 __global__ __launch_bounds__(BA_BLOCK) void k_ba_linearize(const BaDev* __restrict__ wins, int cond = 0) {
   const BaDev& B = wins[blockIdx.y];
   if (ba_finished_lin(B) || ba_gate_skip(B, cond)) return;   // (a window whose resident loop has ended is left alone)
@@ -511,7 +465,7 @@ __global__ __launch_bounds__(BA_BLOCK) void k_ba_linearize(const BaDev* __restri
   const int i = blockIdx.x * BA_BLOCK + threadIdx.x;
   double e = 0;
   int ns;
-  if (i < B.nr && !B.r_lin[i]) e = linearize_one<true, 0, TILED>(B, i, B.r_host[i], B.r_target[i], nullptr, ns);
+  if (i < B.nr && !B.r_lin[i]) e = linearize_one<true, 0>(B, i, B.r_host[i], B.r_target[i], nullptr, ns);
   e = block_sum_d(e, lds);
   if (threadIdx.x == 0) B.e_part[blockIdx.x] = e;
 }
@@ -701,33 +655,21 @@ constexpr int TE_ROWS = 26;
 constexpr int TE_WAVE_FLOATS = TE_ROWS * TE_STRIDE;
 constexpr int TE_LDS_FLOATS = (BA_BLOCK / 64) * TE_WAVE_FLOATS;
 typedef double te_d4 __attribute__((ext_vector_type(4)));
-// How the cross-residual / cross-point sums are carried (compile-time, A/B: tools/mk_variant.sh <name> -DSDSO_ACC_MODE=k; measured on the
-// 24 windows of tests/diag/truth_spread.py and the 256-window step, profiles/r06_acc_modes.txt):
-//   1 (default)  v_mfma_f64_16x16x4_f64 throughout: first pose update 1.4e-6 (median) from the f64-accumulator truth, the CPU float path
-//                1.3e-5; +8 us on k_ba_lin_fused, +10 us on k_ba_sc_host per 256-window step (the f64 form runs at half the fp32 rate);
-//   2            fp32 MFMA over 16-term chains from a zero accumulator, the chains added in f64 on the VALU: free in time, but a chain's
-//                error grows with its partial sums, not with its length alone — 6.4e-6, half way;
-//   0            one fp32 chain per wave (rounds 1-5): 1.1e-5.
-#ifndef SDSO_ACC_MODE
-#define SDSO_ACC_MODE 1
-#endif
-constexpr int ACC_MODE = SDSO_ACC_MODE;
-#ifndef SDSO_ACC_MODE_SC
-#define SDSO_ACC_MODE_SC SDSO_ACC_MODE
-#endif
-constexpr int ACC_MODE_SC = SDSO_ACC_MODE_SC;      // the Schur kernel's own choice (A/B: top sums in f64 MFMA, Schur sums in short fp32 chains)
+// Why f64 MFMA for the cross-residual / cross-point sums (measured on the 24 windows of tests/diag/truth_spread.py and the 256-window step,
+// profiles/r06_acc_modes.txt): first pose update 1.4e-6 (median) from the f64-accumulator truth, the CPU float path 1.3e-5; +8 us on
+// k_ba_lin_fused, +10 us on k_ba_sc_host per 256-window step (the f64 form runs at half the fp32 rate).  fp32 MFMA over 16-term chains added
+// in f64 was free in time but only half way (6.4e-6: a chain's error grows with its partial sums, not with its length alone); one fp32 chain
+// per wave (rounds 1-5) 1.1e-5.
 static_assert(TE_LDS_FLOATS * 4 >= ((BA_BLOCK / 64) * 256 + BA_BLOCK / 64) * 8, "the waves' f64 tiles lie over the panels");
 
-template <bool LDS_ONLY = false>
 __device__ __forceinline__ void top_emit(const BaDev& B, const float* x, const float* y, float a, float b, float c, float TR00, float TR10, float TR01,
-                                         float TR11, float TR02, float TR12, const float* br, bool on, float* stage, int chunk = -1 /* default: blockIdx.x */) {
-  if (chunk < 0) chunk = (int)blockIdx.x;
+                                         float TR11, float TR02, float TR12, const float* br, bool on, float* stage) {
+  const int chunk = blockIdx.x;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   float* S = stage + wv * TE_WAVE_FLOATS;
   const int m = lane & 15, kq = lane >> 4;
   const int mu = m < 10 ? m : 9;
-  te_d4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};   // ACC_MODE 1: D[i][j], i = lane/16 + 4 v; otherwise i = 4 (lane/16) + v
-  te_f4 accf = {0.f, 0.f, 0.f, 0.f};
+  te_d4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};   // D[i][j], i = lane/16 + 4 v
   const unsigned long long onmask = __ballot(on);
 #pragma unroll
   for (int ph = 0; ph < 2; ph++) {
@@ -741,49 +683,23 @@ __device__ __forceinline__ void top_emit(const BaDev& B, const float* x, const f
     S[22 * TE_STRIDE + lane] = ph ? TR12 : TR02;
 #pragma unroll
     for (int q = 0; q < 3; q++) S[(23 + q) * TE_STRIDE + lane] = br[3 * ph + q];
-    wg_barrier<LDS_ONLY>();
+    __syncthreads();
     const float one = (m == 10 + ph) ? 1.f : 0.f;
-    if (ACC_MODE == 1) {
 #pragma unroll
-      for (int s4 = 0; s4 < 16; s4 += 2) {
-        float av0 = S[mu * TE_STRIDE + 4 * s4 + kq], av1 = S[mu * TE_STRIDE + 4 * s4 + 4 + kq];
-        av0 = m < 10 ? av0 : one; av1 = m < 10 ? av1 : one;
-        const float bv0 = S[(10 + m) * TE_STRIDE + 4 * s4 + kq], bv1 = S[(10 + m) * TE_STRIDE + 4 * s4 + 4 + kq];
-        acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av0, (double)bv0, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av1, (double)bv1, acc1, 0, 0, 0);
-      }
-    } else {
-      // four chains of four steps (16 residuals each), two in flight; a chain's result joins the f64 sum while the next ones run
-      te_f4 ch[4];
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        ch[q] = (te_f4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s4 = 4 * q; s4 < 4 * q + 4; s4++) {
-          float av = S[mu * TE_STRIDE + 4 * s4 + kq];
-          av = m < 10 ? av : one;
-          const float bv = S[(10 + m) * TE_STRIDE + 4 * s4 + kq];
-          if (ACC_MODE == 0) accf = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, accf, 0, 0, 0);
-          else ch[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, ch[q], 0, 0, 0);
-        }
-      }
-      if (ACC_MODE == 2) {
-#pragma unroll
-        for (int q = 0; q < 4; q++)
-#pragma unroll
-          for (int v = 0; v < 4; v++) acc0[v] += (double)ch[q][v];
-      }
+    for (int s4 = 0; s4 < 16; s4 += 2) {
+      float av0 = S[mu * TE_STRIDE + 4 * s4 + kq], av1 = S[mu * TE_STRIDE + 4 * s4 + 4 + kq];
+      av0 = m < 10 ? av0 : one; av1 = m < 10 ? av1 : one;
+      const float bv0 = S[(10 + m) * TE_STRIDE + 4 * s4 + kq], bv1 = S[(10 + m) * TE_STRIDE + 4 * s4 + 4 + kq];
+      acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av0, (double)bv0, acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av1, (double)bv1, acc1, 0, 0, 0);
     }
-    wg_barrier<LDS_ONLY>();
+    __syncthreads();
   }
   double* R = (double*)stage;
 #pragma unroll
-  for (int v = 0; v < 4; v++) {
-    if (ACC_MODE == 1) R[wv * 256 + (kq + 4 * v) * 16 + m] = acc0[v] + acc1[v];
-    else R[wv * 256 + (4 * kq + v) * 16 + m] = ACC_MODE == 0 ? (double)accf[v] : acc0[v];
-  }
+  for (int v = 0; v < 4; v++) R[wv * 256 + (kq + 4 * v) * 16 + m] = acc0[v] + acc1[v];
   if (lane == 0) R[(BA_BLOCK / 64) * 256 + wv] = (double)__popcll(onmask);
-  wg_barrier<LDS_ONLY>();
+  __syncthreads();
   if (threadIdx.x < 92) {
     const int t = threadIdx.x;
     int off;
@@ -894,56 +810,26 @@ __global__ __launch_bounds__(BA_BLOCK) void k_ba_accum_top(const BaDev* __restri
 // Workgroups per CU: four without the Jacobian stores (124 VGPRs, 40 KB of LDS each); with them the kernel needs 152 VGPRs
 // (capping it at 128 spills 22-38 of them and loses more than the fourth wave per SIMD gains), so three.
 // The 32 taps of a residual come in through the cooperative quad gather (linearize_coop).  (Rounds 1-4 kept two more gathers for A/B — one
-// residual's taps on one lane, and LDS-DMA rounds; both lost or tied, profiles/README.md.)
+// residual's taps on one lane, and LDS-DMA rounds; both lost or tied, profiles/README.md.)  One chunk per workgroup: a persistent workgroup
+// that requested the next chunk's inputs under the current one's work was 26-28 % slower (spills at three waves per SIMD,
+// profiles/r06_lin_pk_ab.txt).
 // The workgroup barriers behind the linearisation exchange data through LDS only (the gather stage handed over to the reduction's panels, the
-// energy sum, the waves' tiles).  -DSDSO_LIN_LDS_BARRIERS=1 makes them wait for the wave's LDS traffic only, not for its outstanding
-// Jacobian-record stores (`__syncthreads()` is s_waitcnt vmcnt(0) lgkmcnt(0) + s_barrier) — measured: no difference (0.772-0.777 against
-// 0.770-0.774 ms, profiles/r06_lin_barriers_ab.txt: two other workgroups per CU run under a wave's wait), so the plain barriers stay.
-#ifndef SDSO_LIN_LDS_BARRIERS
-#define SDSO_LIN_LDS_BARRIERS 0
-#endif
-constexpr bool LIN_LDS_BARRIERS = SDSO_LIN_LDS_BARRIERS != 0;
-template <bool MATERIALIZE, bool TILED>
+// energy sum, the waves' tiles).  They are plain `__syncthreads()` (s_waitcnt vmcnt(0) lgkmcnt(0) + s_barrier), which also waits for the
+// wave's outstanding Jacobian-record stores; waiting for the LDS traffic alone made no difference (0.772-0.777 against 0.770-0.774 ms,
+// profiles/r06_lin_barriers_ab.txt: two other workgroups per CU run under a wave's wait).
+template <bool MATERIALIZE>
 __global__ __launch_bounds__(BA_BLOCK, (MATERIALIZE ? 3 : 4)) void k_ba_lin_fused(const BaDev* __restrict__ wins) {
-  constexpr bool COOP = true;
   // by-value copy first: every pointer of the descriptor is read before the kernel's first store, so the
   // compiler can prove them global (global_load / s_load instead of flat_load) and keep them in SGPRs
   const BaDev B = wins[blockIdx.y];
   if (ba_finished_lin(B)) return;
   if ((int)blockIdx.x >= B.nchunks) return;
-  constexpr int STAGE_FLOATS = (BA_BLOCK / 64) * (COOP ? CG_WAVE_FLOATS : 0);
+  constexpr int STAGE_FLOATS = (BA_BLOCK / 64) * CG_WAVE_FLOATS;
   constexpr int RED_FLOATS = TE_LDS_FLOATS > STAGE_FLOATS ? TE_LDS_FLOATS : STAGE_FLOATS;
   __shared__ float red[RED_FLOATS];    // the gather stage of the linearisation, then the MFMA panels of the reduction
   double* const lds = (double*)red;    // (the energy reduction runs between the two uses; 40 KB in all = four workgroups per CU)
-#ifdef SDSO_LIN_PERSIST
-  // A/B (round 6, verdict item 5a): a persistent workgroup walks the chunks blockIdx.x, blockIdx.x + gridDim.x, ... of its window (launched with
-  // half the chunks as grid: two chunks per workgroup) and requests the NEXT chunk's descriptor, r_state / r_lin / r_point at the top of the current
-  // one and its p_geo once the current chunk's taps are through — three dependent round trips of the next chunk under the current one's work.
-  int4 chN = B.chunks[blockIdx.x];
-  bool liveN = false; LinPre preN{1, 0, make_float4(0.f, 0.f, 0.f, 0.f)};
-  {
-    const int i0 = chN.y + threadIdx.x;
-    liveN = (int)threadIdx.x < chN.z && !B.r_lin[i0];
-    if (liveN) { preN.st = B.r_state[i0]; preN.pt = B.r_point[i0]; }
-#if SDSO_LIN_PERSIST >= 2
-    if (liveN) preN.geo = B.p_geo[preN.pt];
-#endif
-  }
-  for (int chunk = blockIdx.x; chunk < B.nchunks; chunk += gridDim.x) {
-  const int4 ch = chN;
-  const bool live = liveN;
-  const LinPre preC = preN;
-  const int nxt = chunk + (int)gridDim.x;
-  if (nxt < B.nchunks) {
-    chN = B.chunks[nxt];
-    const int in = chN.y + threadIdx.x;
-    liveN = (int)threadIdx.x < chN.z && !B.r_lin[in];
-    if (liveN) { preN.st = B.r_state[in]; preN.pt = B.r_point[in]; }
-  }
-#else
   const int chunk = blockIdx.x;
   const int4 ch = B.chunks[blockIdx.x];
-#endif
   const int pair = __builtin_amdgcn_readfirstlane(ch.x);   // one (host,target) per workgroup: precalc, image, thresholds are wave-uniform
   const int i = ch.y + threadIdx.x;
   float x[10], y[10], a = 0, b = 0, c = 0;
@@ -953,26 +839,14 @@ __global__ __launch_bounds__(BA_BLOCK, (MATERIALIZE ? 3 : 4)) void k_ba_lin_fuse
   for (int k = 0; k < 10; k++) { x[k] = 0; y[k] = 0; }
   bool on = false;
   double e = 0;
-#ifndef SDSO_LIN_PERSIST
   const bool live = (int)threadIdx.x < ch.z && !B.r_lin[i];
-#endif
   float jl[76];
   float rs5[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
   int ns = 1;
   uint8_t st = 1;
-  if (COOP) {
-#ifdef SDSO_LIN_PERSIST
-    if (live) st = (uint8_t)preC.st;
-    e = linearize_coop<MATERIALIZE, 2, TILED>(B, i, live, pair % B.nf, pair / B.nf, jl, ns, rs5, red + (threadIdx.x >> 6) * CG_WAVE_FLOATS, &preC);
-#if SDSO_LIN_PERSIST >= 2
-    if (nxt < B.nchunks && liveN) preN.geo = B.p_geo[preN.pt];      // (the next chunk's point index arrived long ago)
-#endif
-#else
-    if (live) st = B.r_state[i];
-    e = linearize_coop<MATERIALIZE, 2, TILED>(B, i, live, pair % B.nf, pair / B.nf, jl, ns, rs5, red + (threadIdx.x >> 6) * CG_WAVE_FLOATS);
-#endif
-    wg_barrier<LIN_LDS_BARRIERS>();   // the reduction below reuses the stage of all waves
-  }
+  if (live) st = B.r_state[i];
+  e = linearize_coop<MATERIALIZE, 2>(B, i, live, pair % B.nf, pair / B.nf, jl, ns, rs5, red + (threadIdx.x >> 6) * CG_WAVE_FLOATS);
+  __syncthreads();   // the reduction below reuses the stage of all waves
   if (live) {
     float* rec = B.r_rec + (size_t)B.r_orig[i] * 16;
     // the 64-byte record of this residual (BaDev::r_rec): written once, whole, at the end (four 16-byte stores of one half line)
@@ -1022,14 +896,10 @@ __global__ __launch_bounds__(BA_BLOCK, (MATERIALIZE ? 3 : 4)) void k_ba_lin_fuse
       *(float4*)(rec + 12) = make_float4(rhcd[2], rhcd[3], (float)act, 0.f);
     }
   }
-  e = block_sum_d<LIN_LDS_BARRIERS>(e, lds);
+  e = block_sum_d(e, lds);
   if (threadIdx.x == 0) B.e_part[chunk] = e;
-  wg_barrier<LIN_LDS_BARRIERS>();
-  top_emit<LIN_LDS_BARRIERS>(B, x, y, a, b, c, TR00, TR10, TR01, TR11, TR02, TR12, br, on, red, chunk);
-#ifdef SDSO_LIN_PERSIST
-  __syncthreads();   // the next chunk's gather stage lies over the panels
-  }
-#endif
+  __syncthreads();
+  top_emit(B, x, y, a, b, c, TR00, TR10, TR01, TR11, TR02, TR12, br, on, red);
 }
 
 // ------------------------------------------------------------------ linearised energy (EnergyFunctional::calcLEnergyPt, EnergyFunctional.cpp:354-417)
@@ -1122,7 +992,7 @@ __global__ __launch_bounds__(128) void k_ba_zero_topL(const BaDev* __restrict__ 
 //            point's target -> record map (a word of nibbles) for phase 2.  The quad exchanges H / `any` by DPP and stores the point's 32 bytes
 //            of BaDev::p_out ([8..13], the sums of linearised / marginalised residuals, only when such residuals exist or their stale values
 //            have to be cleared) and idepth_hessian / the active-record mask / `maxRelBaseline = 0` (:44-48) in BaDev::p_track.
-//   phase 2  Z^T diag(HdiF) Z on the matrix cores (v_mfma_f64_16x16x4_f64 since round 6 — ACC_MODE_SC —, K = 4 points), Z = [JpJdF of the 7 targets a
+//   phase 2  Z^T diag(HdiF) Z on the matrix cores (v_mfma_f64_16x16x4_f64 since round 6, K = 4 points), Z = [JpJdF of the 7 targets a
 //            point can observe (never its host) | Hcd | bdSumF] (61 columns in a 4 x 4 grid of 16-column tiles): only the 10 tiles on and above the
 //            diagonal are accumulated (80 accumulator registers in f64); the bins below the
 //            diagonal are written as mirror images, which makes accD(i,j,k) == accD(i,k,j)^T hold EXACTLY as it does in the reference
@@ -1172,13 +1042,11 @@ __global__ __launch_bounds__(BA_BLOCK, 2) void k_ba_sc_host(const BaDev* __restr
   float* const bufT = bufA + 2 * SCH_REC;
   float (*pt)[8] = reinterpret_cast<float (*)[8]>(bufT + SCH_REC);
   const int pb = B.host_pt_beg[h], pe = B.host_pt_beg[h + 1];     // (in the descriptor itself: no dependent round trip before the first DMA)
-  // the sums over the points are carried in f64 like the top sums (top_emit, ACC_MODE_SC): a group's 16 points are one short fp32 MFMA chain
-  // per tile, the groups' tiles are added in f64 (mode 1: f64 MFMAs on the float operands converted exactly, (w z_a) z_b with the
-  // product w z_a exact); ONE rounding to float when the bins are written
+  // the sums over the points are carried in f64 like the top sums (top_emit): f64 MFMAs on the float operands converted exactly,
+  // (w z_a) z_b with the product w z_a exact; ONE rounding to float when the bins are written
   te_d4 acc[SC_NT];
-  te_f4 grp[SC_NT];                              // mode 2: the tiles of one group; mode 0: the running float sums
 #pragma unroll
-  for (int t = 0; t < SC_NT; t++) { acc[t] = (te_d4){0.0, 0.0, 0.0, 0.0}; grp[t] = (te_f4){0.f, 0.f, 0.f, 0.f}; }
+  for (int t = 0; t < SC_NT; t++) acc[t] = (te_d4){0.0, 0.0, 0.0, 0.0};
   auto sc_ut = [](int a, int b) { return a * 4 - (a * (a - 1)) / 2 + (b - a); };   // index of the upper tile (a <= b): 0..9
   const int ci = lane & 15, kq = lane >> 4;
   const int tsub = ci >> 3, asub = ci & 7;
@@ -1362,39 +1230,15 @@ __global__ __launch_bounds__(BA_BLOCK, 2) void k_ba_sc_host(const BaDev* __restr
       for (int u = 0; u < 4; u++)
 #pragma unroll
         for (int tt = 0; tt < 4; tt++) zz[u][tt] = oks[u][tt] ? zz[u][tt] : 0.f;
-      if (ACC_MODE_SC == 1) {
 #pragma unroll
-        for (int u = 0; u < 4; u++) {
-          double za[4], zd[4];
+      for (int u = 0; u < 4; u++) {
+        double za[4], zd[4];
 #pragma unroll
-          for (int tt = 0; tt < 4; tt++) { zd[tt] = (double)zz[u][tt]; za[tt] = (double)hx[u] * zd[tt]; }
+        for (int tt = 0; tt < 4; tt++) { zd[tt] = (double)zz[u][tt]; za[tt] = (double)hx[u] * zd[tt]; }
 #pragma unroll
-          for (int a = 0; a < 4; a++) {
+        for (int a = 0; a < 4; a++) {
 #pragma unroll
-            for (int b = a; b < 4; b++) acc[sc_ut(a, b)] = __builtin_amdgcn_mfma_f64_16x16x4f64(za[a], zd[b], acc[sc_ut(a, b)], 0, 0, 0);
-          }
-        }
-      } else {
-        if (ACC_MODE_SC == 2) {
-#pragma unroll
-          for (int t = 0; t < SC_NT; t++) grp[t] = (te_f4){0.f, 0.f, 0.f, 0.f};
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-          float za[4];
-#pragma unroll
-          for (int tt = 0; tt < 4; tt++) za[tt] = hx[u] * zz[u][tt];
-#pragma unroll
-          for (int a = 0; a < 4; a++) {
-#pragma unroll
-            for (int b = a; b < 4; b++) grp[sc_ut(a, b)] = __builtin_amdgcn_mfma_f32_16x16x4f32(za[a], zz[u][b], grp[sc_ut(a, b)], 0, 0, 0);
-          }
-        }
-        if (ACC_MODE_SC == 2) {
-#pragma unroll
-          for (int t = 0; t < SC_NT; t++)
-#pragma unroll
-            for (int v = 0; v < 4; v++) acc[t][v] += (double)grp[t][v];
+          for (int b = a; b < 4; b++) acc[sc_ut(a, b)] = __builtin_amdgcn_mfma_f64_16x16x4f64(za[a], zd[b], acc[sc_ut(a, b)], 0, 0, 0);
         }
       }
     }
@@ -1405,15 +1249,9 @@ __global__ __launch_bounds__(BA_BLOCK, 2) void k_ba_sc_host(const BaDev* __restr
   }
   SCS();
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (ACC_MODE_SC == 0) {
-#pragma unroll
-    for (int t = 0; t < SC_NT; t++)
-#pragma unroll
-      for (int v = 0; v < 4; v++) acc[t][v] = (double)grp[t][v];
-  }
   // ---- the host's bins from ONE wave's accumulators (WPH: this wave's; otherwise wave 0's after the tree), rounded to float: d[v] of lane
-  // (kq, ci) = D[16 a + 4 kq + v][16 b + ci] of tile (a, b) — four consecutive rows per lane (ACC_MODE_SC 1: the f64 MFMA leaves rows
-  // kq + 4 v on a lane; its tiles are turned through 1 KB of LDS into that layout first).  Every (t1, t2) block of 256 bytes is covered by
+  // (kq, ci) = D[16 a + 4 kq + v][16 b + ci] of tile (a, b) — four consecutive rows per lane (the f64 MFMA leaves rows kq + 4 v on a lane;
+  // its tiles are turned through 1 KB of LDS into that layout first).  Every (t1, t2) block of 256 bytes is covered by
   // the four stores of its tile; the blocks below the diagonal are float4s of the mirrored tile; a tile ON the diagonal takes its lower
   // triangle from the mirror image too: D(r, c) and D(c, r) differ in the last bit ((w z_r) z_c against (w z_c) z_r), and the stitch relies
   // on accD(h, i, j) == accD(h, j, i)^T exactly.  The blocks of the host's own (absent) target are zeros.
@@ -1430,24 +1268,18 @@ __global__ __launch_bounds__(BA_BLOCK, 2) void k_ba_sc_host(const BaDev* __restr
       for (int b = a; b < 4; b++) {
         const int t2p = 2 * b + (ci >> 3), t2 = t2p + (t2p >= h ? 1 : 0);
         te_f4 d;
-        {
-          const te_d4 dd = acc[sc_ut(a, b)];
+        const te_d4 dd = acc[sc_ut(a, b)];
 #pragma unroll
-          for (int v = 0; v < 4; v++) d[v] = (float)dd[v];
-          if (ACC_MODE_SC == 1 || a == b) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        for (int v = 0; v < 4; v++) d[v] = (float)dd[v];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
-            for (int v = 0; v < 4; v++) T[(ACC_MODE_SC == 1 ? kq + 4 * v : 4 * kq + v) * 17 + ci] = d[v];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            if (ACC_MODE_SC == 1) {
+        for (int v = 0; v < 4; v++) T[(kq + 4 * v) * 17 + ci] = d[v];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
-              for (int v = 0; v < 4; v++) d[v] = T[(4 * kq + v) * 17 + ci];
-            }
-            if (a == b) {
+        for (int v = 0; v < 4; v++) d[v] = T[(4 * kq + v) * 17 + ci];
+        if (a == b) {
 #pragma unroll
-              for (int v = 0; v < 4; v++) { const float m = T[ci * 17 + 4 * kq + v]; d[v] = (4 * kq + v > ci) ? m : d[v]; }
-            }
-          }
+          for (int v = 0; v < 4; v++) { const float m = T[ci * 17 + 4 * kq + v]; d[v] = (4 * kq + v > ci) ? m : d[v]; }
         }
         if (t1p < 7 && t1 < nf) {
           if (t2p < 7) {

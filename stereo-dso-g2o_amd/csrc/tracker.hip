@@ -419,9 +419,7 @@ static int choose_gx(const sdso_ctx* ctx, int nprob, int maxn) {
   int target = (ctx->n_cu * 8 + nprob - 1) / nprob;            // ~8 workgroups per CU over the batch
   // few, fat workgroups: the per-workgroup epilogue (48-value reduction, partial stores) is amortised over several
   // loop trips (measured on 640 problems: gx 10 -> 65 us, 4 -> 62 us, 1 -> 71 us)
-  int gx = std::max(1, std::min(by_points, target));
-  if (const char* e = dbg_env("SDSO_TRK_GX")) gx = std::max(1, std::min(by_points, atoi(e)));   // experiment
-  return gx;
+  return std::max(1, std::min(by_points, target));
 }
 
 extern "C" int sdso_track_batch_prepare(sdso_ctx* ctx, int nprob, const int* ref_slots, const int* frame_slots, const sdso_track_eval_t* evs) {
