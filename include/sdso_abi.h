@@ -473,6 +473,7 @@ int sdso_ba_get_state(sdso_ctx* ctx, int win, double* state_out /* nf*10 */, flo
  *   sdso_comm_unique_id : rank 0 creates the 128-byte ncclUniqueId; the caller ships it to the other ranks (MPI, sockets, a file ...)
  *   sdso_comm_init      : collective over the nranks processes; binds the communicator to ctx (its device, its stream)
  *   sdso_comm_attach    : a second ctx of the same process / device uses the communicator of `owner`
+ *                         (`owner` must not be re-initialised or destroyed concurrently with this call)
  *   sdso_ba_allreduce   : in-place sum of the batch's contiguous block (sdso_ba_batch_accum_dev) over the ranks
  *   sdso_ba_allreduce_window : the same for one window's block (sdso_ba_accum_dev), between sdso_ba_accumulate and sdso_ba_solve
  * A single-iteration exchange sums everything solveSystemF needs.  The energy threshold of the newest frame (setNewFrameEnergyTH,

@@ -97,9 +97,18 @@ static int dmalloc(sdso_ctx* ctx, BaWindowDev* W, void** p, size_t bytes, bool z
 // synchronise the stream — the buffer is only waited for when its turn comes again, two reservations later.  A caller that does not commit
 // synchronises the stream itself before the ctx reserves again (upload_tables, opt_finish).
 struct StageBuf { char* p[2] = {nullptr, nullptr}; size_t cap[2] = {0, 0}; hipEvent_t ev[2] = {nullptr, nullptr}; bool busy[2] = {false, false}; int cur = 0; };
-static std::map<sdso_ctx*, StageBuf> g_stage;
+struct OptBufs;
+struct OptRun;
+// the BA state of a ctx besides its windows (sdso_ctx::ba): created by the first call that needs it, freed with the windows
+struct BaCtxState {
+  StageBuf stage;
+  BaBatch* batch = nullptr;   // sdso_ba_batch_create
+  OptBufs* bufs = nullptr;    // scratch of the resident GN loop
+  OptRun* run = nullptr;      // the batch loop in flight between sdso_ba_batch_optimize_begin and _end
+};
+static BaCtxState& ba_state(sdso_ctx* ctx) { if (!ctx->ba) ctx->ba = new BaCtxState(); return *ctx->ba; }
 static int stage_reserve(sdso_ctx* ctx, size_t bytes, char** out) {
-  StageBuf& b = reg_get(g_stage, ctx);
+  StageBuf& b = ba_state(ctx).stage;
   b.cur ^= 1;
   const int k = b.cur;
   if (b.busy[k]) { SDSO_HIP(ctx, hipEventSynchronize(b.ev[k])); b.busy[k] = false; }
@@ -114,16 +123,14 @@ static int stage_reserve(sdso_ctx* ctx, size_t bytes, char** out) {
   return SDSO_OK;
 }
 static int stage_commit(sdso_ctx* ctx) {      // everything that reads the latest reservation has been enqueued on ctx->stream
-  StageBuf& b = reg_get(g_stage, ctx);
+  StageBuf& b = ba_state(ctx).stage;
   const int k = b.cur;
   if (!b.ev[k]) SDSO_HIP(ctx, hipEventCreateWithFlags(&b.ev[k], hipEventDisableTiming));
   SDSO_HIP(ctx, hipEventRecord(b.ev[k], ctx->stream));
   b.busy[k] = true;
   return SDSO_OK;
 }
-static void stage_free(sdso_ctx* ctx) {
-  StageBuf b;
-  if (!reg_take(g_stage, ctx, b)) return;
+static void stage_free(StageBuf& b) {
   for (int k = 0; k < 2; k++) { if (b.ev[k]) hipEventDestroy(b.ev[k]); if (b.p[k]) hipHostFree(b.p[k]); }
 }
 #define DM(ptr, T, count)                                                   \
@@ -161,16 +168,17 @@ struct BaBatch {
   bool scattered = false;        // the latest sdso_ba_allreduce was the reduce-scatter: only this rank's windows hold summed accumulators
   bool keep_system = false;      // sdso_ba_batch_keep_system: the resident loop's solves also write lastHS / lastbS (37 KB per window and iteration)
 };
-static std::map<sdso_ctx*, BaBatch*> g_batches;
+static BaBatch* get_batch(sdso_ctx* ctx) { return ctx && ctx->ba ? ctx->ba->batch : nullptr; }
 void free_optrun(sdso_ctx* ctx);    // the resident GN loop's bookkeeping (end of this file)
-void free_optbufs(sdso_ctx* ctx);
+void free_optbufs(OptBufs* b);
 int optimize_resident_single(sdso_ctx* ctx, BaWindowDev* W, int mnumOptIts, sdso_ba_opt_result_t* res);
 // Dissolve the ctx's batch: every member window gets its own accumulator block back (host descriptor and its device copy),
 // so later per-window calls never touch the freed batch block.
 static void free_batch(sdso_ctx* ctx) {
-  BaBatch* taken = nullptr;
   free_optrun(ctx);   // a resident loop over the batch ends with it
-  if (!reg_take(g_batches, ctx, taken) || !taken) return;
+  BaBatch* taken = get_batch(ctx);
+  if (!taken) return;
+  ctx->ba->batch = nullptr;
   hipStreamSynchronize(ctx->stream);
   for (BaWindowDev* W : taken->W) {
     W->d.accum = W->accum_own;
@@ -184,8 +192,7 @@ static void free_batch(sdso_ctx* ctx) {
 }
 void release_all_windows(sdso_ctx* ctx) {
   free_batch(ctx);
-  free_optbufs(ctx);
-  stage_free(ctx);
+  if (ctx->ba) { free_optbufs(ctx->ba->bufs); stage_free(ctx->ba->stage); delete ctx->ba; ctx->ba = nullptr; }
   for (auto& kv : ctx->wins) free_window(ctx, kv.second);
   ctx->wins.clear();
 }
@@ -699,7 +706,7 @@ static void ensure_folded(sdso_ctx* ctx, BaBatch* Bt) {
   launch_fold_deferred(ctx, Bt->L);
   Bt->folded = true;
 }
-static void ensure_folded_win(sdso_ctx* ctx, BaWindowDev* W) { if (W->in_batch && reg_has(g_batches, ctx)) ensure_folded(ctx, reg_get(g_batches, ctx)); }
+static void ensure_folded_win(sdso_ctx* ctx, BaWindowDev* W) { if (W->in_batch) ensure_folded(ctx, get_batch(ctx)); }
 // bookkeeping for sdso_ba_get_linearization: where the latest linearisation's records are (fetch_jacobians)
 static void mark_linearized(const std::vector<BaWindowDev*>& Ws, bool fused_materialized) {
   for (BaWindowDev* W : Ws) W->j_inplace_last = fused_materialized && W->d.jfix != 0;
@@ -1416,7 +1423,7 @@ extern "C" int sdso_ba_batch_create(sdso_ctx* ctx, int nwin, const int* wins) {
   BaBatch* Bt = new BaBatch();
   Bt->d_arr = d_arr; Bt->d_accum = d_accum; Bt->W = Ws;
   Bt->wins.assign(wins, wins + nwin);
-  reg_get(g_batches, ctx) = Bt;
+  ba_state(ctx).batch = Bt;
   hipMemsetAsync(Bt->d_accum, 0, sizeof(float) * af * nwin, ctx->stream);
   std::vector<BaDev> h(nwin);
   BaLaunch L{};
@@ -1441,7 +1448,6 @@ extern "C" int sdso_ba_batch_create(sdso_ctx* ctx, int nwin, const int* wins) {
   return SDSO_OK;
 }
 namespace sdso {
-static BaBatch* get_batch(sdso_ctx* ctx) { return ctx && reg_has(g_batches, ctx) ? reg_get(g_batches, ctx) : nullptr; }
 // launch descriptor of the batch with the state-dependent flags refreshed
 static const BaLaunch& batch_launch(BaBatch* Bt) {
   Bt->L.any_lin = false;
@@ -1709,10 +1715,8 @@ struct OptBufs {
   float* d_lpart = nullptr; size_t lpart_cap = 0;
   float* d_solrec = nullptr; size_t solrec_cap = 0;
 };
-static std::map<sdso_ctx*, OptBufs*> g_optbufs;
-void free_optbufs(sdso_ctx* ctx) {
-  OptBufs* b = nullptr;
-  if (!reg_take(g_optbufs, ctx, b) || !b) return;
+void free_optbufs(OptBufs* b) {
+  if (!b) return;
   hipFree(b->d_sums); hipFree(b->d_pack); hipFree(b->d_gather); hipFree(b->d_out); hipFree(b->d_lpart); hipFree(b->d_solrec);
   if (b->h_out) hipHostFree(b->h_out);
   delete b;
@@ -1773,8 +1777,8 @@ static int opt_begin(sdso_ctx* ctx, OptRun& R, int stop_on_convergence) {
     R.scatter = want != 0;
   }
   R.sums_stride = 2 * (R.L.max_nblk_pts + 1);
-  if (!reg_has(g_optbufs, ctx)) reg_get(g_optbufs, ctx) = new OptBufs();
-  OptBufs* B = reg_get(g_optbufs, ctx);
+  OptBufs*& B = ba_state(ctx).bufs;
+  if (!B) B = new OptBufs();
   R.B = B;
   const size_t pf = opt_pack_floats(cap);
   int rc;
@@ -1993,7 +1997,6 @@ static bool batch_defers_fold(sdso_ctx* ctx, BaBatch* Bt) { (void)ctx; return ta
 
 // solveSystem + doStepFromBackup + the loop's host part of iteration R.iteration.  Single rank: ONE launch of the fused tail kernel.
 // Sharded windows: tail kernel (stitch, solve, resubstitute, points' step) -> pack -> all-gather -> k_ba_opt_step, as before.
-static std::map<sdso_ctx*, OptRun*> g_optruns;   // the batch loop in flight between sdso_ba_batch_optimize_begin and _end
 static int opt_solve_step(sdso_ctx* ctx, OptRun& R, double lambda, int orth, bool folded) {
   if (!tail_enabled() || R.L.alt || R.momentum) {   // (momentum: the stepsize / the kept step come between the solve and the step — opt_step)
     launch_solve(ctx, R.L, lambda, orth, folded);
@@ -2084,18 +2087,17 @@ int optimize_resident_single(sdso_ctx* ctx, BaWindowDev* W, int mnumOptIts, sdso
 // rank only); anything else takes the all-reduce, whatever mode the batch carries.
 // The decision itself is taken ONCE, in sdso_ba_batch_optimize_begin, from this rank's state AND agreed on by all ranks (opt_begin:
 // ranks that disagree — another exchange mode, SDSO_BA_TAIL, keep_system — would issue ncclReduceScatter against ncclAllReduce and hang).
+static OptRun* get_run(sdso_ctx* ctx) { return ctx && ctx->ba ? ctx->ba->run : nullptr; }
 bool ba_batch_scatter_wanted(sdso_ctx* ctx) {
   BaBatch* Bt = get_batch(ctx);
-  if (!Bt || !reg_has(g_optruns, ctx)) return false;
-  OptRun* R = reg_get(g_optruns, ctx);
-  return R && R->active && R->scatter && R->W == Bt->W;
+  OptRun* R = get_run(ctx);
+  return Bt && R && R->active && R->scatter && R->W == Bt->W;
 }
 void ba_batch_scatter_done(sdso_ctx* ctx) {
   if (BaBatch* Bt = get_batch(ctx)) Bt->scattered = true;
 }
 void free_optrun(sdso_ctx* ctx) {
-  OptRun* r = nullptr;
-  if (reg_take(g_optruns, ctx, r) && r) delete r;
+  if (ctx->ba) { delete ctx->ba->run; ctx->ba->run = nullptr; }
 }
 }  // namespace sdso
 
@@ -2114,12 +2116,12 @@ extern "C" int sdso_ba_batch_optimize_begin(sdso_ctx* ctx, int stop_on_convergen
   R->scatter_local = Bt->exchange_mode == 1;
   int rc = opt_begin(ctx, *R, stop_on_convergence);
   if (rc) { delete R; return rc; }
-  reg_get(g_optruns, ctx) = R;
+  ba_state(ctx).run = R;
   return SDSO_OK;
 }
 extern "C" int sdso_ba_batch_step(sdso_ctx* ctx) {
-  if (!ctx || !reg_has(g_optruns, ctx)) return sdso::fail(ctx, SDSO_ERR_STATE, "sdso_ba_batch_optimize_begin first");
-  OptRun* R = reg_get(g_optruns, ctx);
+  OptRun* R = get_run(ctx);
+  if (!R) return sdso::fail(ctx, SDSO_ERR_STATE, "sdso_ba_batch_optimize_begin first");
   SDSO_REQUIRE(ctx, get_batch(ctx) && get_batch(ctx)->W == R->W, "the batch changed since sdso_ba_batch_optimize_begin");
   SDSO_REQUIRE(ctx, !R->gated, "sdso_ba_batch_step drives the accepted-step flow; energy-gated windows run through sdso_ba_batch_optimize");
   return opt_step(ctx, *R);
@@ -2127,8 +2129,8 @@ extern "C" int sdso_ba_batch_step(sdso_ctx* ctx) {
 // sdso_ba_batch_solve + sdso_ba_batch_step as ONE enqueue: solveSystemF, resubstituteF, doStepFromBackup, setPrecalcValues / setDeltaF /
 // setNewFrameEnergyTH and the break test of the batch's resident loop run in one launch of the fused tail kernel (ba_tail.hip)
 extern "C" int sdso_ba_batch_solve_step(sdso_ctx* ctx, double lambda, int orthogonalize_x) {
-  if (!ctx || !reg_has(g_optruns, ctx)) return sdso::fail(ctx, SDSO_ERR_STATE, "sdso_ba_batch_optimize_begin first");
-  OptRun* R = reg_get(g_optruns, ctx);
+  OptRun* R = get_run(ctx);
+  if (!R) return sdso::fail(ctx, SDSO_ERR_STATE, "sdso_ba_batch_optimize_begin first");
   BaBatch* Bt = get_batch(ctx);
   SDSO_REQUIRE(ctx, Bt && Bt->W == R->W, "the batch changed since sdso_ba_batch_optimize_begin");
   SDSO_REQUIRE(ctx, !R->gated, "sdso_ba_batch_solve_step drives the accepted-step flow; energy-gated windows run through sdso_ba_batch_optimize");
@@ -2139,8 +2141,8 @@ extern "C" int sdso_ba_batch_solve_step(sdso_ctx* ctx, double lambda, int orthog
   return opt_solve_step(ctx, *R, lambda, orthogonalize_x ? 1 : 0, Bt->folded);
 }
 extern "C" int sdso_ba_batch_optimize_end(sdso_ctx* ctx, sdso_ba_opt_result_t* out) {
-  if (!ctx || !reg_has(g_optruns, ctx)) return sdso::fail(ctx, SDSO_ERR_STATE, "sdso_ba_batch_optimize_begin first");
-  OptRun* R = reg_get(g_optruns, ctx);
+  OptRun* R = get_run(ctx);
+  if (!R) return sdso::fail(ctx, SDSO_ERR_STATE, "sdso_ba_batch_optimize_begin first");
   SDSO_REQUIRE(ctx, get_batch(ctx) && get_batch(ctx)->W == R->W, "the batch changed since sdso_ba_batch_optimize_begin");
   R->L = batch_launch(get_batch(ctx));
   const int rc = opt_finish(ctx, *R, out);
@@ -2165,7 +2167,7 @@ extern "C" int sdso_ba_batch_optimize(sdso_ctx* ctx, int mnumOptIts, sdso_ba_opt
   }
   int rc = sdso_ba_batch_optimize_begin(ctx, 1);
   if (rc) return rc;
-  OptRun* R = reg_get(g_optruns, ctx);
+  OptRun* R = get_run(ctx);
   const int N = opt_iterations(R->L.nf, mnumOptIts);
   if (R->gated) {
     if ((rc = opt_gated_start(ctx, *R))) { free_optrun(ctx); return rc; }

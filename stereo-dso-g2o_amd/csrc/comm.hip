@@ -13,7 +13,6 @@
 #include <dlfcn.h>
 #include <cstring>
 #include <rccl/rccl.h>
-#include <map>
 #include <memory>
 #include <vector>
 #include <algorithm>
@@ -84,20 +83,8 @@ struct Comm {
   bool host() const { return h_allreduce != nullptr; }
   ~Comm() { if (comm) { RcclApi* a = rccl_api(nullptr); if (a) a->CommDestroy(comm); } }
 };
-static std::map<sdso_ctx*, std::shared_ptr<Comm>> g_comms;
-void release_comm(sdso_ctx* ctx) {
-  std::shared_ptr<Comm> dying;     // destroyed (ncclCommDestroy may block) after the registry lock is released
-  {
-    std::lock_guard<std::mutex> g(registry_mutex());
-    auto it = g_comms.find(ctx);
-    if (it != g_comms.end()) { dying = std::move(it->second); g_comms.erase(it); }
-  }
-}
-static std::shared_ptr<Comm> comm_of(sdso_ctx* ctx) {
-  std::lock_guard<std::mutex> g(registry_mutex());
-  auto it = g_comms.find(ctx);
-  return it == g_comms.end() ? nullptr : it->second;
-}
+// the ctx lets go of its communicator (sdso_ctx::comm); the last ctx that shares it destroys it (ncclCommDestroy)
+void release_comm(sdso_ctx* ctx) { ctx->comm.reset(); }
 }  // namespace sdso
 
 using namespace sdso;
@@ -105,11 +92,11 @@ using namespace sdso;
 namespace sdso {
 // used by the resident GN loop (ba.hip): ranks of ctx's communicator (1 without one), the all-gather of the per-rank energy / break-test
 // records, and the max over ranks of a host int (collective, synchronises the ctx stream)
-int comm_nranks(sdso_ctx* ctx) { auto c = comm_of(ctx); return c ? c->nranks : 1; }
-int comm_rank(sdso_ctx* ctx) { auto c = comm_of(ctx); return c ? c->rank : 0; }
-bool comm_present(sdso_ctx* ctx) { return comm_of(ctx) != nullptr; }
+int comm_nranks(sdso_ctx* ctx) { return ctx->comm ? ctx->comm->nranks : 1; }
+int comm_rank(sdso_ctx* ctx) { return ctx->comm ? ctx->comm->rank : 0; }
+bool comm_present(sdso_ctx* ctx) { return ctx->comm != nullptr; }
 int comm_allgather_floats(sdso_ctx* ctx, const float* send, float* recv, size_t nfloats) {
-  auto c = comm_of(ctx);
+  Comm* c = ctx->comm.get();
   if (!c) return sdso::fail(ctx, SDSO_ERR_STATE, "no communicator");
   if (c->host()) {
     std::lock_guard<std::mutex> hg(c->h_mutex);
@@ -127,7 +114,7 @@ int comm_allgather_floats(sdso_ctx* ctx, const float* send, float* recv, size_t 
   return SDSO_OK;
 }
 int comm_max_int(sdso_ctx* ctx, int* value) {
-  auto c = comm_of(ctx);
+  Comm* c = ctx->comm.get();
   if (!c) return SDSO_OK;
   if (c->host()) {
     const float mine = (float)*value;                       // capacities are far below 2^24: exact
@@ -179,8 +166,7 @@ extern "C" int sdso_comm_init(sdso_ctx* ctx, int nranks, int rank, const void* i
   ncclUniqueId id;
   std::memcpy(&id, id128, sizeof(id));
   SDSO_NCCL(ctx, a, a->CommInitRank(&c->comm, nranks, id, rank));
-  std::lock_guard<std::mutex> g(registry_mutex());
-  g_comms[ctx] = c;
+  ctx->comm = std::move(c);
   return SDSO_OK;
 }
 
@@ -194,24 +180,22 @@ extern "C" int sdso_comm_init_host(sdso_ctx* ctx, int nranks, int rank, sdso_hos
   auto c = std::make_shared<Comm>();
   c->nranks = nranks; c->rank = rank; c->device = ctx->device;
   c->h_allreduce = allreduce; c->h_allgather = allgather; c->h_user = user;
-  std::lock_guard<std::mutex> g(registry_mutex());
-  g_comms[ctx] = c;
+  ctx->comm = std::move(c);
   return SDSO_OK;
 }
 
 extern "C" int sdso_comm_attach(sdso_ctx* ctx, sdso_ctx* owner) {
   if (!ctx || !owner) return SDSO_ERR_STATE;
-  auto c = comm_of(owner);
+  const std::shared_ptr<Comm> c = owner->comm;
   SDSO_REQUIRE(ctx, c, "the owner context has no communicator");
   SDSO_REQUIRE(ctx, c->device == ctx->device, "contexts that share a communicator must sit on the same device");
-  std::lock_guard<std::mutex> g(registry_mutex());
-  g_comms[ctx] = c;
+  ctx->comm = c;
   return SDSO_OK;
 }
 
 extern "C" int sdso_comm_info(sdso_ctx* ctx, int* nranks, int* rank) {
   if (!ctx) return SDSO_ERR_STATE;
-  auto c = comm_of(ctx);
+  Comm* c = ctx->comm.get();
   if (nranks) *nranks = c ? c->nranks : 0;
   if (rank) *rank = c ? c->rank : -1;
   return SDSO_OK;
@@ -225,7 +209,7 @@ extern "C" int sdso_comm_destroy(sdso_ctx* ctx) {
 }
 
 static int allreduce_block(sdso_ctx* ctx, void* ptr, size_t nfloats) {
-  auto c = comm_of(ctx);
+  Comm* c = ctx->comm.get();
   SDSO_REQUIRE(ctx, c, "no communicator: call sdso_comm_init (or sdso_comm_attach) first");
   SDSO_REQUIRE(ctx, ptr && nfloats > 0, "nothing to reduce");
   SDSO_HIP(ctx, hipSetDevice(ctx->device));
@@ -249,7 +233,7 @@ static int allreduce_block(sdso_ctx* ctx, void* ptr, size_t nfloats) {
 // the bytes of the all-reduce on every xGMI link; the solve of a window then runs on one rank only and x comes back by all-gather
 // (ba.hip: opt_solve_step).  In place: rank r's slice of the block is both its send and its receive segment.
 static int reduce_scatter_block(sdso_ctx* ctx, void* ptr, size_t nfloats) {
-  auto c = comm_of(ctx);
+  Comm* c = ctx->comm.get();
   SDSO_REQUIRE(ctx, c, "no communicator: call sdso_comm_init (or sdso_comm_attach) first");
   SDSO_REQUIRE(ctx, ptr && nfloats > 0 && nfloats % c->nranks == 0, "the block does not divide over the ranks");
   SDSO_HIP(ctx, hipSetDevice(ctx->device));

@@ -120,11 +120,16 @@ extern "C" int sdso_ctx_create(int device_ordinal, sdso_ctx** out) {
   return SDSO_OK;
 }
 
+static void free_pyramid(PyramidDev& P) {
+  for (int l = 0; l < P.levels; l++) hipFree(P.d[l]);
+  if (P.tiled0) hipFree(P.tiled0);
+  if (P.plane0) hipFree(P.plane0);
+}
+
 namespace sdso {
 void release_all_windows(sdso_ctx* ctx);
 void release_track_batch(sdso_ctx* ctx);
-void release_trace(sdso_ctx* ctx);
-void release_match(sdso_ctx* ctx);
+void release_stereo(sdso_ctx* ctx);
 void release_selector(sdso_ctx* ctx);
 void release_g2o(sdso_ctx* ctx);
 void release_comm(sdso_ctx* ctx);
@@ -137,15 +142,13 @@ extern "C" void sdso_ctx_destroy(sdso_ctx* ctx) {
   if (ctx->aux) { hipStreamSynchronize(ctx->aux); hipStreamDestroy(ctx->aux); ctx->aux = nullptr; }
   if (ctx->ev_main) hipEventDestroy(ctx->ev_main);
   if (ctx->ev_aux) hipEventDestroy(ctx->ev_aux);
-  for (auto& kv : ctx->pyr)
-    { for (int l = 0; l < kv.second.levels; l++) hipFree(kv.second.d[l]); if (kv.second.tiled0) hipFree(kv.second.tiled0); if (kv.second.plane0) hipFree(kv.second.plane0); }
+  for (auto& kv : ctx->pyr) free_pyramid(kv.second);
   for (auto& kv : ctx->refs)
     for (int l = 0; l < SDSO_PYR_LEVELS; l++) if (kv.second.pc[l]) hipFree(kv.second.pc[l]);
   release_all_windows(ctx);
   for (auto& b : ctx->ba_pool) hipFree(b.first);
   release_track_batch(ctx);
-  release_trace(ctx);
-  release_match(ctx);
+  release_stereo(ctx);
   release_selector(ctx);
   release_g2o(ctx);
   release_comm(ctx);
@@ -242,9 +245,7 @@ extern "C" int sdso_release_pyramid(sdso_ctx* ctx, int frame_slot) {
   auto it = ctx->pyr.find(frame_slot);
   if (it == ctx->pyr.end()) return SDSO_OK;
   SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  for (int l = 0; l < it->second.levels; l++) hipFree(it->second.d[l]);
-  if (it->second.tiled0) hipFree(it->second.tiled0);
-  if (it->second.plane0) hipFree(it->second.plane0);
+  free_pyramid(it->second);
   ctx->pyr.erase(it);
   return SDSO_OK;
 }

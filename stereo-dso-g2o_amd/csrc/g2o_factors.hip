@@ -30,21 +30,21 @@ struct G2oState {
   float* d_flow = nullptr;                           // 4 floats per 32nd level-0 point
   int flow_cap = 0;
 };
-static std::map<sdso_ctx*, G2oState> g_g2o;
-
 void release_g2o(sdso_ctx* ctx) {
-  G2oState st;
-  if (!reg_take(g_g2o, ctx, st)) return;
-  for (auto& kv : st.sets) { if (kv.second.mask) hipFree(kv.second.mask); if (kv.second.xref) hipFree(kv.second.xref); }
-  if (st.d_part) hipFree(st.d_part);
-  if (st.d_cnt) hipFree(st.d_cnt);
-  if (st.d_flow) hipFree(st.d_flow);
+  G2oState* st = ctx->g2o;
+  if (!st) return;
+  for (auto& kv : st->sets) { if (kv.second.mask) hipFree(kv.second.mask); if (kv.second.xref) hipFree(kv.second.xref); }
+  if (st->d_part) hipFree(st->d_part);
+  if (st->d_cnt) hipFree(st->d_cnt);
+  if (st->d_flow) hipFree(st->d_flow);
+  delete st;
+  ctx->g2o = nullptr;
 }
 
 // sdso_track_release_ref: the edge sets built on a released template go with it
 void release_g2o_ref(sdso_ctx* ctx, int ref_slot) {
-  if (!reg_has(g_g2o, ctx)) return;
-  G2oState& st = reg_get(g_g2o, ctx);
+  if (!ctx->g2o) return;
+  G2oState& st = *ctx->g2o;
   for (auto it = st.sets.begin(); it != st.sets.end();) {
     if (it->first.first == ref_slot) {
       if (it->second.mask) hipFree(it->second.mask);
@@ -327,8 +327,8 @@ __global__ __launch_bounds__(256) void k_g2o_lba_eval(LbaDev L) {
 }
 
 static G2oEdgeSet* find_set(sdso_ctx* ctx, int ref_slot, int lvl) {
-  if (!reg_has(g_g2o, ctx)) return nullptr;
-  G2oState& st = reg_get(g_g2o, ctx);
+  if (!ctx->g2o) return nullptr;
+  G2oState& st = *ctx->g2o;
   auto it = st.sets.find({ref_slot, lvl});
   return it == st.sets.end() ? nullptr : &it->second;
 }
@@ -350,7 +350,8 @@ extern "C" int sdso_g2o_track_add_edges(sdso_ctx* ctx, int ref_slot, int frame_s
   SDSO_REQUIRE(ctx, lvl >= 0 && lvl < ip->second.levels, "level out of range");
   SDSO_REQUIRE(ctx, ev->w == ip->second.w[lvl] && ev->h == ip->second.h[lvl], "level size does not match the uploaded pyramid");
   const int n = ir->second.n[lvl];
-  G2oState& st = reg_get(g_g2o, ctx);
+  if (!ctx->g2o) ctx->g2o = new G2oState();
+  G2oState& st = *ctx->g2o;
   G2oEdgeSet& S = st.sets[{ref_slot, lvl}];
   if (S.cap < n) {
     SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -419,7 +420,7 @@ extern "C" int sdso_g2o_track_linearize(sdso_ctx* ctx, int ref_slot, int frame_s
   chi2[0] = chi2[1] = 0;
   const int n = S->n;
   if (n == 0) return SDSO_OK;
-  G2oState& st = reg_get(g_g2o, ctx);
+  G2oState& st = *ctx->g2o;   // (find_set found one of its edge sets)
   if (!st.d_part) { SDSO_HIP(ctx, hipMalloc(&st.d_part, sizeof(double) * kSysDoubles * kMaxLinBlocks)); st.part_blocks = kMaxLinBlocks; }
   const int blocks = std::min(kMaxLinBlocks, (n + 255) / 256);
   double *d_err = nullptr, *d_J = nullptr;

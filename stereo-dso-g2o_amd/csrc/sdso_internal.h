@@ -5,7 +5,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <map>
-#include <mutex>
+#include <memory>
 #include <string>
 #include <vector>
 #include "../../include/sdso_abi.h"
@@ -48,7 +48,12 @@ struct ProfEntry {
 };
 
 struct BaWindowDev;  // ba.hip
+struct BaCtxState;   // ba.hip
 struct TrackBatch;   // tracker.hip
+struct StereoState;  // stereo.hip
+struct SelState;     // selector.hip
+struct G2oState;     // g2o_factors.hip
+struct Comm;         // comm.hip
 
 }  // namespace sdso
 
@@ -59,7 +64,13 @@ struct sdso_ctx {
   std::map<int, sdso::PyramidDev> pyr;
   std::map<int, sdso::RefDev> refs;
   std::map<int, sdso::BaWindowDev*> wins;
+  // per-module state, owned by the ctx: null until the module's first call needs it, freed by the module's release_* (sdso_ctx_destroy)
+  sdso::BaCtxState* ba = nullptr;       // staging, batch and resident GN loop of the BA
   sdso::TrackBatch* tb = nullptr;
+  sdso::StereoState* stereo = nullptr;  // the prepared traceStereo batch and the matching batches
+  sdso::SelState* sel = nullptr;        // the pixel selector's random pattern
+  sdso::G2oState* g2o = nullptr;        // edge sets and partial systems of the g2o factors
+  std::shared_ptr<sdso::Comm> comm;     // shared with the contexts joined by sdso_comm_attach
   // generic scratch
   void* scratch = nullptr;
   size_t scratch_bytes = 0;
@@ -87,21 +98,6 @@ struct sdso_ctx {
 };
 
 namespace sdso {
-
-// Per-context state kept outside sdso_ctx lives in file-local registries keyed by the ctx.  A ctx is used by one thread at a
-// time, but different contexts may be driven from different threads (tracking / mapping), so the registries themselves are
-// guarded; the mapped objects are only touched by their ctx's thread (std::map nodes are stable).
-inline std::mutex& registry_mutex() { static std::mutex m; return m; }
-template <class V> inline V& reg_get(std::map<sdso_ctx*, V>& m, sdso_ctx* ctx) { std::lock_guard<std::mutex> g(registry_mutex()); return m[ctx]; }
-template <class V> inline bool reg_has(std::map<sdso_ctx*, V>& m, sdso_ctx* ctx) { std::lock_guard<std::mutex> g(registry_mutex()); return m.count(ctx) != 0; }
-template <class V> inline bool reg_take(std::map<sdso_ctx*, V>& m, sdso_ctx* ctx, V& out) {
-  std::lock_guard<std::mutex> g(registry_mutex());
-  auto it = m.find(ctx);
-  if (it == m.end()) return false;
-  out = it->second;
-  m.erase(it);
-  return true;
-}
 
 inline int fail(sdso_ctx* ctx, int code, const std::string& msg) {
   if (ctx) ctx->err = msg;

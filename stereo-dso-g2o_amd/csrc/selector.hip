@@ -210,20 +210,19 @@ __global__ __launch_bounds__(256) void k_ps_thin(float* __restrict__ map, int w,
   if (nk) atomicAdd(killed, nk);
 }
 
+}  // namespace
+
+namespace sdso {
 struct SelState {
   unsigned char* d_rnd = nullptr;
   std::vector<unsigned char> h_rnd;
   int w = 0, h = 0;
 };
-static std::map<sdso_ctx*, SelState> g_sel;
-
-}  // namespace
-
-namespace sdso {
 void release_selector(sdso_ctx* ctx) {
-  SelState st;
-  if (!reg_take(g_sel, ctx, st)) return;
-  if (st.d_rnd) hipFree(st.d_rnd);
+  if (!ctx->sel) return;
+  if (ctx->sel->d_rnd) hipFree(ctx->sel->d_rnd);
+  delete ctx->sel;
+  ctx->sel = nullptr;
 }
 }  // namespace sdso
 
@@ -247,7 +246,8 @@ extern "C" int sdso_pixel_select(sdso_ctx* ctx, int frame_slot, float density, i
   SDSO_REQUIRE(ctx, P.levels >= 3, "the selector reads absSquaredGrad of levels 0..2");
   const int w = P.w[0], h = P.h[0], w32 = w / 32, h32 = h / 32;
   SDSO_REQUIRE(ctx, w32 > 0 && h32 > 0, "image smaller than one 32x32 cell");
-  SelState& S = reg_get(g_sel, ctx);
+  if (!ctx->sel) ctx->sel = new SelState();
+  SelState& S = *ctx->sel;
   if (S.w != w || S.h != h) {
     if (S.d_rnd) { SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream)); hipFree(S.d_rnd); S.d_rnd = nullptr; }
     glibc_rand_bytes(3141592u, (size_t)w * h, S.h_rnd);

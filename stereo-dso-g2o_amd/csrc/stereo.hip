@@ -629,7 +629,12 @@ struct TraceBatch {
   uint8_t* bytes = nullptr;
   int n = 0;
 };
-static std::map<sdso_ctx*, TraceBatch> g_trace;
+struct StereoState {
+  TraceBatch* trace = nullptr;   // the prepared traceStereo batch (sdso_trace_stereo_prepare / _enqueue / _fetch)
+  TraceBatch match[2];           // forward and back batches of sdso_stereo_match_batch
+};
+static StereoState& stereo_state(sdso_ctx* ctx) { if (!ctx->stereo) ctx->stereo = new StereoState(); return *ctx->stereo; }
+static TraceBatch* prepared_trace(sdso_ctx* ctx) { return ctx && ctx->stereo ? ctx->stereo->trace : nullptr; }
 
 static int trace_reserve(sdso_ctx* ctx, TraceBatch& B, int n) {
   if (B.n >= n) return SDSO_OK;
@@ -653,11 +658,17 @@ static void trace_bind(TraceBatch& B, int n) {
   T.lastTraceUV = f + 28 * N; T.lastTracePixelInterval = f + 30 * N;
   T.lastTraceStatus = B.bytes; T.status = B.bytes + N; T.skip = nullptr;
 }
-void release_trace(sdso_ctx* ctx) {
-  TraceBatch tb;
-  if (!reg_take(g_trace, ctx, tb)) return;
-  if (tb.blob) hipFree(tb.blob);
-  if (tb.bytes) hipFree(tb.bytes);
+static void trace_free(TraceBatch& B) {
+  if (B.blob) hipFree(B.blob);
+  if (B.bytes) hipFree(B.bytes);
+}
+void release_stereo(sdso_ctx* ctx) {
+  StereoState* S = ctx->stereo;
+  if (!S) return;
+  if (S->trace) { trace_free(*S->trace); delete S->trace; }
+  for (TraceBatch& B : S->match) trace_free(B);
+  delete S;
+  ctx->stereo = nullptr;
 }
 }  // namespace sdso
 
@@ -669,7 +680,9 @@ extern "C" int sdso_trace_stereo_prepare(sdso_ctx* ctx, int frame_slot, const fl
   auto ip = ctx->pyr.find(frame_slot);
   SDSO_REQUIRE(ctx, ip != ctx->pyr.end(), "unknown frame slot");
   const int n = P->n;
-  TraceBatch& B = reg_get(g_trace, ctx);
+  StereoState& S = stereo_state(ctx);
+  if (!S.trace) S.trace = new TraceBatch();
+  TraceBatch& B = *S.trace;
   int rc = trace_reserve(ctx, B, std::max(n, 1));
   if (rc) return rc;
   trace_bind(B, n);
@@ -699,8 +712,8 @@ static void launch_trace_stereo(sdso_ctx* ctx, const TraceDev& T, bool timed = f
   else { if (timed) launch_timed(ctx, "k_trace_stereo", 1, (k_trace_stereo_blk<0, P>), g, b, T); else hipLaunchKernelGGL((k_trace_stereo_blk<0, P>), g, b, 0, ctx->stream, T); }
 }
 extern "C" int sdso_trace_stereo_enqueue(sdso_ctx* ctx) {
-  if (!ctx || !reg_has(g_trace, ctx)) return sdso::fail(ctx, SDSO_ERR_STATE, "no prepared trace batch");
-  TraceBatch& B = reg_get(g_trace, ctx);
+  if (!prepared_trace(ctx)) return sdso::fail(ctx, SDSO_ERR_STATE, "no prepared trace batch");
+  TraceBatch& B = *prepared_trace(ctx);
   if (B.T.n == 0) return SDSO_OK;
   SDSO_HIP(ctx, hipMemcpyAsync(B.blob + 3 * (size_t)B.n, B.blob + 32 * (size_t)B.n, sizeof(float) * 3 * (size_t)B.n, hipMemcpyDeviceToDevice, ctx->stream));
   SDSO_HIP(ctx, hipMemcpyAsync(B.bytes, B.bytes + 2 * (size_t)B.n, (size_t)B.n, hipMemcpyDeviceToDevice, ctx->stream));
@@ -709,8 +722,8 @@ extern "C" int sdso_trace_stereo_enqueue(sdso_ctx* ctx) {
   return SDSO_OK;
 }
 extern "C" int sdso_trace_stereo_fetch(sdso_ctx* ctx, sdso_trace_points_t* P, uint8_t* status) {
-  if (!ctx || !reg_has(g_trace, ctx)) return sdso::fail(ctx, SDSO_ERR_STATE, "no prepared trace batch");
-  TraceBatch& B = reg_get(g_trace, ctx);
+  if (!prepared_trace(ctx)) return sdso::fail(ctx, SDSO_ERR_STATE, "no prepared trace batch");
+  TraceBatch& B = *prepared_trace(ctx);
   const int n = B.T.n;
   TraceDev& T = B.T;
 #define DN(dst, src, cnt) if (n && dst) SDSO_HIP(ctx, hipMemcpyAsync((dst), (src), sizeof(float) * (size_t)(cnt), hipMemcpyDeviceToHost, ctx->stream))
@@ -739,7 +752,7 @@ extern "C" int sdso_trace_on_batch(sdso_ctx* ctx, int frame_slot, int ngeom, con
   if (!pts->idepth_stereo) pts->idepth_stereo = pts->idepth_min_stereo;
   int rc = sdso_trace_stereo_prepare(ctx, frame_slot, K0, 0.f, 1, pts);   // uploads the point state into the ctx's trace batch
   if (rc) return rc;
-  TraceBatch& B = reg_get(g_trace, ctx);
+  TraceBatch& B = *prepared_trace(ctx);
   rc = ensure_scratch(ctx, sizeof(sdso_trace_geom_t) * (size_t)ngeom + sizeof(int) * (size_t)n);
   if (rc) return rc;
   sdso_trace_geom_t* d_geom = (sdso_trace_geom_t*)ctx->scratch;
@@ -808,18 +821,6 @@ __global__ __launch_bounds__(256) void k_match_back_points(int n, TraceDev F, Tr
   Bk.lastTraceUV[2 * p] = 0.f; Bk.lastTraceUV[2 * p + 1] = 0.f; Bk.lastTracePixelInterval[p] = 0.f;
 }
 
-namespace sdso {
-static std::map<sdso_ctx*, TraceBatch> g_match[2];
-void release_match(sdso_ctx* ctx) {
-  for (int k = 0; k < 2; k++) {
-    TraceBatch tb;
-    if (!reg_take(g_match[k], ctx, tb)) continue;
-    if (tb.blob) hipFree(tb.blob);
-    if (tb.bytes) hipFree(tb.bytes);
-  }
-}
-}  // namespace sdso
-
 extern "C" int sdso_stereo_match_batch(sdso_ctx* ctx, int slot_a, int slot_b, const float K[4], float baseline, int mode_right_first,
                                        sdso_stereo_match_t* M) {
   if (!ctx) return SDSO_ERR_STATE;
@@ -833,8 +834,9 @@ extern "C" int sdso_stereo_match_batch(sdso_ctx* ctx, int slot_a, int slot_b, co
   SDSO_REQUIRE(ctx, M->u && M->v, "null point arrays");
   for (int i = 0; i < n; i++)
     SDSO_REQUIRE(ctx, M->u[i] >= 2 && M->v[i] >= 2 && M->u[i] < w - 3 && M->v[i] < h - 3, "immature point too close to the image border");
-  TraceBatch& A = reg_get(g_match[0], ctx);
-  TraceBatch& Bk = reg_get(g_match[1], ctx);
+  StereoState& S = stereo_state(ctx);
+  TraceBatch& A = S.match[0];
+  TraceBatch& Bk = S.match[1];
   int rc = trace_reserve(ctx, A, n);
   if (rc) return rc;
   rc = trace_reserve(ctx, Bk, n);

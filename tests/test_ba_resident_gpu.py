@@ -16,6 +16,8 @@ import helpers
 
 pytestmark = pytest.mark.gpu
 
+SDSO_ERR_STATE = -4   # include/sdso_abi.h:36
+
 
 def _oracle_opt(oracle, win, its):
     nf, npts, nr = win["nf"], win["np"], win["nr"]
@@ -363,3 +365,80 @@ def test_cu_partitioned_ctx_gives_the_same_windows(oracle):
     assert a[3] == b[3] and a[3] >= 2 and a[4] == b[4]
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
     assert np.abs(a[0]).max() > 0
+
+
+def test_contexts_keep_their_state_apart():
+    """Every ctx owns its batch, its resident loop in flight, its prepared trace batch and its selector pattern: a second ctx sees none of
+    them, a ctx destroyed with its loop still in flight leaves nothing behind for the next one, and a batch of the second ctx optimises to
+    the same states, idepths and residual states as on a fresh ctx of its own."""
+    wins = helpers.gen_windows([dict(w=320, h=240, nf=4, pts_per_kf=60, seed=3031), dict(w=320, h=240, nf=4, pts_per_kf=60, seed=3037)])
+    nf = 4
+    keepalive = []
+
+    def batch_on(ctx):
+        for k, win in enumerate(wins):
+            slots = [40 + k * nf + f for f in range(nf)]
+            for f in range(nf):
+                ctx.upload_pyramid(slots[f], win["pyrs"][f][:1])
+            W, keep = abi.make_ba_window(win, frame_slots=slots)
+            keepalive.append((W, keep))
+            ctx.check(ctx.L.sdso_ba_upload_window(ctx.h, 70 + k, C.byref(W)))
+        ids = np.array([70 + k for k in range(len(wins))], np.int32)
+        ctx.check(ctx.L.sdso_ba_batch_create(ctx.h, len(wins), abi.ip(ids)))
+
+    def optimise(ctx):
+        res = (abi.BAOptResult * len(wins))()
+        ctx.check(ctx.L.sdso_ba_batch_optimize(ctx.h, 6, res))
+        out = []
+        for k, win in enumerate(wins):
+            s, i, r = np.zeros((nf, 10)), np.zeros(win["np"], np.float32), np.zeros(win["nr"], np.uint8)
+            ctx.check(ctx.L.sdso_ba_get_state(ctx.h, 70 + k, abi.dp(s), abi.fp(i), abi.bp(r)))
+            out.append((s, i, r, res[k].iterations))
+        return out
+
+    def refused(ctx, rc, msg):
+        assert rc == SDSO_ERR_STATE and ctx.L.sdso_last_error(ctx.h) == msg, (rc, ctx.L.sdso_last_error(ctx.h))
+
+    def no_state(ctx):
+        refused(ctx, ctx.L.sdso_ba_batch_step(ctx.h), b"sdso_ba_batch_optimize_begin first")
+        refused(ctx, ctx.L.sdso_trace_stereo_enqueue(ctx.h), b"no prepared trace batch")
+
+    ctxs = {}
+    try:
+        a = ctxs["a"] = abi.Context(0)
+        b = ctxs["b"] = abi.Context(0)
+        batch_on(a)
+        batch_on(b)
+        a.check(a.L.sdso_ba_batch_optimize_begin(a.h, 1))
+        pr = synth.stereo_problem(w=320, h=240, npts=400, seed=4031)
+        left = np.ascontiguousarray(pr["pyr_l"][0]); right = np.ascontiguousarray(pr["pyr_r"][0])
+        a.upload_pyramid(80, [left]); a.upload_pyramid(81, [right])
+        n = len(pr["u"])
+        col, wgt, gH, eth = np.zeros((n, 8), np.float32), np.zeros((n, 8), np.float32), np.zeros((n, 4), np.float32), np.zeros(n, np.float32)
+        a.check(a.L.sdso_immature_init_batch(a.h, 80, n, abi.fp(pr["u"]), abi.fp(pr["v"]), abi.fp(col), abi.fp(wgt), abi.fp(gH), abi.fp(eth)))
+        P, d = abi.make_trace_points(n, pr["u"], pr["v"], col, wgt, gH, eth)
+        K = np.array(pr["K"], np.float32)
+        a.check(a.L.sdso_trace_stereo_prepare(a.h, 81, abi.fp(K), float(pr["calib"]["baseline"]), 1, C.byref(P)))
+        a.check(a.L.sdso_make_pyramid(a.h, 82, pr["w"], pr["h"], abi.fp(np.ascontiguousarray(left[..., 0]))))
+        m, pot, nsel = np.zeros((pr["h"], pr["w"]), np.float32), C.c_int(3), C.c_int(0)
+        a.check(a.L.sdso_pixel_select(a.h, 82, 1500.0, 1, 1.0, C.byref(pot), abi.fp(m), C.byref(nsel)))
+        assert nsel.value > 0
+
+        no_state(b)                                       # A's loop in flight and A's trace batch are A's alone
+        ctxs.pop("a").close()                             # destroyed with its loop still in flight
+        c = ctxs["c"] = abi.Context(0)
+        no_state(c)
+        refused(c, c.L.sdso_ba_batch_optimize_begin(c.h, 1), b"no batch")
+        got = optimise(b)
+        for k in list(ctxs):
+            ctxs.pop(k).close()
+        fresh = ctxs["fresh"] = abi.Context(0)
+        batch_on(fresh)
+        want = optimise(fresh)
+    finally:
+        for ctx in ctxs.values():
+            ctx.close()
+    for (sg, ig, rg, itg), (sw, iw, rw, itw) in zip(got, want):
+        assert itg == itw and itg >= 1
+        assert np.array_equal(sg, sw) and np.array_equal(ig, iw) and np.array_equal(rg, rw)
+    assert np.abs(got[0][0]).max() > 0
