@@ -46,6 +46,24 @@ def oracle_eval(L, pc_l, dI_l, ev, want_mask=True):
     return H.reshape(8, 8), b, res, nw.value, mask[:n]
 
 
+WARPED_FIELDS = ("idepth", "u", "v", "dx", "dy", "residual", "weight", "refColor")
+
+
+def oracle_eval_warped(L, pc_l, dI_l, ev):
+    """oracle_eval plus calcRes' buf_warped (CoarseTracker.cpp:750-775): one float32 row per field of WARPED_FIELDS, n_warped
+    columns (the inliers in point order, then the zero rows that pad the count to a multiple of 4)."""
+    n = len(pc_l["u"])
+    cap = n + 4
+    H = np.zeros(64); b = np.zeros(8); res = np.zeros(6); nw = C.c_int(0)
+    mask = np.zeros(max(n, 1), np.uint8)
+    buf = np.zeros((8, cap), np.float32)
+    u, v, idp, col = [np.ascontiguousarray(pc_l[k], np.float32) for k in ("u", "v", "idepth", "color")]
+    img = np.ascontiguousarray(dI_l, np.float32)
+    L.orc_track_calc_res_gs(n, abi.fp(u), abi.fp(v), abi.fp(idp), abi.fp(col), abi.fp(img), C.byref(ev), abi.dp(H), abi.dp(b),
+                            abi.dp(res), C.byref(nw), abi.bp(mask), abi.fp(buf), cap)
+    return H.reshape(8, 8), b, res, nw.value, mask[:n], buf[:, :nw.value].copy()
+
+
 def permuted_window(win, seed):
     """The same BA window with the points shuffled inside every host group (residuals follow their
     points).  Mathematically identical problem; only the order of the float sums changes — used to
