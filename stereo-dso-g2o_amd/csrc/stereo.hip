@@ -651,8 +651,10 @@ static void trace_bind(TraceBatch& B, int n) {
   const size_t N = B.n;
   TraceDev& T = B.T;
   T.n = n;
-  // in/out fields {idepth_min_stereo, idepth_max_stereo, quality} are contiguous (3N floats at 3N) with a
-  // pristine copy at 32N, so that enqueue can be repeated on identical input (benchmark)
+  // in/out fields {idepth_min_stereo, idepth_max_stereo, quality, idepth_stereo} are contiguous (4N floats at 3N) with a
+  // pristine copy at 32N, so that enqueue can be repeated on identical input (benchmark).  idepth_stereo is written only for
+  // GOOD points (ImmaturePoint.cpp:448): without its copy, an enqueue in another refinement mode would return the previous
+  // enqueue's value for a point that was GOOD there and is not now.
   T.u_stereo = f; T.v_stereo = f + N; T.idepth_min = f + 2 * N; T.idepth_min_stereo = f + 3 * N; T.idepth_max_stereo = f + 4 * N; T.quality = f + 5 * N;
   T.idepth_stereo = f + 6 * N; T.color = f + 7 * N; T.weights = f + 15 * N; T.gradH = f + 23 * N; T.energyTH = f + 27 * N;
   T.lastTraceUV = f + 28 * N; T.lastTracePixelInterval = f + 30 * N;
@@ -699,7 +701,7 @@ extern "C" int sdso_trace_stereo_prepare(sdso_ctx* ctx, int frame_slot, const fl
 #undef UP
   if (n) SDSO_HIP(ctx, hipMemcpyAsync(T.lastTraceStatus, P->lastTraceStatus, n, hipMemcpyHostToDevice, ctx->stream));
   // pristine copies of the in/out fields
-  SDSO_HIP(ctx, hipMemcpyAsync(B.blob + 32 * (size_t)B.n, B.blob + 3 * (size_t)B.n, sizeof(float) * 3 * (size_t)B.n, hipMemcpyDeviceToDevice, ctx->stream));
+  SDSO_HIP(ctx, hipMemcpyAsync(B.blob + 32 * (size_t)B.n, B.blob + 3 * (size_t)B.n, sizeof(float) * 4 * (size_t)B.n, hipMemcpyDeviceToDevice, ctx->stream));
   SDSO_HIP(ctx, hipMemcpyAsync(B.bytes + 2 * (size_t)B.n, B.bytes, (size_t)B.n, hipMemcpyDeviceToDevice, ctx->stream));
   SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SDSO_OK;
@@ -715,7 +717,7 @@ extern "C" int sdso_trace_stereo_enqueue(sdso_ctx* ctx) {
   if (!prepared_trace(ctx)) return sdso::fail(ctx, SDSO_ERR_STATE, "no prepared trace batch");
   TraceBatch& B = *prepared_trace(ctx);
   if (B.T.n == 0) return SDSO_OK;
-  SDSO_HIP(ctx, hipMemcpyAsync(B.blob + 3 * (size_t)B.n, B.blob + 32 * (size_t)B.n, sizeof(float) * 3 * (size_t)B.n, hipMemcpyDeviceToDevice, ctx->stream));
+  SDSO_HIP(ctx, hipMemcpyAsync(B.blob + 3 * (size_t)B.n, B.blob + 32 * (size_t)B.n, sizeof(float) * 4 * (size_t)B.n, hipMemcpyDeviceToDevice, ctx->stream));
   SDSO_HIP(ctx, hipMemcpyAsync(B.bytes, B.bytes + 2 * (size_t)B.n, (size_t)B.n, hipMemcpyDeviceToDevice, ctx->stream));
   launch_trace_stereo(ctx, B.T, true);
   SDSO_HIP(ctx, hipGetLastError());

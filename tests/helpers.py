@@ -238,3 +238,99 @@ def gen_windows(specs):
         return [synth.ba_window(**s) for s in specs]
     with ThreadPoolExecutor(max_workers=min(4, len(specs))) as ex:
         return list(ex.map(lambda s: synth.ba_window(**s), specs))
+
+
+# ------------------------------------------------------------------ makeCoarseDepthL0 inputs (CoarseTracker.cpp:288-354)
+CD_TILE, CD_BLOCK = 2048, 256     # csrc/coarse_depth.hip: k_cd_splat's LDS tile of earlier points, and its workgroup
+
+
+def splat_points(n, w, h, seed):
+    """n level-0 points for makeCoarseDepthL0's splat (u, v int32 anywhere in the w x h image; new_idepth and weight float32, both
+    positive), with pixels shared on purpose where k_cd_splat (csrc/coarse_depth.hip) changes regime:
+      * a pair across every 256-point workgroup edge, 2047/2048 and 4095/4096 (tile edges) among them;
+      * first hits in one 2048-point tile with later hits in later tiles, the last point among them;
+      * one pixel hit by 40 points spread over every tile;
+      * pairs inside one workgroup.
+    A group that meets a point of an earlier group joins that group's pixel.  Returns (u, v, new_idepth, weight)."""
+    rs = np.random.RandomState(seed)
+    u = rs.randint(0, w, n).astype(np.int32)
+    v = rs.randint(0, h, n).astype(np.int32)
+    idp = rs.uniform(0.02, 0.4, n).astype(np.float32)
+    wgt = rs.uniform(0.2, 3.0, n).astype(np.float32)
+    cand = [[b - 1, b] for b in range(CD_BLOCK, n, CD_BLOCK)]
+    cand += [[100, 2100, 4200, 9000, 16500], [2050, 4100, 6150, 19000], [1, 4097, 10000, n - 1]]
+    cand.append(list(np.unique(np.linspace(3, n - 3, 40).round().astype(int))))
+    for b in range(0, n, 3 * CD_BLOCK):
+        cand += [[b + 10, b + 11], [b + 20, b + 250]]
+    used = set()
+    for g in cand:
+        g = list(dict.fromkeys(int(i) for i in g if 0 <= i < n))
+        if len(g) < 2:
+            continue
+        anchor = next((i for i in g if i in used), g[0])
+        u[g] = u[anchor]
+        v[g] = v[anchor]
+        used.update(g)
+    return u, v, idp, wgt
+
+
+def pixel_groups(u, v, w):
+    """the points of every pixel hit more than once: a list of index arrays (ascending)"""
+    pix = u.astype(np.int64) + w * v.astype(np.int64)
+    order = np.argsort(pix, kind="stable")
+    ps = pix[order]
+    start = np.nonzero(np.r_[True, ps[1:] != ps[:-1]])[0] if len(ps) else np.zeros(0, np.int64)
+    return [g for g in np.split(order, start[1:]) if len(g) > 1]
+
+
+def window_points(win, seed):
+    """The points of a synth.ba_window as makeCoarseDepthL0 STEP1 splats them into the newest keyframe (CoarseTracker.cpp:290-354):
+    centerProjectedTo = (Ku, Kv, idepth there) from the point's idepth and the two poses, Ku / Kv inside PointFrameResidual's bounds
+    (1.1 < Ku < w - 3), rounded with (int)(Ku + 0.5f); frame by frame, then point by point (the reference's double loop: the splat
+    order); weight = sqrtf(1e-3 / (HdiF + 1e-12)) with a random HdiF.  Returns (u, v, new_idepth, weight, cpt)."""
+    import synth
+    rs = np.random.RandomState(seed)
+    nf, w, h = win["nf"], win["w"], win["h"]
+    fx, fy, cx, cy = [float(x) for x in win["K"]]
+    Ki = np.linalg.inv(np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]]))
+    out = []
+    for k in range(nf):
+        sel = np.nonzero(win["host"] == k)[0]
+        P = Ki @ np.stack([win["u"][sel], win["v"][sel], np.ones(len(sel))]).astype(np.float64) / win["idepth"][sel].astype(np.float64)
+        R, t = synth.se3_mul(win["poses"][nf - 1], synth.se3_inv(win["poses"][k]))
+        Pt = R @ P + t[:, None]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            cpt = np.stack([fx * Pt[0] / Pt[2] + cx, fy * Pt[1] / Pt[2] + cy, 1.0 / Pt[2]], axis=1).astype(np.float32)
+        ok = (Pt[2] > 0) & (cpt[:, 0] > 1.1) & (cpt[:, 1] > 1.1) & (cpt[:, 0] < w - 3) & (cpt[:, 1] < h - 3)
+        out.append(cpt[ok])
+    cpt = np.ascontiguousarray(np.concatenate(out))
+    ui = (cpt[:, 0] + np.float32(0.5)).astype(np.int32)
+    vi = (cpt[:, 1] + np.float32(0.5)).astype(np.int32)
+    hdi = (1.0 / rs.uniform(50, 5000, len(cpt))).astype(np.float32)
+    wgt = np.sqrt((1e-3 / (hdi.astype(np.float64) + 1e-12)).astype(np.float32)).astype(np.float32)
+    return ui, vi, np.ascontiguousarray(cpt[:, 2]), wgt, cpt
+
+
+def edge_points(n, w, h, seed):
+    """splat_points with the edge inputs sdso_track_make_ref accepts mixed in: points on rows and columns 0, 1, w-2 / h-2 and w-1 / h-1
+    (outside STEP5's scan, CoarseTracker.cpp:507-508, but inside the pyramid sums and the dilation), the four corners, zero weights,
+    zero and negative new_idepth (STEP5 rejects !(idepth > 0)); some of them on the shared pixels of splat_points."""
+    u, v, idp, wgt = splat_points(n, w, h, seed)
+    rs = np.random.RandomState(seed + 1)
+    at = rs.permutation(n)
+    k = 0
+    for x in (0, 1, w - 2, w - 1):
+        m = min(12, n - k)
+        u[at[k:k + m]] = x; v[at[k:k + m]] = rs.randint(0, h, m); k += m
+    for y in (0, 1, h - 2, h - 1):
+        m = min(12, n - k)
+        v[at[k:k + m]] = y; u[at[k:k + m]] = rs.randint(0, w, m); k += m
+    for x, y in ((0, 0), (w - 1, 0), (0, h - 1), (w - 1, h - 1)):
+        if k < n:
+            u[at[k]], v[at[k]] = x, y; k += 1
+    sel = rs.rand(n)
+    wgt[sel < 0.05] = 0
+    idp[(sel >= 0.05) & (sel < 0.09)] = 0
+    neg = (sel >= 0.09) & (sel < 0.14)
+    idp[neg] = -rs.uniform(0.01, 0.4, int(neg.sum())).astype(np.float32)
+    return u, v, idp, wgt

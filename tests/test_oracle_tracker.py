@@ -3,7 +3,19 @@ the reference has none for this path).  Independent evidence used instead:
   * the 8 Jacobian columns accumulated into b = J^T W r agree with a finite-difference derivative
     of the Huber energy w.r.t. the left-multiplied increment (double re-evaluation);
   * the DSO-native LM recovers the synthetic motion;
-  * the pyramid rule of the generator equals the oracle's makeImages restatement bit-for-bit."""
+  * the pyramid rule of the generator equals the oracle's makeImages restatement bit-for-bit.
+
+makeCoarseDepthL0 STEP1-splat .. STEP5 (CoarseTracker.cpp:352-534) has two float restatements: the oracle's orc_make_coarse_depth
+and the numpy synth.make_pc.  They must agree bit for bit at window scale (1232x368 and 640x480, up to 20 000 points, pixels shared
+across the 2048-point tiles of the device splat), and both are held to coarse_depth_truth, a float64 truth that does not depend on
+summation order.  With positive idepths and weights the kept pixels and their order equal the truth's; the normalised idepth's
+largest relative error to the truth, measured on the CPU over three seeds each of n = 1, 257, 2049, 4097, 20 000 and over 4000
+selected points of a rendered scene, both shapes:
+  level           0        1        2        3        4
+  measured     2.9e-7   2.9e-7   4.1e-7   3.1e-7   3.3e-7
+  bar          9e-7     9e-7     1.2e-6   1e-6     1e-6
+The device path (sdso_track_make_ref) is bit-identical to both restatements (tests/test_tracking_ref_gpu.py), so these bars are its
+bars too."""
 import ctypes as C
 
 import numpy as np
@@ -156,3 +168,105 @@ def test_make_coarse_depth_oracle_equals_the_generator(oracle):
         assert len(a[l]["u"]) == len(b[l]["u"]) > 0
         for k in ("u", "v", "idepth", "color"):
             assert np.array_equal(a[l][k], b[l][k]), (l, k)
+
+
+# ------------------------------------------------------------------ makeCoarseDepthL0 at window scale
+CD_BARS = (9e-7, 9e-7, 1.2e-6, 1e-6, 1e-6)      # per level: about 3x the largest error measured (module docstring)
+
+
+def coarse_depth_truth(u, v, idp, wgt, ref_pyr):
+    """makeCoarseDepthL0 STEP1-splat .. STEP5 (CoarseTracker.cpp:352-534) in float64, written so that no result depends on the order of
+    a sum: the splat is np.bincount, the pyramid 2x2 block sums, the dilation reads the four neighbours of the flattened map through a
+    zero-padded copy (the reference's linear offsets, the wrap into the next row included; the element past the map is no
+    neighbour), the normalisation comes last.  Returns per level dict(u, v, idepth, color) in STEP5's scan order (idepth float64)."""
+    L = len(ref_pyr)
+    h0, w0 = ref_pyr[0].shape[:2]
+    pix = u.astype(np.int64) + w0 * v.astype(np.int64)
+    idm = [np.bincount(pix, weights=idp.astype(np.float64) * wgt.astype(np.float64), minlength=w0 * h0).reshape(h0, w0)]
+    wsm = [np.bincount(pix, weights=wgt.astype(np.float64), minlength=w0 * h0).reshape(h0, w0)]
+    for l in range(1, L):
+        hl, wl = ref_pyr[l].shape[:2]
+        idm.append(idm[-1][:2 * hl, :2 * wl].reshape(hl, 2, wl, 2).sum(axis=(1, 3)))
+        wsm.append(wsm[-1][:2 * hl, :2 * wl].reshape(hl, 2, wl, 2).sum(axis=(1, 3)))
+    out = []
+    for l in range(L):
+        hl, wl = idm[l].shape
+        offs = (1 + wl, -1 - wl, wl - 1, -wl + 1) if l < 2 else (1, -1, wl, -wl)      # STEP3 diagonal, STEP4 axis neighbours
+        idf, wsf = idm[l].reshape(-1).copy(), wsm[l].reshape(-1).copy()
+        pad = wl + 1
+        idpad, bak = np.pad(idf, pad), np.pad(wsf, pad)
+        i = np.arange(wl, wl * hl - wl)
+        s, num, cnt = np.zeros(len(i)), np.zeros(len(i)), np.zeros(len(i))
+        for o in offs:
+            j = pad + i + o
+            nb = bak[j] > 0
+            s += np.where(nb, idpad[j], 0.0)
+            num += np.where(nb, bak[j], 0.0)
+            cnt += nb
+        fill = (wsf[i] <= 0) & (cnt > 0)
+        idf[i[fill]] = s[fill] / cnt[fill]
+        wsf[i[fill]] = num[fill] / cnt[fill]
+        ys, xs = np.meshgrid(np.arange(2, hl - 2), np.arange(2, wl - 2), indexing="ij")
+        ys, xs = ys.reshape(-1), xs.reshape(-1)
+        ws = wsf[xs + wl * ys]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            idn = idf[xs + wl * ys] / ws
+        col = ref_pyr[l][ys, xs, 0]
+        keep = (ws > 0) & np.isfinite(col) & (idn > 0)
+        out.append(dict(u=xs[keep], v=ys[keep], idepth=idn[keep], color=col[keep]))
+    return out
+
+
+def _random_pyramid(w, h, seed):
+    rs = np.random.RandomState(seed)
+    return synth.make_pyramid(rs.uniform(0, 255, (h, w)).astype(np.float32), synth.pyramid_levels(w, h))
+
+
+def _assert_same_template(a, b):
+    assert len(a) == len(b)
+    for l in range(len(a)):
+        for k in ("u", "v", "idepth", "color"):
+            assert a[l][k].dtype == b[l][k].dtype == np.float32 and np.array_equal(a[l][k], b[l][k]), (l, k)
+
+
+@pytest.mark.parametrize("shape", [(1232, 368), (640, 480)])
+def test_make_coarse_depth_restatements_at_window_scale(oracle, shape):
+    """orc_make_coarse_depth and synth.make_pc bit-identical at up to 20 000 points, with pixels shared across the 2048-point tiles,
+    and on the edge inputs (border rows and columns, zero weights, zero and negative idepths)."""
+    import pyoracle
+    w, h = shape
+    pyr = _random_pyramid(w, h, 11)
+    for n, seed in ((1, 1), (257, 2), (2049, 3), (4097, 4), (20000, 5)):
+        u, v, idp, wgt = helpers.splat_points(n, w, h, seed)
+        a = synth.make_pc(u, v, idp, wgt, pyr)
+        _assert_same_template(a, pyoracle.make_coarse_depth(oracle, u, v, idp, wgt, pyr))
+        assert len(a[0]["u"]) > 0
+    crossing = [g for g in helpers.pixel_groups(u, v, w) if g[0] // helpers.CD_TILE != g[-1] // helpers.CD_TILE]
+    assert len(crossing) > 100 and max(len(g) for g in crossing) >= 32      # the n = 20 000 input: what the tiles have to get right
+    u, v, idp, wgt = helpers.edge_points(3000, w, h, 6)
+    a = synth.make_pc(u, v, idp, wgt, pyr)
+    _assert_same_template(a, pyoracle.make_coarse_depth(oracle, u, v, idp, wgt, pyr))
+    assert ((u == 0) | (v == h - 1)).any() and (wgt == 0).any() and (idp < 0).any()
+
+
+@pytest.mark.parametrize("shape", [(1232, 368), (640, 480)])
+def test_make_coarse_depth_against_f64_truth(shape):
+    """The float restatement against coarse_depth_truth: the same pixels in the same order, the same colours, the normalised idepth
+    within CD_BARS of the truth on every level."""
+    w, h = shape
+    pyr = _random_pyramid(w, h, 12)
+    L = len(pyr)
+    worst = np.zeros(L)
+    for n, seed in ((257, 21), (2049, 22), (4097, 23), (20000, 24), (20000, 25)):
+        u, v, idp, wgt = helpers.splat_points(n, w, h, seed)
+        a = synth.make_pc(u, v, idp, wgt, pyr)
+        t = coarse_depth_truth(u, v, idp, wgt, pyr)
+        for l in range(L):
+            assert len(t[l]["u"]) > 0
+            assert np.array_equal(a[l]["u"], t[l]["u"].astype(np.float32)) and np.array_equal(a[l]["v"], t[l]["v"].astype(np.float32)), (n, l)
+            assert np.array_equal(a[l]["color"], t[l]["color"]), (n, l)
+            rel = np.abs(a[l]["idepth"].astype(np.float64) - t[l]["idepth"]) / t[l]["idepth"]
+            worst[l] = max(worst[l], rel.max())
+    assert (worst <= np.array(CD_BARS[:L])).all(), worst
+    assert worst.max() > 0                              # the float path does round: the comparison is not vacuous
+

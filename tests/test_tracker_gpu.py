@@ -186,13 +186,14 @@ def test_make_ref_bit_exact_bookkeeping(gpu_ctx, oracle):
     """CoarseTracker::makeCoarseDepthL0 STEP1-5 on the device (sdso_track_make_ref) against the oracle's C++ restatement
     (oracle/orc_tracker.cpp::orc_make_coarse_depth, CoarseTracker.cpp:352-534): pc_n of every level, the ORDER of the template points and every float
     must be identical — this is the tracker's point-index bookkeeping.  The input has pixels hit by 2, 3 and 5 points
-    with different weights (the splat must add them in point order)."""
+    with different weights (the splat must add them in point order).  Its 1500 points fill one 2048-point tile of k_cd_splat, so
+    collisions across tiles are left to tests/test_tracking_ref_gpu.py."""
     prob = synth.tracker_problem(w=640, h=480, npts=1500, seed=2031)
     u, v, idp = prob["points"]
     rs = np.random.RandomState(3)
     u = u.astype(np.int32).copy(); v = v.astype(np.int32).copy(); idp = idp.astype(np.float32).copy()
     for dst, src in ((10, 500), (11, 500), (12, 500), (13, 500), (20, 700), (21, 700), (30, 900), (1400, 3), (1401, 3)):
-        u[dst], v[dst] = u[src], v[src]                       # collisions, also across the 256-thread / 2048-tile boundaries
+        u[dst], v[dst] = u[src], v[src]                       # collisions, also across 256-thread workgroups
     wgt = rs.uniform(0.2, 3.0, len(u)).astype(np.float32)
     idp = (idp * rs.uniform(0.9, 1.1, len(u))).astype(np.float32)
     import pyoracle
