@@ -572,6 +572,51 @@ typedef struct {
 } sdso_activate_t;
 int sdso_activate_points_batch(sdso_ctx* ctx, const sdso_activate_t* A, int8_t* status, float* idepth_out, uint8_t* res_state);
 
+/* CoarseDistanceMap (src/FullSystem/CoarseTracker.h:165-197) and the first half of FullSystem::activatePointsMT
+ * (FullSystem.cpp:823-902): the step between sdso_trace_on_batch and sdso_activate_points_batch.  One map per ctx, at pyramid
+ * level 1 (w1 = w >> 1, h1 = h >> 1), resident on the device; values are 0..39 (the growth step that reached the pixel) or 1000.
+ *
+ * sdso_distmap_make = CoarseDistanceMap::makeDistanceMap (CoarseTracker.cpp:1216-1255) + growDistBFS (:1260-1363).
+ *   geom[g]   : K[1] * fhToNew.rotationMatrix().cast<float>() * Ki[0] and K[1] * fhToNew.translation().cast<float>() of keyframe g as
+ *               the caller computes them at :1235-1236; point_geom[i] selects it
+ *   u, v, idepth_scaled : PointHessian members of the n active points, in the reference's loop order
+ *   n_seeds   : numItems — the projections inside 0 < u < w1, 0 < v < h1, duplicates counted (may be NULL)
+ * A projection whose quotient is not finite or does not fit an int (undefined in the reference) counts as outside the image.
+ * sdso_distmap_add = CoarseDistanceMap::addIntoDistFinal(u, v) (:1366-1372) for n pixels one after the other, in order.
+ * sdso_distmap_get = fwdWarpedIDDistFinal, w1*h1 floats.
+ * add / get / sdso_activate_select return SDSO_ERR_STATE until a map has been made on this ctx. */
+typedef struct { float KRKi[9]; float Kt[3]; } sdso_distmap_geom_t;
+int sdso_distmap_make(sdso_ctx* ctx, int w, int h, int ngeom, const sdso_distmap_geom_t* geom, int n, const int* point_geom,
+                      const float* u, const float* v, const float* idepth_scaled, int* n_seeds);
+int sdso_distmap_add(sdso_ctx* ctx, int n, const int* iu, const int* iv);
+int sdso_distmap_get(sdso_ctx* ctx, float* map /* w1*h1 */);
+
+/* FullSystem::activatePointsMT STEP 2 (FullSystem.cpp:837-902) for the n immature points of every keyframe but the newest, flattened
+ * in the reference's loop order (hosts in frameHessians order, each host's immaturePoints in index order).  Works on the map the
+ * preceding sdso_distmap_make left in the ctx and leaves the re-grown map there (every selection runs addIntoDistFinal, :893, so a
+ * candidate is tested against the points selected before it).
+ *   geom[g], host_flagged[g] : KRKi / Kt (:841-842) and FrameHessian::flaggedForMarginalization of host g; point_geom[i] selects it
+ *   lastTraceStatus          : ImmaturePointStatus (ImmaturePoint.h:50-56)
+ *   decision[n]   : 0 KEEP (stays immature), 1 DELETE (`delete ph; host->immaturePoints[i] = 0`), 2 SELECT (pushed to toOptimize)
+ *   iu, iv [n]    : the level-1 pixel of :884-885, valid where the candidate reached the distance test (SELECT, or KEEP by
+ *                   distance); unspecified elsewhere; may be NULL
+ *   n_selected    : toOptimize.size() (may be NULL) */
+typedef struct {
+  int w, h;                                /* wG[0], hG[0] */
+  int ngeom;
+  const sdso_distmap_geom_t* geom;         /* ngeom */
+  const uint8_t* host_flagged;             /* ngeom */
+  int n;
+  const int* point_geom;
+  const float* u; const float* v; const float* idepth_min; const float* idepth_max;
+  const float* quality; const float* lastTracePixelInterval;
+  const uint8_t* lastTraceStatus;
+  const float* my_type;
+  float currentMinActDist;                 /* FullSystem::currentMinActDist after STEP 1 (:798-817) */
+  float minTraceQuality;                   /* setting_minTraceQuality = 3 (settings.cpp:112) */
+} sdso_activate_select_t;
+int sdso_activate_select(sdso_ctx* ctx, const sdso_activate_select_t* S, uint8_t* decision, int* iu, int* iv, int* n_selected);
+
 /* Left-right-left matching as every caller of traceStereo performs it (FullSystem::stereoMatch FullSystem.cpp:581-613,
  * traceNewCoarseNonKey :667-725, CoarseTracker::makeCoarseDepthL0 CoarseTracker.cpp:295-347):
  *   forward: ImmaturePoint(u, v, frame A) traced into frame B   (interval idepth_min/max_stereo, NULL = fresh 0 / NaN)

@@ -132,6 +132,7 @@ void release_track_batch(sdso_ctx* ctx);
 void release_stereo(sdso_ctx* ctx);
 void release_selector(sdso_ctx* ctx);
 void release_g2o(sdso_ctx* ctx);
+void release_distmap(sdso_ctx* ctx);
 void release_comm(sdso_ctx* ctx);
 }
 
@@ -151,6 +152,7 @@ extern "C" void sdso_ctx_destroy(sdso_ctx* ctx) {
   release_stereo(ctx);
   release_selector(ctx);
   release_g2o(ctx);
+  release_distmap(ctx);
   release_comm(ctx);
   if (ctx->gammaB) hipFree(ctx->gammaB);
   if (ctx->scratch) hipFree(ctx->scratch);

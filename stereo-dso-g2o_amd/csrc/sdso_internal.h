@@ -53,6 +53,7 @@ struct TrackBatch;   // tracker.hip
 struct StereoState;  // stereo.hip
 struct SelState;     // selector.hip
 struct G2oState;     // g2o_factors.hip
+struct DistMapState; // distmap.hip
 struct Comm;         // comm.hip
 
 }  // namespace sdso
@@ -70,6 +71,7 @@ struct sdso_ctx {
   sdso::StereoState* stereo = nullptr;  // the prepared traceStereo batch and the matching batches
   sdso::SelState* sel = nullptr;        // the pixel selector's random pattern
   sdso::G2oState* g2o = nullptr;        // edge sets and partial systems of the g2o factors
+  sdso::DistMapState* dm = nullptr;     // the level-1 CoarseDistanceMap
   std::shared_ptr<sdso::Comm> comm;     // shared with the contexts joined by sdso_comm_attach
   // generic scratch
   void* scratch = nullptr;

@@ -21,6 +21,8 @@
 //   AccumulatedTopHessianSSE::{setZero, addPoint<mode>, addPointsInternal<mode>, stitchDouble, stitchDoubleMT}        OptimizationBackend/AccumulatedTopHessian.h:66-97, :162-169
 //   AccumulatedSCHessianSSE::{setZero, addPoint, addPointsInternal, stitchDouble, stitchDoubleMT}                     OptimizationBackend/AccumulatedSCHessian.h:66-96, :155-160
 //   EnergyFunctional::{calcLEnergyF_MT, calcMEnergyF, setDeltaF, setAdjointsF}                                       OptimizationBackend/EnergyFunctional.h:75-86
+//   CoarseDistanceMap::{makeK, makeDistanceMap, addIntoDistFinal, fwdWarpedIDDistFinal, K, Ki}                          FullSystem/CoarseTracker.h:165-197
+//   void FullSystem::activatePointsMT() STEP 1-2                                                                      FullSystem/FullSystem.cpp:796-902
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -872,6 +874,167 @@ inline auto traceOn(Device& dev, ImmaturePointT* p, int frame_slot, const Mat33f
   std::vector<uint8_t> st;
   traceOnAll(dev, one, std::vector<int>{0}, std::vector<sdso_trace_geom_t>{g}, frame_slot, st);
   return static_cast<decltype(p->lastTraceStatus)>(st[0]);
+}
+
+// =================================================================================== CoarseDistanceMap / activatePointsMT STEP 1-2
+// class CoarseDistanceMap (FullSystem/CoarseTracker.h:165-197) with the members its caller (FullSystem::activatePointsMT,
+// FullSystem.cpp:823-902) touches: makeK(CalibHessian*), makeDistanceMap(frameHessians, frame), addIntoDistFinal(u, v),
+// fwdWarpedIDDistFinal, K[], Ki[].  The map itself lives on the device (one per Device); fwdWarpedIDDistFinal is a host copy that
+// distFinal() refreshes on demand.  Mat33fT / Vec3fT are the reference's Eigen float types (element access (i, j) / [i]; an
+// `inverse()` member is used where the type has one).  The float products K[1] * R * Ki[0] and K[1] * t are formed here, row times
+// column summed left to right.
+namespace detail {
+template <class M> inline auto inverse33(const M& m, int) -> decltype(m.inverse()) { return m.inverse(); }
+template <class M> inline M inverse33(const M& m, long) {          // cofactors times 1 / det
+  M r;
+  const float c00 = m(1, 1) * m(2, 2) - m(1, 2) * m(2, 1), c10 = m(1, 2) * m(2, 0) - m(1, 0) * m(2, 2), c20 = m(1, 0) * m(2, 1) - m(1, 1) * m(2, 0);
+  const float id = 1.f / (c00 * m(0, 0) + c10 * m(0, 1) + c20 * m(0, 2));
+  r(0, 0) = c00 * id; r(1, 0) = c10 * id; r(2, 0) = c20 * id;
+  r(0, 1) = (m(0, 2) * m(2, 1) - m(0, 1) * m(2, 2)) * id; r(1, 1) = (m(0, 0) * m(2, 2) - m(0, 2) * m(2, 0)) * id; r(2, 1) = (m(0, 1) * m(2, 0) - m(0, 0) * m(2, 1)) * id;
+  r(0, 2) = (m(0, 1) * m(1, 2) - m(0, 2) * m(1, 1)) * id; r(1, 2) = (m(0, 2) * m(1, 0) - m(0, 0) * m(1, 2)) * id; r(2, 2) = (m(0, 0) * m(1, 1) - m(0, 1) * m(1, 0)) * id;
+  return r;
+}
+}  // namespace detail
+
+template <class Mat33fT>
+class CoarseDistanceMap {
+ public:
+  CoarseDistanceMap(Device& dev, int ww, int hh) : dev_(dev), buf_((size_t)(ww / 2) * (hh / 2), 1000.f) {
+    fwdWarpedIDDistFinal = buf_.data();
+    for (int l = 0; l < SDSO_PYR_LEVELS; l++) w[l] = h[l] = 0;
+  }
+  // makeK(CalibHessian*) — CoarseTracker.cpp:1374-1402 (pyrLevelsUsed and wG[0] / hG[0] are globals in the reference)
+  template <class CalibHessianT>
+  void makeK(CalibHessianT* HCalib, int pyrLevelsUsed, int wG0, int hG0) {
+    w[0] = wG0; h[0] = hG0;
+    fx[0] = HCalib->fxl(); fy[0] = HCalib->fyl(); cx[0] = HCalib->cxl(); cy[0] = HCalib->cyl();
+    for (int level = 1; level < pyrLevelsUsed; ++level) {
+      w[level] = w[0] >> level; h[level] = h[0] >> level;
+      fx[level] = fx[level - 1] * 0.5; fy[level] = fy[level - 1] * 0.5;
+      cx[level] = (cx[0] + 0.5) / ((int)1 << level) - 0.5;
+      cy[level] = (cy[0] + 0.5) / ((int)1 << level) - 0.5;
+    }
+    for (int level = 0; level < pyrLevelsUsed; ++level) {
+      Mat33fT& k = K[level];
+      k(0, 0) = fx[level]; k(0, 1) = 0; k(0, 2) = cx[level]; k(1, 0) = 0; k(1, 1) = fy[level]; k(1, 2) = cy[level]; k(2, 0) = 0; k(2, 1) = 0; k(2, 2) = 1;
+      Ki[level] = detail::inverse33(k, 0);
+      fxi[level] = Ki[level](0, 0); fyi[level] = Ki[level](1, 1); cxi[level] = Ki[level](0, 2); cyi[level] = Ki[level](1, 2);
+    }
+  }
+  // KRKi = K[1] * fhToNew.rotationMatrix().cast<float>() * Ki[0], Kt = K[1] * fhToNew.translation().cast<float>() with
+  // fhToNew = frame->PRE_worldToCam * fh->PRE_camToWorld (CoarseTracker.cpp:1232-1236, FullSystem.cpp:840-842)
+  template <class FrameHessianT>
+  sdso_distmap_geom_t geomOf(const FrameHessianT* fh, const FrameHessianT* frame) const {
+    const auto fhToNew = frame->PRE_worldToCam * fh->PRE_camToWorld;
+    const auto R = fhToNew.rotationMatrix();
+    const auto t = fhToNew.translation();
+    float Rf[9], KR[9];
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) Rf[i * 3 + j] = (float)R(i, j);
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) KR[i * 3 + j] = (K[1](i, 0) * Rf[j] + K[1](i, 1) * Rf[3 + j]) + K[1](i, 2) * Rf[6 + j];
+    sdso_distmap_geom_t g;
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) g.KRKi[i * 3 + j] = (KR[i * 3] * Ki[0](0, j) + KR[i * 3 + 1] * Ki[0](1, j)) + KR[i * 3 + 2] * Ki[0](2, j);
+    for (int i = 0; i < 3; i++) g.Kt[i] = (K[1](i, 0) * (float)t[0] + K[1](i, 1) * (float)t[1]) + K[1](i, 2) * (float)t[2];
+    return g;
+  }
+  // makeDistanceMap(std::vector<FrameHessian*> frameHessians, FrameHessian* frame) — CoarseTracker.cpp:1216-1255
+  template <class FrameHessianT>
+  void makeDistanceMap(std::vector<FrameHessianT*> frameHessians, FrameHessianT* frame) {
+    std::vector<sdso_distmap_geom_t> geom;
+    std::vector<int> pg;
+    std::vector<float> u, v, id;
+    for (FrameHessianT* fh : frameHessians) {
+      if (frame == fh) continue;
+      geom.push_back(geomOf(fh, frame));
+      for (auto* ph : fh->pointHessians) { pg.push_back((int)geom.size() - 1); u.push_back(ph->u); v.push_back(ph->v); id.push_back(ph->idepth_scaled); }
+    }
+    dev_.check(sdso_distmap_make(dev_.ctx(), w[0], h[0], (int)geom.size(), geom.data(), (int)u.size(), pg.data(), u.data(), v.data(), id.data(), &numItems),
+               "sdso_distmap_make");
+    stale_ = true;
+  }
+  // addIntoDistFinal(int u, int v) — CoarseTracker.cpp:1366-1372
+  void addIntoDistFinal(int u, int v) {
+    if (w[0] == 0) return;
+    dev_.check(sdso_distmap_add(dev_.ctx(), 1, &u, &v), "sdso_distmap_add");
+    stale_ = true;
+  }
+  // the host copy of the map, fetched when the device's has changed since the last call
+  float* distFinal() {
+    if (stale_) { dev_.check(sdso_distmap_get(dev_.ctx(), buf_.data()), "sdso_distmap_get"); stale_ = false; }
+    return fwdWarpedIDDistFinal;
+  }
+  void markStale() { stale_ = true; }
+  Device& device() { return dev_; }
+
+  float* fwdWarpedIDDistFinal;
+  Mat33fT K[SDSO_PYR_LEVELS];
+  Mat33fT Ki[SDSO_PYR_LEVELS];
+  float fx[SDSO_PYR_LEVELS], fy[SDSO_PYR_LEVELS], fxi[SDSO_PYR_LEVELS], fyi[SDSO_PYR_LEVELS];
+  float cx[SDSO_PYR_LEVELS], cy[SDSO_PYR_LEVELS], cxi[SDSO_PYR_LEVELS], cyi[SDSO_PYR_LEVELS];
+  int w[SDSO_PYR_LEVELS], h[SDSO_PYR_LEVELS];
+  int numItems = 0;                                   // bfsNum handed to growDistBFS by the last makeDistanceMap
+
+ private:
+  Device& dev_;
+  std::vector<float> buf_;
+  bool stale_ = false;
+};
+
+// activatePointsMT STEP 1 (FullSystem.cpp:798-817): `float currentMinActDist` moved by double literals
+inline void updateMinActDist(float& currentMinActDist, int nPoints, float setting_desiredPointDensity) {
+  if (nPoints < setting_desiredPointDensity * 0.66) currentMinActDist -= 0.8;
+  if (nPoints < setting_desiredPointDensity * 0.8) currentMinActDist -= 0.5;
+  else if (nPoints < setting_desiredPointDensity * 0.9) currentMinActDist -= 0.2;
+  else if (nPoints < setting_desiredPointDensity) currentMinActDist -= 0.1;
+  if (nPoints > setting_desiredPointDensity * 1.5) currentMinActDist += 0.8;
+  if (nPoints > setting_desiredPointDensity * 1.3) currentMinActDist += 0.5;
+  if (nPoints > setting_desiredPointDensity * 1.15) currentMinActDist += 0.2;
+  if (nPoints > setting_desiredPointDensity) currentMinActDist += 0.1;
+  if (currentMinActDist < 0) currentMinActDist = 0;
+  if (currentMinActDist > 4) currentMinActDist = 4;
+}
+
+// activatePointsMT STEP 2 (FullSystem.cpp:837-902) over the callers' immaturePoints vectors, after coarseDistanceMap->makeDistanceMap:
+// every candidate gets idxInImmaturePoints, the deleted ones are `delete`d and their entry is set to 0 exactly where the reference
+// does it, the selected ones come back in toOptimize order; the map on the device has been re-grown around each of them.
+template <class CoarseDistanceMapT, class FrameHessianT>
+inline auto selectPointsToActivate(CoarseDistanceMapT& cdm, std::vector<FrameHessianT*>& frameHessians, float currentMinActDist, float setting_minTraceQuality)
+    -> std::vector<typename std::remove_reference<decltype(*frameHessians[0]->immaturePoints[0])>::type*> {
+  using ImmaturePointT = typename std::remove_reference<decltype(*frameHessians[0]->immaturePoints[0])>::type;
+  std::vector<ImmaturePointT*> toOptimize;
+  toOptimize.reserve(20000);
+  FrameHessianT* newestHs = frameHessians.back();
+  std::vector<sdso_distmap_geom_t> geom;
+  std::vector<uint8_t> flagged, st;
+  std::vector<int> pg;
+  std::vector<float> u, v, imin, imax, q, itv, ty;
+  for (FrameHessianT* host : frameHessians) {
+    if (host == newestHs) continue;
+    geom.push_back(cdm.geomOf(host, newestHs));
+    flagged.push_back(host->flaggedForMarginalization ? 1 : 0);
+    for (unsigned int i = 0; i < host->immaturePoints.size(); i += 1) {
+      ImmaturePointT* ph = host->immaturePoints[i];
+      ph->idxInImmaturePoints = i;
+      pg.push_back((int)geom.size() - 1); u.push_back(ph->u); v.push_back(ph->v); imin.push_back(ph->idepth_min); imax.push_back(ph->idepth_max);
+      q.push_back(ph->quality); itv.push_back(ph->lastTracePixelInterval); st.push_back((uint8_t)ph->lastTraceStatus); ty.push_back(ph->my_type);
+    }
+  }
+  const int n = (int)u.size();
+  std::vector<uint8_t> decision(n);
+  sdso_activate_select_t S{cdm.w[0], cdm.h[0], (int)geom.size(), geom.data(), flagged.data(), n, pg.data(), u.data(), v.data(), imin.data(), imax.data(),
+                           q.data(), itv.data(), st.data(), ty.data(), currentMinActDist, setting_minTraceQuality};
+  int n_selected = 0;
+  cdm.device().check(sdso_activate_select(cdm.device().ctx(), &S, decision.data(), nullptr, nullptr, &n_selected), "sdso_activate_select");
+  cdm.markStale();
+  int k = 0;
+  for (FrameHessianT* host : frameHessians) {
+    if (host == newestHs) continue;
+    for (unsigned int i = 0; i < host->immaturePoints.size(); i += 1, k++) {
+      ImmaturePointT* ph = host->immaturePoints[i];
+      if (decision[k] == 1) { delete ph; host->immaturePoints[i] = 0; }
+      else if (decision[k] == 2) toOptimize.push_back(ph);
+    }
+  }
+  return toOptimize;
 }
 
 // EnergyFunctional::marginalizeFrame's algebra (EnergyFunctional.cpp:554-660) on plain row-major arrays

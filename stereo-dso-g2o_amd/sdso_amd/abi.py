@@ -129,6 +129,30 @@ class Activate(C.Structure):
                 ("color", c_float_p), ("weights", c_float_p), ("energyTH", c_float_p)]
 
 
+class DistMapGeom(C.Structure):
+    """sdso_distmap_geom_t: K[1] * R * Ki[0] and K[1] * t of one keyframe into the newest (CoarseTracker.cpp:1235-1236)."""
+    _fields_ = [("KRKi", C.c_float * 9), ("Kt", C.c_float * 3)]
+
+
+class ActivateSelect(C.Structure):
+    """sdso_activate_select_t: the candidates of FullSystem::activatePointsMT STEP 2 (FullSystem.cpp:837-902)."""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("ngeom", C.c_int), ("geom", C.POINTER(DistMapGeom)), ("host_flagged", c_u8_p),
+                ("n", C.c_int), ("point_geom", c_int_p), ("u", c_float_p), ("v", c_float_p), ("idepth_min", c_float_p), ("idepth_max", c_float_p),
+                ("quality", c_float_p), ("lastTracePixelInterval", c_float_p), ("lastTraceStatus", c_u8_p), ("my_type", c_float_p),
+                ("currentMinActDist", C.c_float), ("minTraceQuality", C.c_float)]
+
+
+def make_distmap_geoms(KRKi, Kt):
+    """(ng, 3, 3) and (ng, 3) float32 arrays -> a ctypes array of DistMapGeom."""
+    KRKi = np.ascontiguousarray(KRKi, np.float32).reshape(-1, 9)
+    Kt = np.ascontiguousarray(Kt, np.float32).reshape(-1, 3)
+    G = (DistMapGeom * max(1, len(KRKi)))()
+    for g in range(len(KRKi)):
+        G[g].KRKi[:] = KRKi[g].tolist()
+        G[g].Kt[:] = Kt[g].tolist()
+    return G
+
+
 class StereoMatch(C.Structure):
     _fields_ = [("n", C.c_int), ("u", c_float_p), ("v", c_float_p), ("idepth_min_stereo", c_float_p), ("idepth_max_stereo", c_float_p),
                 ("back_idepth_min_stereo", c_float_p), ("back_idepth_max_stereo", c_float_p), ("status_fwd", c_u8_p), ("status_back", c_u8_p),
@@ -358,6 +382,10 @@ def load():
     L.sdso_g2o_track_newest_coarse.argtypes = [vp, C.c_int, C.c_int, C.POINTER(TrackParams), C.POINTER(SE3), C.POINTER(Aff), C.POINTER(TrackResult)]
     L.sdso_g2o_lba_eval.argtypes = [vp, C.POINTER(G2oLba), c_double_p, c_double_p, c_u8_p, c_float_p, c_float_p, c_float_p, c_u8_p]
     L.sdso_trace_set_gn_mode.argtypes = [vp, C.c_int]
+    L.sdso_distmap_make.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(DistMapGeom), C.c_int, c_int_p, c_float_p, c_float_p, c_float_p, c_int_p]
+    L.sdso_distmap_add.argtypes = [vp, C.c_int, c_int_p, c_int_p]
+    L.sdso_distmap_get.argtypes = [vp, c_float_p]
+    L.sdso_activate_select.argtypes = [vp, C.POINTER(ActivateSelect), c_u8_p, c_int_p, c_int_p, c_int_p]
     _lib = L
     return L
 
@@ -381,6 +409,7 @@ EXPORTED_SYMBOLS = [
     "sdso_ba_batch_optimize", "sdso_ba_batch_optimize_begin", "sdso_ba_batch_step", "sdso_ba_batch_solve_step", "sdso_ba_batch_optimize_end", "sdso_ba_get_state",
     "sdso_comm_unique_id", "sdso_comm_init", "sdso_comm_init_host", "sdso_comm_attach", "sdso_comm_info", "sdso_comm_destroy", "sdso_ba_allreduce", "sdso_ba_allreduce_window",
     "sdso_g2o_track_add_edges", "sdso_g2o_track_linearize", "sdso_g2o_track_newest_coarse", "sdso_g2o_lba_eval", "sdso_trace_set_gn_mode",
+    "sdso_distmap_make", "sdso_distmap_add", "sdso_distmap_get", "sdso_activate_select",
 ]
 
 
