@@ -386,6 +386,67 @@ int sdso_ba_get_deltas(sdso_ctx* ctx, int win, float* cDeltaF, double* frame_del
 int sdso_ba_marginalize_frame_dev(sdso_ctx* ctx, int win, int idx, double* HM_out, double* bM_out);
 int sdso_ba_adopt_prior(sdso_ctx* ctx, int win, int from_win);
 
+/* Edit an uploaded window IN PLACE: the device form of EnergyFunctional::insertResidual (EnergyFunctional.cpp:445), insertFrame (:462),
+ * insertPoint (:507), dropResidual (:524), dropPointsF (:739), removePoint (:755), the removePoint loop of marginalizePointsF (:692-696)
+ * and the residual drops of FullSystem::marginalizeFrame (FullSystemMarginalize.cpp:146-198).  The seven stages run in this order; every
+ * index of an existing frame / point / residual refers to the window BEFORE the call (an appended frame k is nf_before + k).  Any stage
+ * may be empty.  Afterwards the window is what sdso_ba_upload_window of the edited window would have made (makeIDX order, :998-1018),
+ * with every float-valued state of the surviving points and residuals carried on the device:
+ *   carried (device)     : u, v, idepth, idepth_zero, colour, weights, maxRelBaseline, numGoodResiduals, res_state, isNew
+ *   carried (host mirror): calibration, frame states / evalPT / frameEnergyTH / exposure / frameID / slot, hasDepthPrior, solverMode,
+ *                          affine modes, forceAcceptStep, resInM
+ *   prior                : no frame leaves: HM / bM as the device holds them, the rows / columns of appended frames zero (insertFrame,
+ *                          :476-482).  Frames leave: the caller has run sdso_ba_marginalize_frame_dev for exactly those frames since the
+ *                          last sdso_ba_marginalize_points; that chained prior is installed device to device.
+ *   everything else      : as after an upload (no post-state, nothing linearised, accumulators cleared). */
+typedef struct {
+  /* stage 1  dropResidual (:524-533), one after the other in the given order: the LAST entry of residualsAll takes the freed slot */
+  int n_drop_res;      const int* drop_res;
+  /* stage 2  removePoint (:755-771) one after the other in the given order: marginalizePointsF's loop over allPointsToMarg (:692-696) */
+  int n_remove_points; const int* remove_points;
+  /* stage 3  dropPointsF (:739-752): per host frame the rescanning loop `if flagged: removePoint, i--` */
+  const uint8_t* drop_point;                        /* np flags, or NULL */
+  /* stage 4  frames leave, one after the other (FullSystemMarginalize.cpp:146-198): every remaining point drops its residual into that
+   *          frame (swap-with-last), then the frame is erased and later frames move up */
+  int n_remove_frames; const int* remove_frames;
+  /* stage 5  insertFrame (:462-504): appended at the end */
+  int n_add_frames;
+  const double* evalPT; const double* state; const double* state_zero;      /* as in sdso_ba_window_t, n_add_frames entries */
+  const float* ab_exposure; const float* frameEnergyTH; const int* frameID; const int* frame_slot;
+  /* stage 6  insertResidual (:445-458) on surviving points: pushed to the back of residualsAll in the given order */
+  int n_add_res; const int* add_res_point; const int* add_res_target;
+  const uint8_t* add_res_state; const uint8_t* add_res_isNew;               /* isNew NULL: 1 */
+  /* stage 7  insertPoint (:507-521): pushed to the back of its host's list in the given order, with its residuals */
+  int n_add_points;
+  const int* pt_host;                               /* may be an appended frame */
+  const float* pt_u; const float* pt_v; const float* pt_idepth; const float* pt_idepth_zero;
+  const float* pt_color; const float* pt_weights;   /* n_add_points*8 */
+  const uint8_t* pt_hasDepthPrior; const float* pt_maxRelBaseline; const int* pt_numGoodResiduals;   /* the last two NULL: 0 */
+  int n_pt_res; const int* pt_res_point;            /* index into the appended points, non-decreasing */
+  const int* pt_res_target; const uint8_t* pt_res_state; const uint8_t* pt_res_isNew;                /* isNew NULL: 1 */
+} sdso_ba_window_edit_t;
+/* The order the edit produces, on the host without a ctx (like sdso_ba_marginalize_frame).
+ *   in : nf, np, nr, host[np], res_point[nr], res_target[nr] of the window before the edit
+ *   out: nf2 / np2 / nr2 and, each optional, frame_src[nf2], point_src[np2], res_src[nr2]: the index before the edit, or -1-k for the
+ *        k-th appended frame / point / residual (stage 6's residuals first, then stage 7's).  Size the arrays for nf + n_add_frames,
+ *        np + n_add_points, nr + n_add_res + n_pt_res.
+ * SDSO_ERR_ARG for an edit the reference could not perform: an index out of range or named twice in one stage; a point or residual
+ * named after an earlier stage removed it; a residual added to a point that leaves, onto its own host, onto a target the point already
+ * observes, as a ninth residual, or into a frame that leaves; a frame leaving that still hosts a point
+ * (assert(frame->pointHessians.size()==0), FullSystemMarginalize.cpp:148); more than 8 frames. */
+int sdso_ba_window_plan(int nf, int np, int nr, const int* host, const int* res_point, const int* res_target,
+                        const sdso_ba_window_edit_t* E, int* nf2, int* np2, int* nr2,
+                        int* frame_src, int* point_src, int* res_src);
+/* Apply the edit (enqueue only, like sdso_ba_upload_window).  Every refusal is decided before any device work and leaves the window as it
+ * was: SDSO_ERR_ARG as for sdso_ba_window_plan or for an appended frame without an uploaded pyramid of the window's size; SDSO_ERR_STATE
+ * for a window inside a batch (sdso_ba_batch_create again afterwards), a surviving residual that is linearised (fixLinearizationF only
+ * touches points that leave), a frame removal without the matching sdso_ba_marginalize_frame_dev calls, and an edit that removes no
+ * frame after sdso_ba_marginalize_frame_dev has run (its prior would be lost). */
+int sdso_ba_window_update(sdso_ctx* ctx, int win, const sdso_ba_window_edit_t* E);
+/* The maps of the latest sdso_ba_window_update of this window (sizes: its current nf / np / nr; each may be NULL); SDSO_ERR_STATE when
+ * the window has not been updated since its upload. */
+int sdso_ba_window_get_order(sdso_ctx* ctx, int win, int* frame_src, int* point_src, int* res_src);
+
 /* keep projectedTo / centerProjectedTo of PointFrameResidual (Residuals.h:96-99) for
  * sdso_ba_get_linearization; off by default (76 B of extra stores per residual). */
 int sdso_ba_keep_projections(sdso_ctx* ctx, int win, int on);

@@ -73,6 +73,9 @@ struct BaWindowDev {
   sdso_ba_opt_result_t last_result{0, 0, 0, 0};
   float* d_post = nullptr;      // nr x 19: projectedTo, centerProjectedTo of the closing linearisation
   int resInL = 0, resInM = 0;
+  // sdso_ba_window_update: where every frame / point / residual of this window came from (sdso_ba_window_get_order)
+  bool has_order = false;
+  std::vector<int> ord_frame, ord_point, ord_res;
 };
 
 // zeroed device buffer for a window: reuse a pooled buffer of a released window when one of a similar size exists
@@ -274,7 +277,13 @@ extern "C" int sdso_ba_release_window(sdso_ctx* ctx, int win) {
   return SDSO_OK;
 }
 
-static int upload_window_impl(sdso_ctx* ctx, int win, const sdso_ba_window_t* Win) {
+// What sdso_ba_window_update (ba_update.hip) hands to the upload: the window being replaced and, per point / residual of the new window
+// (window order), the index in the old one whose device state is carried (< 0: the entry is new and comes from Win like any uploaded one).
+struct WindowCarry { BaWindowDev* old; const int* point_src; const int* res_src; const double* prior_H; const double* prior_b; int prior_dim; };
+static void launch_window_gather(sdso_ctx* ctx, const BaWindowDev* W, const WindowCarry& cy, const int* d_psrc, const int* d_rsrc);   // ba_update.hip
+// carry == nullptr: sdso_ba_upload_window.  Otherwise the old window stays registered and untouched (the caller swaps the two once this
+// returned SDSO_OK, or frees *made), and the surviving entries' rows are gathered from its slab after the staged copy.
+static int upload_window_impl(sdso_ctx* ctx, int win, const sdso_ba_window_t* Win, const WindowCarry* carry = nullptr, BaWindowDev** made = nullptr) {
   if (!ctx) return SDSO_ERR_STATE;
   SDSO_HIP(ctx, hipSetDevice(ctx->device));
   SDSO_REQUIRE(ctx, Win, "null window");
@@ -293,12 +302,13 @@ static int upload_window_impl(sdso_ctx* ctx, int win, const sdso_ba_window_t* Wi
     fprintf(stderr, "[sdso_ba_upload_window] %-28s %7.1f us\n", what, std::chrono::duration<double, std::micro>(t - t_prev).count());
     t_prev = t;
   };
-  int rc = sdso_ba_release_window(ctx, win);
+  int rc = carry ? SDSO_OK : sdso_ba_release_window(ctx, win);
   if (rc) return rc;
   mark("release of the old window");
 
   BaWindowDev* W = new BaWindowDev();
-  ctx->wins[win] = W;
+  if (made) *made = W;
+  if (!carry) ctx->wins[win] = W;
   BaDev& d = W->d;
   std::memset(&d, 0, sizeof(d));
   d.nf = nf; d.np = np; d.nr = nr; d.nrp = (nr + 63) & ~63; d.w = Win->w; d.h = Win->h; d.n = 8 * nf + 4;
@@ -458,6 +468,8 @@ static int upload_window_impl(sdso_ctx* ctx, int win, const sdso_ba_window_t* Wi
   PL(d.sol, double, sol_doubles(n, nf), false);
   PL(W->d_pflag, uint8_t, np, false); PL(W->d_sums, float, 2 * (W->nblk_pts + 1), false);
   PL(W->d_opt, BaOptDev, 1, false);
+  int *g_psrc = nullptr, *g_rsrc = nullptr;     // sdso_ba_window_update: the gather maps (pair-sorted for the residuals), staged with the rest
+  if (carry) { PL(g_psrc, int, np, true); PL(g_rsrc, int, nr, true); }
 #undef PL
   size_t init_bytes = 0, total = 0;
   for (int pass = 0; pass < 2; pass++) {
@@ -530,6 +542,11 @@ static int upload_window_impl(sdso_ctx* ctx, int win, const sdso_ba_window_t* Wi
   STG(d_chunks, chunks.data(), sizeof(int4) * chunks.size()); STG(d_pair_beg, pair_beg.data(), sizeof(int) * (nf * nf + 1));
   STG(d_items, items.data(), sizeof(int4) * items.size()); STG(d_host_beg, host_beg.data(), sizeof(int) * (nf + 1));
   STG(W->dt_HM, W->HM.data(), sizeof(double) * n * n); STG(W->dt_bM, W->bM.data(), sizeof(double) * n);
+  if (carry) {
+    std::vector<int> rs(nr);
+    for (int j = 0; j < nr; j++) { const int o = carry->res_src[W->perm[j]]; rs[j] = o >= 0 ? carry->old->inv[o] : -1; }
+    STG(g_psrc, carry->point_src, sizeof(int) * np); STG(g_rsrc, rs.data(), sizeof(int) * nr);
+  }
   mark("staging of points / residuals");
   // the tables at the uploaded state, staged with everything else
   build_tables(W, true);
@@ -545,6 +562,7 @@ static int upload_window_impl(sdso_ctx* ctx, int win, const sdso_ba_window_t* Wi
   mark("tables (adjoints, projector)");
   SDSO_HIP(ctx, hipMemcpyAsync(slab, stage, init_bytes, hipMemcpyHostToDevice, ctx->stream));
   if (total > init_bytes) SDSO_HIP(ctx, hipMemsetAsync(slab + init_bytes, 0, total - init_bytes, ctx->stream));
+  if (carry) launch_window_gather(ctx, W, *carry, g_psrc, g_rsrc);   // the survivors' rows and the prior: old slab -> new slab
   // per-residual record: target in slot 15, newState OUTLIER, newEnergyWO -1
   if (nr) hipLaunchKernelGGL(k_ba_init_res, dim3(W->nblk_res), dim3(BA_BLOCK), 0, ctx->stream, W->d_self);
   SDSO_HIP(ctx, hipGetLastError());
@@ -1673,10 +1691,11 @@ extern "C" int sdso_ba_marginalize_frame_dev(sdso_ctx* ctx, int win, int idx, do
 // columns zero — what EnergyFunctional::insertFrame does to HM / bM (EnergyFunctional.cpp:468-476: conservativeResize + setZero of the new
 // rows and columns).  `win` must have been uploaded with HM = bM = NULL (zeros) and its LEADING frames must be the frames the prior covers,
 // in the same order (checked by frameID): a prior attached to other frames is an error, never a silent result.
-__global__ __launch_bounds__(256) void k_ba_prior_adopt(double* __restrict__ HM, double* __restrict__ bM, int n, const double* __restrict__ src, int m) {
+__global__ __launch_bounds__(256) void k_ba_prior_adopt(double* __restrict__ HM, double* __restrict__ bM, int n, const double* __restrict__ srcH,
+                                                        const double* __restrict__ srcb, int m) {
   for (int e = blockIdx.x * 256 + threadIdx.x; e < n * n + n; e += gridDim.x * 256) {
-    if (e < n * n) { const int i = e / n, j = e - i * n; HM[e] = (i < m && j < m) ? src[(size_t)i * m + j] : 0.0; }
-    else { const int i = e - n * n; bM[i] = i < m ? src[(size_t)m * m + i] : 0.0; }
+    if (e < n * n) { const int i = e / n, j = e - i * n; HM[e] = (i < m && j < m) ? srcH[(size_t)i * m + j] : 0.0; }
+    else { const int i = e - n * n; bM[i] = i < m ? srcb[i] : 0.0; }
   }
 }
 extern "C" int sdso_ba_adopt_prior(sdso_ctx* ctx, int win, int from_win) {
@@ -1689,7 +1708,7 @@ extern "C" int sdso_ba_adopt_prior(sdso_ctx* ctx, int win, int from_win) {
   SDSO_REQUIRE(ctx, W->prior_pristine, "the adopting window must have been uploaded with HM = bM = NULL and not have changed its prior since");
   for (int i = 0; i < k; i++)
     SDSO_REQUIRE(ctx, W->frames[i].frameID == F->frames[F->marg_frames[i]].frameID, "the window's leading frames are not the frames the prior covers (frameID mismatch)");
-  hipLaunchKernelGGL(k_ba_prior_adopt, dim3(8), dim3(256), 0, ctx->stream, W->dt_HM, W->dt_bM, n, (const double*)F->d_marg, m);
+  hipLaunchKernelGGL(k_ba_prior_adopt, dim3(8), dim3(256), 0, ctx->stream, W->dt_HM, W->dt_bM, n, (const double*)F->d_marg, (const double*)F->d_marg + (size_t)m * m, m);
   SDSO_HIP(ctx, hipGetLastError());
   W->hm_host_valid = false;
   W->accumulated = false;
@@ -2317,3 +2336,6 @@ extern "C" int sdso_ba_get_counts(sdso_ctx* ctx, int win, int* resInA, int* resI
   if (resInM) *resInM = W->resInM;
   return SDSO_OK;
 }
+
+
+#include "ba_update.hip"   // sdso_ba_window_plan / _update / _get_order (same translation unit: upload_window_impl is the builder)

@@ -24,6 +24,7 @@
 //   CoarseDistanceMap::{makeK, makeDistanceMap, addIntoDistFinal, fwdWarpedIDDistFinal, K, Ki}                          FullSystem/CoarseTracker.h:165-197
 //   void FullSystem::activatePointsMT() STEP 1-2                                                                      FullSystem/FullSystem.cpp:796-902
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -339,6 +340,8 @@ class WindowedBA {
     for (size_t i = 0; i < residuals_.size(); i++) res_index_[residuals_[i]->data] = (int)i;
     for (size_t i = 0; i < points_.size(); i++) point_index_[points_[i]] = (int)i;
     lin_valid_ = app_valid_ = acc_valid_ = marg_valid_ = false;
+    frames_.assign(ef->frames.begin(), ef->frames.end());
+    clearPending_();
   }
 
   // Vec3 FullSystem::linearizeAll(false): returns lastEnergyP
@@ -360,6 +363,7 @@ class WindowedBA {
   template <class PointFrameResidualT>
   double linearize(PointFrameResidualT* r, CalibHessianT* /*HCalib*/) {
     if (r->efResidual->isLinearized) return 0.0;
+    requireNoPendingEdit_("linearize");
     if (!lin_valid_) {
       const int nr = (int)residuals_.size();
       linearizeAll();
@@ -385,6 +389,7 @@ class WindowedBA {
       return;
     }
     if (!app_valid_) {
+      requireNoPendingEdit_("applyRes");
       const int nr = (int)residuals_.size();
       applyRes();
       a_state_.assign(nr, 0); a_act_.assign(nr, 0);
@@ -537,6 +542,7 @@ class WindowedBA {
   // RawResidualJacobian records (EFResidual::J) — only the accumulators this library replaces read them.
   // Returns sqrtf(lastEnergy[0] / (patternNum * ef->resInA)) like the reference (:1039); lastResult carries lastEnergy[0].
   float optimize(int mnumOptIts, EnergyFunctionalT* ef, CalibHessianT* HCalib) {
+    requireNoPendingEdit_("optimize");
     const int nf = nf_, np = (int)points_.size(), nr = (int)residuals_.size(), n = 8 * nf + 4;
     sdso_ba_opt_result_t out;
     lin_valid_ = app_valid_ = acc_valid_ = marg_valid_ = false;
@@ -612,6 +618,7 @@ class WindowedBA {
       for (unsigned int k = 0; k < ph->residuals.size(); k++)
         if (ph->residuals[k] == pfr) {
           ef->dropResidual(pfr->efResidual);
+          res_index_.erase(pfr); residuals_[i] = nullptr; pending_drop_res_.push_back(i);   // stage 1 of the next update(), in toRemove order
           delete ph->residuals[k];                         // deleteOut<PointFrameResidual>(ph->residuals, k), FullSystem.h:62-71
           ph->residuals[k] = ph->residuals.back();
           ph->residuals.pop_back();
@@ -619,7 +626,7 @@ class WindowedBA {
           break;
         }
     }
-    residuals_.clear();                                    // (dropResidual deleted some of them: re-upload before the next call)
+    // (dropResidual deleted some residuals: their slots in residuals_ are null until update() — or upload() — brings the device window in line)
     lastRemoved = nResRemoved;
     // ---- EnergyFunctional
     ef->lastX.resize(n); ef->lastbS.resize(n); ef->lastHS.resize(n, n);
@@ -636,6 +643,7 @@ class WindowedBA {
   // The caller goes on with the reference's removePoint loop (:730-735).
   template <class IsMarg>
   void marginalizePointsF(EnergyFunctionalT* ef, IsMarg is_marg) {
+    requireNoPendingEdit_("marginalizePointsF");
     std::vector<uint8_t> flag(points_.size());
     for (size_t p = 0; p < points_.size(); p++) flag[p] = is_marg(points_[p]) ? 1 : 0;
     const int n = 8 * nf_ + 4;
@@ -648,7 +656,170 @@ class WindowedBA {
   }
   sdso_ba_opt_result_t lastResult{};
 
+  // ---- the window stays on the device from one call to the next (sdso_ba_window_update) instead of being flattened and uploaded again.
+  // The reference deletes the objects it removes, so the shim is told about a removal BEFORE the reference performs it (an index is
+  // looked up while the pointer is still valid, and a later object at the same address cannot be mistaken for it):
+  //   optimize()                      notes the toRemove drops itself (stage 1)
+  //   willRemovePoint(p)              before each ef->removePoint(p) of marginalizePointsF's loop (EnergyFunctional.cpp:692-696): stage 2
+  //   willDropPoints(is_drop)         before ef->dropPointsF() (:739-752), is_drop(p) = p->stateFlag == EFPointStatus::PS_DROP: stage 3
+  //   marginalizeFrame(ef, f)         in place of the algebra of EnergyFunctional::marginalizeFrame (:560-628) on the device-resident prior
+  //                                   (sdso_ba_marginalize_frame_dev), ef->HM / ef->bM written back; the caller goes on with :631-660.
+  //                                   The residuals into that frame are dropped by FullSystem::marginalizeFrame as before: stage 4
+  //   update(ef, slot_of)             after the reference inserted what the next keyframe brings (insertFrame, insertResidual, insertPoint):
+  //                                   frames / residuals / points the shim has not seen are stages 5-7, in makeIDX order
+  // update() leaves points_ / residuals_ and their index maps describing the edited window (checked against sdso_ba_window_get_order).
+  template <class EFPointT>
+  void willRemovePoint(EFPointT* p) {
+    const int i = point_index_.at(p);
+    pending_rm_points_.push_back(i);
+    forgetPoint_(i);
+  }
+  template <class IsDrop>
+  void willDropPoints(IsDrop is_drop) {
+    if (pending_drop_flags_.empty()) pending_drop_flags_.assign(points_.size(), 0);
+    for (size_t i = 0; i < points_.size(); i++)
+      if (points_[i] && is_drop(points_[i])) { pending_drop_flags_[i] = 1; forgetPoint_((int)i); }
+  }
+  template <class EFFrameT>
+  void marginalizeFrame(EnergyFunctionalT* ef, EFFrameT* f) {
+    int old_idx = -1, idx = 0;                             // idx counts the frames the prior still covers (sdso_abi.h)
+    for (size_t k = 0; k < frames_.size(); k++) {
+      if (frames_[k] == f) { old_idx = (int)k; break; }
+      if (std::find(pending_rm_frames_.begin(), pending_rm_frames_.end(), (int)k) == pending_rm_frames_.end()) idx++;
+    }
+    if (old_idx < 0) throw Error("marginalizeFrame: the frame is not part of the uploaded window");
+    const int left = nf_ - (int)pending_rm_frames_.size() - 1, m = 8 * left + 4;
+    std::vector<double> H((size_t)m * m), b(m);
+    dev_.check(sdso_ba_marginalize_frame_dev(dev_.ctx(), win_, idx, H.data(), b.data()), "sdso_ba_marginalize_frame_dev");
+    ef->HM.resize(m, m); ef->bM.resize(m);
+    for (int i = 0; i < m; i++) { ef->bM[i] = b[i]; for (int j = 0; j < m; j++) ef->HM(i, j) = H[(size_t)i * m + j]; }
+    pending_rm_frames_.push_back(old_idx);
+    for (size_t i = 0; i < residuals_.size(); i++)         // FullSystem::marginalizeFrame drops them next (FullSystemMarginalize.cpp:150-180)
+      if (residuals_[i] && residuals_[i]->target == f) { res_index_.erase(residuals_[i]->data); residuals_[i] = nullptr; }
+  }
+  template <class SlotOf>
+  void update(EnergyFunctionalT* ef, SlotOf slot_of) {
+    const int nf_old = nf_;
+    std::unordered_map<const void*, int> frame_old;        // EFFrame* -> index before the call (appended frames: nf_old + k)
+    for (int k = 0; k < nf_old; k++)
+      if (std::find(pending_rm_frames_.begin(), pending_rm_frames_.end(), k) == pending_rm_frames_.end()) frame_old[frames_[k]] = k;
+    // ---- stage 5: frames the shim has not seen (insertFrame appends, EnergyFunctional.cpp:465-466)
+    std::vector<double> evalPT, state, state_zero; std::vector<float> exposure, energyTH; std::vector<int> frameID, slots;
+    int n_add_frames = 0;
+    for (auto* f : ef->frames) {
+      if (frame_old.count(f)) { if (n_add_frames) throw Error("update: a known frame follows a new one"); continue; }
+      auto* fh = f->data;
+      const sdso_se3_t T = toAbi(fh->get_worldToCam_evalPT());
+      evalPT.insert(evalPT.end(), T.R, T.R + 9); evalPT.insert(evalPT.end(), T.t, T.t + 3);
+      for (int i = 0; i < 10; i++) { state.push_back(fh->get_state()[i]); state_zero.push_back(fh->get_state_zero()[i]); }
+      exposure.push_back(fh->ab_exposure); energyTH.push_back(fh->frameEnergyTH); frameID.push_back(fh->frameID); slots.push_back(slot_of(fh));
+      frame_old[f] = nf_old + n_add_frames++;
+    }
+    auto frame_of = [&](const void* f) {
+      auto it = frame_old.find(f);
+      if (it == frame_old.end()) throw Error("update: a residual or point names a frame that is not part of the window (a frame that left?)");
+      return it->second;
+    };
+    // ---- stages 6 and 7: the residuals and points the shim has not seen, in makeIDX order (EnergyFunctional.cpp:998-1018)
+    std::vector<int> ar_point, ar_target, pt_host, pt_ngood, pr_point, pr_target;
+    std::vector<uint8_t> ar_state, ar_new, pt_prior, pr_state, pr_new;
+    std::vector<float> pt_u, pt_v, pt_id, pt_idz, pt_col, pt_wgt, pt_mrb;
+    std::vector<int> want_point, want_res;                 // what sdso_ba_window_get_order must say
+    decltype(points_) new_points; decltype(residuals_) new_residuals;
+    for (auto* f : ef->frames)
+      for (auto* p : f->points) {
+        auto it = point_index_.find(p);
+        new_points.push_back(p);
+        if (it != point_index_.end()) {
+          want_point.push_back(it->second);
+          for (auto* r : p->residualsAll) {
+            new_residuals.push_back(r);
+            auto ir = res_index_.find(r->data);
+            if (ir != res_index_.end()) { want_res.push_back(ir->second); continue; }
+            want_res.push_back(-1 - (int)ar_point.size());
+            ar_point.push_back(it->second); ar_target.push_back(frame_of(r->target));
+            ar_state.push_back((uint8_t)r->data->state_state); ar_new.push_back(r->data->isNew ? 1 : 0);
+          }
+        } else {
+          auto* ph = p->data;
+          const int q = (int)pt_host.size();
+          want_point.push_back(-1 - q);
+          pt_host.push_back(frame_of(f));
+          pt_u.push_back(ph->u); pt_v.push_back(ph->v); pt_id.push_back(ph->idepth); pt_idz.push_back(ph->idepth_zero);
+          for (int k = 0; k < 8; k++) { pt_col.push_back(ph->color[k]); pt_wgt.push_back(ph->weights[k]); }
+          pt_prior.push_back(ph->hasDepthPrior ? 1 : 0); pt_mrb.push_back(ph->maxRelBaseline); pt_ngood.push_back(ph->numGoodResiduals);
+          for (auto* r : p->residualsAll) {
+            new_residuals.push_back(r);
+            want_res.push_back(-(int)pr_point.size() - 1);   // (+ the stage-6 count, added below)
+            pr_point.push_back(q); pr_target.push_back(frame_of(r->target));
+            pr_state.push_back((uint8_t)r->data->state_state); pr_new.push_back(r->data->isNew ? 1 : 0);
+          }
+        }
+      }
+    {  // stage-7 residual ids follow stage 6's
+      size_t i = 0;
+      for (size_t p = 0; p < new_points.size(); p++) {
+        const size_t cnt = new_points[p]->residualsAll.size();
+        if (want_point[p] < 0) for (size_t k = 0; k < cnt; k++) want_res[i + k] -= (int)ar_point.size();
+        i += cnt;
+      }
+    }
+    sdso_ba_window_edit_t E;
+    std::memset(&E, 0, sizeof(E));
+    E.n_drop_res = (int)pending_drop_res_.size(); E.drop_res = pending_drop_res_.data();
+    E.n_remove_points = (int)pending_rm_points_.size(); E.remove_points = pending_rm_points_.data();
+    E.drop_point = pending_drop_flags_.empty() ? nullptr : pending_drop_flags_.data();
+    E.n_remove_frames = (int)pending_rm_frames_.size(); E.remove_frames = pending_rm_frames_.data();
+    E.n_add_frames = n_add_frames;
+    E.evalPT = evalPT.data(); E.state = state.data(); E.state_zero = state_zero.data();
+    E.ab_exposure = exposure.data(); E.frameEnergyTH = energyTH.data(); E.frameID = frameID.data(); E.frame_slot = slots.data();
+    E.n_add_res = (int)ar_point.size(); E.add_res_point = ar_point.data(); E.add_res_target = ar_target.data();
+    E.add_res_state = ar_state.data(); E.add_res_isNew = ar_new.data();
+    E.n_add_points = (int)pt_host.size(); E.pt_host = pt_host.data();
+    E.pt_u = pt_u.data(); E.pt_v = pt_v.data(); E.pt_idepth = pt_id.data(); E.pt_idepth_zero = pt_idz.data();
+    E.pt_color = pt_col.data(); E.pt_weights = pt_wgt.data();
+    E.pt_hasDepthPrior = pt_prior.data(); E.pt_maxRelBaseline = pt_mrb.data(); E.pt_numGoodResiduals = pt_ngood.data();
+    E.n_pt_res = (int)pr_point.size(); E.pt_res_point = pr_point.data(); E.pt_res_target = pr_target.data();
+    E.pt_res_state = pr_state.data(); E.pt_res_isNew = pr_new.data();
+    dev_.check(sdso_ba_window_update(dev_.ctx(), win_, &E), "sdso_ba_window_update");
+    // ---- the device's order is the EnergyFunctional's, or the two have drifted apart
+    const int nf2 = (int)ef->frames.size();
+    std::vector<int> fs(nf2), ps(new_points.size()), rs(new_residuals.size());
+    dev_.check(sdso_ba_window_get_order(dev_.ctx(), win_, fs.data(), ps.data(), rs.data()), "sdso_ba_window_get_order");
+    for (int k = 0; k < nf2; k++) {
+      const int o = frame_old.at(ef->frames[k]);
+      if (fs[k] != (o < nf_old ? o : -1 - (o - nf_old))) throw Error("update: the device window's frames differ from the EnergyFunctional's");
+    }
+    if (ps != want_point || rs != want_res) throw Error("update: the device window's order differs from the EnergyFunctional's (a removal the shim was not told about?)");
+    points_.swap(new_points); residuals_.swap(new_residuals);
+    res_index_.clear(); point_index_.clear();
+    for (size_t i = 0; i < residuals_.size(); i++) res_index_[residuals_[i]->data] = (int)i;
+    for (size_t i = 0; i < points_.size(); i++) point_index_[points_[i]] = (int)i;
+    frames_.assign(ef->frames.begin(), ef->frames.end());
+    nf_ = nf2; ef_ = ef;
+    HM_.assign((size_t)(8 * nf2 + 4) * (8 * nf2 + 4), 0.0); bM_.assign(8 * nf2 + 4, 0.0);   // (host copies of the prior: sized per window, filled by marginalizePointsF)
+    clearPending_();
+    lin_valid_ = app_valid_ = acc_valid_ = marg_valid_ = false;
+  }
+
  private:
+  // optimize() / willRemovePoint / willDropPoints / marginalizeFrame left null slots in points_ / residuals_: the members that walk those
+  // lists need update() (or upload()) first
+  void requireNoPendingEdit_(const char* who) const {
+    if (!pending_drop_res_.empty() || !pending_rm_points_.empty() || !pending_drop_flags_.empty() || !pending_rm_frames_.empty())
+      throw Error(std::string(who) + ": the EnergyFunctional changed since the device window was brought in line: call update() (or upload()) first");
+  }
+  void clearPending_() { pending_drop_res_.clear(); pending_rm_points_.clear(); pending_drop_flags_.clear(); pending_rm_frames_.clear(); }
+  void forgetPoint_(int i) {                               // the point and its residuals leave the index maps before the reference deletes them
+    for (auto* r : points_[i]->residualsAll) {
+      auto it = res_index_.find(r->data);
+      if (it != res_index_.end()) { residuals_[it->second] = nullptr; res_index_.erase(it); }
+    }
+    point_index_.erase(points_[i]); points_[i] = nullptr;
+  }
+  std::vector<int> pending_drop_res_, pending_rm_points_, pending_rm_frames_;
+  std::vector<uint8_t> pending_drop_flags_;
+  std::vector<const void*> frames_;                        // EFFrame* of the uploaded window, in order
   template <class MatXX, class VecX> void stitched_(int which, MatXX& H, VecX& b) {
     const int n = 8 * nf_ + 4;
     std::vector<double> Hs((size_t)n * n), bs(n);

@@ -71,6 +71,22 @@ class BAWindow(C.Structure):
                 ("maxRelBaseline", c_float_p), ("numGoodResiduals", c_int_p), ("res_isNew", c_u8_p)]
 
 
+class BAWindowEdit(C.Structure):
+    """sdso_ba_window_edit_t: the seven stages of sdso_ba_window_update (include/sdso_abi.h)."""
+    _fields_ = [("n_drop_res", C.c_int), ("drop_res", c_int_p),
+                ("n_remove_points", C.c_int), ("remove_points", c_int_p),
+                ("drop_point", c_u8_p),
+                ("n_remove_frames", C.c_int), ("remove_frames", c_int_p),
+                ("n_add_frames", C.c_int), ("evalPT", c_double_p), ("state", c_double_p), ("state_zero", c_double_p),
+                ("ab_exposure", c_float_p), ("frameEnergyTH", c_float_p), ("frameID", c_int_p), ("frame_slot", c_int_p),
+                ("n_add_res", C.c_int), ("add_res_point", c_int_p), ("add_res_target", c_int_p), ("add_res_state", c_u8_p), ("add_res_isNew", c_u8_p),
+                ("n_add_points", C.c_int), ("pt_host", c_int_p),
+                ("pt_u", c_float_p), ("pt_v", c_float_p), ("pt_idepth", c_float_p), ("pt_idepth_zero", c_float_p),
+                ("pt_color", c_float_p), ("pt_weights", c_float_p),
+                ("pt_hasDepthPrior", c_u8_p), ("pt_maxRelBaseline", c_float_p), ("pt_numGoodResiduals", c_int_p),
+                ("n_pt_res", C.c_int), ("pt_res_point", c_int_p), ("pt_res_target", c_int_p), ("pt_res_state", c_u8_p), ("pt_res_isNew", c_u8_p)]
+
+
 # sdso_comm_init_host's transport callbacks (include/sdso_abi.h)
 HOST_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_size_t)
 HOST_ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t)
@@ -251,6 +267,60 @@ def make_ba_window(win, frame_slots=None, dI_list=None):
     return W, keep
 
 
+def make_window_edit(drop_res=None, remove_points=None, drop_point=None, remove_frames=None, add_frames=None, add_res=None, add_points=None):
+    """Fill a BAWindowEdit.  drop_res / remove_points / remove_frames: index sequences (their order is the order of the drops);
+    drop_point: np flags; add_frames: dict(evalPT (k,12), state (k,10), state_zero (k,10), ab_exposure, frameEnergyTH, frameID,
+    frame_slot); add_res: dict(point, target, state[, isNew]); add_points: dict(host, u, v, idepth, idepth_zero, color (k,8),
+    weights (k,8), hasDepthPrior[, maxRelBaseline, numGoodResiduals], res_point, res_target, res_state[, res_isNew]).  Every index is in
+    the numbering of the window before the call.  Returns (struct, keep-alive list)."""
+    E = BAWindowEdit()
+    keep = []
+    conv = {np.float32: fp, np.float64: dp, np.int32: ip, np.uint8: bp}
+
+    def put(field, a, dt):
+        a = np.ascontiguousarray(a, dtype=dt)
+        keep.append(a)
+        setattr(E, field, conv[dt](a))
+        return a
+
+    if drop_res is not None:
+        E.n_drop_res = len(put("drop_res", drop_res, np.int32))
+    if remove_points is not None:
+        E.n_remove_points = len(put("remove_points", remove_points, np.int32))
+    if drop_point is not None:
+        put("drop_point", drop_point, np.uint8)
+    if remove_frames is not None:
+        E.n_remove_frames = len(put("remove_frames", remove_frames, np.int32))
+    if add_frames is not None:
+        E.n_add_frames = len(put("frameID", add_frames["frameID"], np.int32))
+        for k in ("evalPT", "state", "state_zero"):
+            put(k, add_frames[k], np.float64)
+        for k in ("ab_exposure", "frameEnergyTH"):
+            put(k, add_frames[k], np.float32)
+        put("frame_slot", add_frames["frame_slot"], np.int32)
+    if add_res is not None:
+        E.n_add_res = len(put("add_res_point", add_res["point"], np.int32))
+        put("add_res_target", add_res["target"], np.int32)
+        put("add_res_state", add_res["state"], np.uint8)
+        if add_res.get("isNew") is not None:
+            put("add_res_isNew", add_res["isNew"], np.uint8)
+    if add_points is not None:
+        E.n_add_points = len(put("pt_host", add_points["host"], np.int32))
+        for k in ("u", "v", "idepth", "idepth_zero", "color", "weights"):
+            put("pt_" + k, add_points[k], np.float32)
+        put("pt_hasDepthPrior", add_points["hasDepthPrior"], np.uint8)
+        if add_points.get("maxRelBaseline") is not None:
+            put("pt_maxRelBaseline", add_points["maxRelBaseline"], np.float32)
+        if add_points.get("numGoodResiduals") is not None:
+            put("pt_numGoodResiduals", add_points["numGoodResiduals"], np.int32)
+        E.n_pt_res = len(put("pt_res_point", add_points["res_point"], np.int32))
+        put("pt_res_target", add_points["res_target"], np.int32)
+        put("pt_res_state", add_points["res_state"], np.uint8)
+        if add_points.get("res_isNew") is not None:
+            put("pt_res_isNew", add_points["res_isNew"], np.uint8)
+    return E, keep
+
+
 def make_trace_points(n, u, v, color, weights, gradH, energyTH, idepth_min_stereo=None, idepth_max_stereo=None):
     """Fresh immature points (idepth_min=0, idepth_max=NaN; ImmaturePoint.cpp:34)."""
     d = dict(
@@ -354,6 +424,9 @@ def load():
     L.sdso_ba_calc_energies.argtypes = [vp, C.c_int, c_double_p, c_double_p]
     L.sdso_ba_marginalize_frame_dev.argtypes = [vp, C.c_int, C.c_int, c_double_p, c_double_p]
     L.sdso_ba_adopt_prior.argtypes = [vp, C.c_int, C.c_int]
+    L.sdso_ba_window_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, C.POINTER(BAWindowEdit), c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p]
+    L.sdso_ba_window_update.argtypes = [vp, C.c_int, C.POINTER(BAWindowEdit)]
+    L.sdso_ba_window_get_order.argtypes = [vp, C.c_int, c_int_p, c_int_p, c_int_p]
     L.sdso_ba_get_deltas.argtypes = [vp, C.c_int, c_float_p, c_double_p, c_double_p, c_float_p]
     L.sdso_comm_unique_id.argtypes = [vp]
     L.sdso_comm_init.argtypes = [vp, C.c_int, C.c_int, vp]
@@ -406,6 +479,7 @@ EXPORTED_SYMBOLS = [
     "sdso_immature_init_batch", "sdso_trace_stereo_batch", "sdso_trace_stereo_prepare", "sdso_trace_stereo_enqueue",
     "sdso_trace_stereo_fetch", "sdso_stereo_match_batch", "sdso_activate_points_batch", "sdso_ba_marginalize_frame", "sdso_ba_batch_linearize", "sdso_ba_batch_schur", "sdso_pixel_select", "sdso_pixel_selector_pattern", "sdso_trace_on_batch", "sdso_track_make_ref", "sdso_track_newest_coarse_batch", "sdso_track_get_ref",
     "sdso_ba_get_post_state", "sdso_ba_batch_keep_system", "sdso_ba_get_stitched", "sdso_ba_batch_exchange_mode", "sdso_ba_resubstitute", "sdso_ba_get_counts", "sdso_ba_calc_energies", "sdso_ba_get_deltas", "sdso_ba_marginalize_frame_dev", "sdso_ba_adopt_prior",
+    "sdso_ba_window_plan", "sdso_ba_window_update", "sdso_ba_window_get_order",
     "sdso_ba_batch_optimize", "sdso_ba_batch_optimize_begin", "sdso_ba_batch_step", "sdso_ba_batch_solve_step", "sdso_ba_batch_optimize_end", "sdso_ba_get_state",
     "sdso_comm_unique_id", "sdso_comm_init", "sdso_comm_init_host", "sdso_comm_attach", "sdso_comm_info", "sdso_comm_destroy", "sdso_ba_allreduce", "sdso_ba_allreduce_window",
     "sdso_g2o_track_add_edges", "sdso_g2o_track_linearize", "sdso_g2o_track_newest_coarse", "sdso_g2o_lba_eval", "sdso_trace_set_gn_mode",
