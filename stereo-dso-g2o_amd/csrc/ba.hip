@@ -289,6 +289,8 @@ static int upload_window_impl(sdso_ctx* ctx, int win, const sdso_ba_window_t* Wi
   SDSO_REQUIRE(ctx, Win, "null window");
   const int nf = Win->nf, np = Win->np, nr = Win->nr;
   SDSO_REQUIRE(ctx, nf >= 1 && nf <= 8 && np >= 0 && nr >= 0, "window sizes out of range (nf <= 8: setting_maxFrames is 7, settings.cpp:65)");
+  SDSO_REQUIRE(ctx, (size_t)((Win->w + 3) / 4) * (size_t)((Win->h + 1) / 2) * 128 < (size_t)sdso::TAP_RANGE,
+               "image size out of range (k_ba_lin_fused reads a tiled level-0 image through a 2 GiB buffer descriptor with 32-bit offsets)");
   SDSO_REQUIRE(ctx, Win->evalPT && Win->state && Win->state_zero && Win->ab_exposure && Win->frameEnergyTH && Win->frameID && Win->frame_slot, "null frame arrays");
   SDSO_REQUIRE(ctx, np == 0 || (Win->u && Win->v && Win->idepth && Win->idepth_zero && Win->color && Win->weights && Win->host && Win->hasDepthPrior), "null point arrays");
   SDSO_REQUIRE(ctx, nr == 0 || (Win->res_point && Win->res_target && Win->res_state), "null residual arrays");

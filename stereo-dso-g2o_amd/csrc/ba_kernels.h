@@ -22,6 +22,27 @@ constexpr int SOLVER_SVD = 1, SOLVER_ORTHOGONALIZE_SYSTEM = 2, SOLVER_ORTHOGONAL
               SOLVER_REMOVE_POSEPRIOR = 32, SOLVER_USE_GN = 64, SOLVER_FIX_LAMBDA = 128, SOLVER_ORTHOGONALIZE_X = 256,
               SOLVER_MOMENTUM = 512, SOLVER_STEPMOMENTUM = 1024, SOLVER_ORTHOGONALIZE_X_LATER = 2048;
 
+// A pointer read out of a BaDev is a generic pointer to the compiler, whatever the kernel does with the descriptor first: it is accessed
+// with flat_load / flat_store, which count in lgkmcnt as well as in vmcnt, so a wait in front of an LDS read also waits for the memory
+// access issued before it and no wait on memory can be a counted one.  Every array of a BaDev is hipMalloc'ed; these helpers say so.
+//   gld / gst / gst_nt  one access through address space 1 (global_load_* / global_store_*)
+//   uld                 a wave-uniform, read-only value through address space 4 (s_load_*: the scalar cache, the result in SGPRs).  Only
+//                       for data that no kernel writes while this one runs — the scalar cache is not coherent with vector stores
+// T must be a scalar or an ext_vector type (a class such as float4 cannot be copied out of a non-generic address space).
+template <class T> using gptr_t = __attribute__((address_space(1))) T*;
+template <class T> using uptr_t = const __attribute__((address_space(4))) T*;
+template <class T> __device__ __forceinline__ gptr_t<T> as_global(T* p) { return (gptr_t<T>)p; }
+template <class T> __device__ __forceinline__ T gld(const T* p) { return *(gptr_t<const T>)p; }
+template <class T> __device__ __forceinline__ void gst(T* p, T v) { *(gptr_t<T>)p = v; }
+template <class T> __device__ __forceinline__ void gst_nt(T* p, T v) { __builtin_nontemporal_store(v, (gptr_t<T>)p); }
+template <class T> __device__ __forceinline__ T uld(const T* p) { return *(uptr_t<T>)p; }
+// every vector-memory access of the wave has completed (s_waitcnt vmcnt(0), nothing else): ONE wait behind a batch of independent loads
+// instead of a counted one in front of each result's first use.  The scheduling barrier keeps the first uses behind it.
+__device__ __forceinline__ void vm_wait_all() { __builtin_amdgcn_s_waitcnt(0x0f70); __builtin_amdgcn_sched_barrier(0); }
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
 constexpr int BA_BLOCK = 256;
 constexpr int BA_CHUNK = 256;      // residuals per accumulate workgroup
 constexpr int BA_SC_PTS = 32;      // points per SC wave item (<= 64)

@@ -237,6 +237,12 @@ __device__ __forceinline__ double linearize_one(const BaDev& B, int i, int h, in
 // of every pattern pixel in rows of 65 floats ([pixel*3 + channel][residual]).
 constexpr int CG_COORD_FLOATS = 64 * 8 * 2, CG_ROW = 64, CG_HIT_FLOATS = 8 * 3 * CG_ROW, CG_WAVE_FLOATS = CG_COORD_FLOATS + CG_HIT_FLOATS;
 constexpr int CG_BATCH = 8;                                   // loads in flight per lane
+// The target image as a raw buffer: 32-bit byte offsets from a base in SGPRs, and a range check that turns a load which must not happen into
+// zeros.  The range is 2 GiB whatever the image's size (every offset a live lane forms lies inside the image), TAP_OFF_DEAD lies beyond it.
+typedef __amdgpu_buffer_rsrc_t tap_rsrc_t;
+typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
+constexpr unsigned TAP_RANGE = 0x80000000u, TAP_OFF_DEAD = 0xfffffff0u;   // (the window upload, ba.hip, refuses an image of TAP_RANGE bytes or more)
+constexpr int TAP_RSRC_FLAGS = 0x00020000;   // word 3 of a gfx9 (gfx950) raw buffer descriptor: DATA_FORMAT = 32; other families lay this word out differently
 __device__ __forceinline__ void cg_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -251,29 +257,30 @@ __device__ __forceinline__ float quad_bcast(float v) {
 // pattern pixel, corner).  The four corner lanes of a pixel exchange their samples inside the quad and evaluate
 // getInterpolatedElement33 (same expression, same order: bit-identical to interp33); the corner-0 lane parks the result for the
 // residual's own lane.  A residual's image lines are touched by exactly one instruction, so they are fetched once.
-__device__ __forceinline__ void coop_gather_hits(const float4* __restrict__ img, int T, bool dead, const float* Ku, const float* Kv, float* wstage) {
+__device__ __forceinline__ void coop_gather_hits(tap_rsrc_t img /* wave-uniform: SGPRs */, int T, bool dead, const float* Ku, const float* Kv, float* wstage) {
   const int lane = threadIdx.x & 63;
   float2* coords = (float2*)wstage;
   float* hits = wstage + CG_COORD_FLOATS;
 #pragma unroll
   for (int k = 0; k < 8; k++) coords[lane * 8 + k] = dead ? make_float2(-1.f, -1.f) : make_float2(Ku[k], Kv[k]);
   cg_wave_sync();
-  struct __attribute__((packed, aligned(4))) px3 { float x, y, z; };
   const int sub = lane >> 5, px = (lane >> 2) & 7, c = lane & 3;
 #pragma unroll
   for (int r0 = 0; r0 < 32; r0 += CG_BATCH) {
-    px3 q[CG_BATCH];
+    // a batch: its eight coordinates out of LDS, its eight 12-byte tap loads back to back, ONE wait for the eight
+    float qx[CG_BATCH], qy[CG_BATCH], qz[CG_BATCH];
     float2 cx[CG_BATCH];
 #pragma unroll
+    for (int r = 0; r < CG_BATCH; r++) cx[r] = coords[((r0 + r) * 2 + sub) * 8 + px];
+#pragma unroll
     for (int r = 0; r < CG_BATCH; r++) {
-      const int unit = (r0 + r) * 2 + sub;
-      cx[r] = coords[unit * 8 + px];
-      q[r].x = 0; q[r].y = 0; q[r].z = 0;
-      if (cx[r].x >= 0) {
-        const int x = (int)cx[r].x + (c & 1), y = (int)cx[r].y + (c >> 1);
-        q[r] = *(const px3*)(img + tiled_index(x, y, T));
-      }
+      const int x = (int)cx[r].x + (c & 1), y = (int)cx[r].y + (c >> 1);
+      // a dead residual's lanes ask for an offset beyond the descriptor's range: the hardware returns zeros and touches no memory (no branch
+      // around the load, so no wait inside one)
+      const u32x3 q = __builtin_amdgcn_raw_buffer_load_b96(img, cx[r].x >= 0 ? (unsigned)tiled_index(x, y, T) * 16u : TAP_OFF_DEAD, 0, 0);
+      qx[r] = __uint_as_float(q.x); qy[r] = __uint_as_float(q.y); qz[r] = __uint_as_float(q.z);
     }
+    vm_wait_all();
 #pragma unroll
     for (int r = 0; r < CG_BATCH; r++) {
       const int unit = (r0 + r) * 2 + sub;
@@ -288,7 +295,7 @@ __device__ __forceinline__ void coop_gather_hits(const float4* __restrict__ img,
       const float w11 = dxdy, w01 = dy - dxdy, w10 = dx - dxdy, w00 = 1 - dx - dy + dxdy;
       const float wa = (c & 1) ? w11 : w01, wb = (c & 1) ? w10 : w00;
       const float wc = (c & 2) ? wa : wb;
-      const float tx = wc * q[r].x, ty = wc * q[r].y, tz = wc * q[r].z;
+      const float tx = wc * qx[r], ty = wc * qy[r], tz = wc * qz[r];
       const float hx = ((quad_bcast<3>(tx) + quad_bcast<2>(tx)) + quad_bcast<1>(tx)) + tx;
       const float hy = ((quad_bcast<3>(ty) + quad_bcast<2>(ty)) + quad_bcast<1>(ty)) + ty;
       const float hz = ((quad_bcast<3>(tz) + quad_bcast<2>(tz)) + quad_bcast<1>(tz)) + tz;
@@ -301,12 +308,24 @@ __device__ __forceinline__ void coop_gather_hits(const float4* __restrict__ img,
   }
   cg_wave_sync();
 }
+// The fused kernel hands over what it has already fetched (k_ba_lin_fused: the pair's tables in SGPRs, the residual's scalars and the point's
+// 80 bytes in one round trip each), so nothing is loaded here but the taps, and nothing this lane stores is read again: `fresh` = live and
+// not sticky-OOB (state != 1); `energy_old` = r_energy[i].  Every lane state of linearize_one ends in ONE set of stores behind the
+// Jacobian: r_newEnergyWO (-1 unless the residual was linearised to the end), r_newState, and r_newEnergy where it was.  Returns the
+// residual's term of the energy sum (0 for a lane without a residual).
+#define SETQG(g, a, b, c, d)                                                             \
+  do {                                                                                   \
+    const f32x4 _q = {a, b, c, d};                                                       \
+    if (STORE) gst_nt((f32x4*)(J + j_off(S, i, g)), _q); /* streamed, not re-read this iteration */ \
+    if (KEEP == 1 || (KEEP == 2 && ((g) < 6 || (g) > 15))) { jl[4 * (g)] = _q.x; jl[4 * (g) + 1] = _q.y; jl[4 * (g) + 2] = _q.z; jl[4 * (g) + 3] = _q.w; } \
+  } while (0)
 template <bool STORE, int KEEP>
-__device__ __forceinline__ double linearize_coop(const BaDev& B, int i, bool live, int h, int t, float* jl, int& ns_out, float* rs, float* wstage) {
+__device__ __forceinline__ float linearize_coop(const BaDev& B, int i, bool live, bool fresh, const float* pre /* t_precalc of the pair */,
+                                                tap_rsrc_t img, float th /* max of the two frames' thresholds */, f32x4 g, f32x4 c0, f32x4 c1,
+                                                f32x4 w0, f32x4 w1, uint8_t jsel, float energy_old, float* jl, int& ns_out, float* rs, float* wstage) {
   ns_out = 1;
-  bool dead = !live;
-  double ret = 0;
-  float Kus[8], Kvs[8], color[8], weights[8], jab1[8];
+  bool dead = true;
+  float Kus[8], Kvs[8], jab1[8];
   bool oob = false;
   float g_u = 0, g_v = 0, g_dr = 0, g_nid = 0, g_k0 = 0, g_k1 = 0;
   float JIdxJIdx_00 = 0, JIdxJIdx_11 = 0, JIdxJIdx_10 = 0;
@@ -314,21 +333,15 @@ __device__ __forceinline__ double linearize_coop(const BaDev& B, int i, bool liv
   float JabJab_00 = 0, JabJab_01 = 0, JabJab_11 = 0;
   float wJI2_sum = 0, energyLeft = 0;
 #pragma unroll
-  for (int k = 0; k < 8; k++) { Kus[k] = 0; Kvs[k] = 0; color[k] = 0; weights[k] = 0; jab1[k] = 0; }
-  const float* __restrict__ pre = B.t_precalc + (size_t)(h * B.nf + t) * 27;
+  for (int k = 0; k < 8; k++) { Kus[k] = 0; Kvs[k] = 0; jab1[k] = 0; }
   const float affLL0 = pre[24], affLL1 = pre[25], b0 = pre[26];
-  const float4* __restrict__ dIl = B.t_img[t];
+  const float color[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+  const float weights[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
   const int S = B.nrp;
-  float* __restrict__ J = nullptr;
-  if (!dead) do {
-  B.r_newEnergyWO[i] = -1.f;
-  const uint8_t st = B.r_state[i];
-  if (st == 1) { B.r_newState[i] = 1; ret = (double)B.r_energy[i]; dead = true; break; }
-  const int pt = B.r_point[i];
+  float* const J = STORE ? ((jsel != 0) != (B.jfix != 0) ? B.J[0] : B.J[1]) : nullptr;   // jfix: EFResidual::J refreshed in place (ba_kernels.h)
+  if (fresh) do {
   const float* KRKi = pre; const float* Kt = pre + 9; const float* R0 = pre + 12; const float* t0 = pre + 21;
-  const float4 g = B.p_geo[pt];
   const float pu = g.x, pv = g.y, idepth_scaled = g.z, idepth_zero_scaled = g.w;
-  J = STORE ? ((B.r_jsel[i] != 0) != (B.jfix != 0) ? B.J[0] : B.J[1]) : nullptr;   // jfix: EFResidual::J refreshed in place (ba_kernels.h)
   const float fxl = B.fxl, fyl = B.fyl, cxl = B.cxl, cyl = B.cyl, fxli = B.fxli, fyli = B.fyli;
 
   // projectPoint (ResidualProjections.h:64-96) at the FEJ point
@@ -341,18 +354,14 @@ __device__ __forceinline__ double linearize_coop(const BaDev& B, int i, bool liv
   for (int r = 0; r < 3; r++) ptp[r] = ((R0[r * 3 + 0] * KliP[0] + R0[r * 3 + 1] * KliP[1]) + R0[r * 3 + 2] * KliP[2]) + t0[r] * idepth_zero_scaled;
   const float drescale = 1.0f / ptp[2];
   const float new_idepth = idepth_zero_scaled * drescale;
-  if (!(drescale > 0)) { B.r_newState[i] = 1; ret = (double)B.r_energy[i]; dead = true; break; }
+  if (!(drescale > 0)) break;
   const float u = ptp[0] * drescale;
   const float v = ptp[1] * drescale;
   const float Ku0 = u * fxl + cxl;
   const float Kv0 = v * fyl + cyl;
-  if (!(Ku0 > 1.1f && Kv0 > 1.1f && Ku0 < B.wM3 && Kv0 < B.hM3)) { B.r_newState[i] = 1; ret = (double)B.r_energy[i]; dead = true; break; }
+  if (!(Ku0 > 1.1f && Kv0 > 1.1f && Ku0 < B.wM3 && Kv0 < B.hM3)) break;
   g_u = u; g_v = v; g_dr = drescale; g_nid = new_idepth; g_k0 = KliP[0]; g_k1 = KliP[1];   // the geometric Jacobians are built after the taps (fewer live registers during the gathers)
 
-  const float4 c0 = *(const float4*)(B.p_color + (size_t)pt * 8), c1 = *(const float4*)(B.p_color + (size_t)pt * 8 + 4);
-  const float4 w0 = *(const float4*)(B.p_weights + (size_t)pt * 8), w1 = *(const float4*)(B.p_weights + (size_t)pt * 8 + 4);
-  color[0] = c0.x; color[1] = c0.y; color[2] = c0.z; color[3] = c0.w; color[4] = c1.x; color[5] = c1.y; color[6] = c1.z; color[7] = c1.w;
-  weights[0] = w0.x; weights[1] = w0.y; weights[2] = w0.z; weights[3] = w0.w; weights[4] = w1.x; weights[5] = w1.y; weights[6] = w1.z; weights[7] = w1.w;
   // Pass 1 (no memory traffic): project the 8 pattern pixels; the residual is OOB as soon as one leaves
   // the image (Residuals.cpp:215-225).  Doing this first removes the early exit from the sampling loop, so
   // the 32 bilinear taps below are independent loads the hardware can keep in flight together.
@@ -366,10 +375,10 @@ __device__ __forceinline__ double linearize_coop(const BaDev& B, int i, bool liv
     Kvs[idx] = q[1] / q[2];
     if (!(Kus[idx] > 1.1f && Kvs[idx] > 1.1f && Kus[idx] < B.wM3 && Kvs[idx] < B.hM3)) oob = true;
   }
-  if (oob) { B.r_newState[i] = 1; ret = (double)B.r_energy[i]; dead = true; break; }
+  if (oob) break;
+  dead = false;
   } while (0);
-  coop_gather_hits(dIl, B.tiledT, dead, Kus, Kvs, wstage);
-  {
+  coop_gather_hits(img, B.tiledT, dead, Kus, Kvs, wstage);
   if (!dead) {
   const float* hstage = wstage + CG_COORD_FLOATS + (threadIdx.x & 63);
 #pragma unroll
@@ -386,7 +395,7 @@ __device__ __forceinline__ double linearize_coop(const BaDev& B, int i, bool liv
     hw = hw * wgt;
     hit.y *= hw;
     hit.z *= hw;
-    SETQ(6 + idx, residual * hw, hit.y, hit.z, B.affA_fixed ? 0.f : drdA * hw);   // resF, JIdx[0], JIdx[1], JabF[0]
+    SETQG(6 + idx, residual * hw, hit.y, hit.z, B.affA_fixed ? 0.f : drdA * hw);   // resF, JIdx[0], JIdx[1], JabF[0]
     jab1[idx] = B.affB_fixed ? 0.f : hw;
     if (KEEP == 2) {
       const float ra = residual * hw;
@@ -405,11 +414,18 @@ __device__ __forceinline__ double linearize_coop(const BaDev& B, int i, bool liv
     JabJab_01 += drdA * hw * hw;
     JabJab_11 += hw * hw;
     wJI2_sum += hw * hw * (hit.y * hit.y + hit.z * hit.z);
+    // Every sum is complete, in a register, before the next pattern pixel starts.  Without these the compiler packs the eight pixels'
+    // terms into v_pk_* pairs ACROSS the loop, which keeps all eight pixels' products alive to its end: 147 VGPRs instead of 102 (three
+    // workgroups per CU instead of four; scratch in the variant without the stores).  The sums and their order are the same either way
+    // (profiles/lin_waits_ab.txt has both forms side by side).
+    asm volatile("" : "+v"(JIdxJIdx_00), "+v"(JIdxJIdx_11), "+v"(JIdxJIdx_10), "+v"(JabJIdx_00), "+v"(JabJIdx_01), "+v"(JabJIdx_10), "+v"(JabJIdx_11));
+    asm volatile("" : "+v"(JabJab_00), "+v"(JabJab_01), "+v"(JabJab_11), "+v"(wJI2_sum), "+v"(energyLeft));
+    if (KEEP == 2) asm volatile("" : "+v"(rs[0]), "+v"(rs[1]), "+v"(rs[2]), "+v"(rs[3]), "+v"(rs[4]));
   }
   }
-  }
-  if (dead) return ret;
-  if (oob) { B.r_newState[i] = 1; return (double)B.r_energy[i]; }
+  float ewo = -1.f, eret = live ? energy_old : 0.f;
+  const bool done = !dead && !oob;
+  if (done) {
   {  // Residuals.cpp:135-185
     const float* R0 = pre + 12; const float* t0 = pre + 21;
     const float u = g_u, v = g_v, drescale = g_dr, new_idepth = g_nid;
@@ -434,27 +450,32 @@ __device__ __forceinline__ double linearize_coop(const BaDev& B, int i, bool liv
     d_C_y[1] = (d_C_y[1] + v) * SCALE_F;
     d_C_y[2] *= SCALE_C;
     d_C_y[3] = (d_C_y[3] + 1) * SCALE_C;
-    SETQ(0, new_idepth * fxl, 0, -new_idepth * u * fxl, -u * v * fxl);                       // Jpdxi[0][0..3]
-    SETQ(1, (1 + u * u) * fxl, -v * fxl, 0, new_idepth * fyl);                                // Jpdxi[0][4..5], Jpdxi[1][0..1]
-    SETQ(2, -new_idepth * v * fyl, -(1 + v * v) * fyl, u * v * fyl, u * fyl);                 // Jpdxi[1][2..5]
-    SETQ(3, d_C_x[0], d_C_x[1], d_C_x[2], d_C_x[3]);
-    SETQ(4, d_C_y[0], d_C_y[1], d_C_y[2], d_C_y[3]);
-    SETQ(5, d_d_x, d_d_y, 0.f, 0.f);
+    SETQG(0, new_idepth * fxl, 0, -new_idepth * u * fxl, -u * v * fxl);                       // Jpdxi[0][0..3]
+    SETQG(1, (1 + u * u) * fxl, -v * fxl, 0, new_idepth * fyl);                                // Jpdxi[0][4..5], Jpdxi[1][0..1]
+    SETQG(2, -new_idepth * v * fyl, -(1 + v * v) * fyl, u * v * fyl, u * fyl);                 // Jpdxi[1][2..5]
+    SETQG(3, d_C_x[0], d_C_x[1], d_C_x[2], d_C_x[3]);
+    SETQG(4, d_C_y[0], d_C_y[1], d_C_y[2], d_C_y[3]);
+    SETQG(5, d_d_x, d_d_y, 0.f, 0.f);
   }
-  SETQ(14, jab1[0], jab1[1], jab1[2], jab1[3]);
-  SETQ(15, jab1[4], jab1[5], jab1[6], jab1[7]);
-  SETQ(16, JIdxJIdx_00, JIdxJIdx_10, JIdxJIdx_10, JIdxJIdx_11);
-  SETQ(17, JabJIdx_00, JabJIdx_01, JabJIdx_10, JabJIdx_11);
-  SETQ(18, JabJab_00, JabJab_01, JabJab_01, JabJab_11);
+  SETQG(14, jab1[0], jab1[1], jab1[2], jab1[3]);
+  SETQG(15, jab1[4], jab1[5], jab1[6], jab1[7]);
+  SETQG(16, JIdxJIdx_00, JIdxJIdx_10, JIdxJIdx_10, JIdxJIdx_11);
+  SETQG(17, JabJIdx_00, JabJIdx_01, JabJIdx_10, JabJIdx_11);
+  SETQG(18, JabJab_00, JabJab_01, JabJab_01, JabJab_11);
 
-  B.r_newEnergyWO[i] = energyLeft;
-  const float th = fmaxf(B.t_frameTH[h], B.t_frameTH[t]);
+  ewo = energyLeft;
   if (energyLeft > th || wJI2_sum < 2) { energyLeft = th; ns_out = 2; }
   else ns_out = 0;
-  B.r_newState[i] = (uint8_t)ns_out;
-  B.r_newEnergy[i] = energyLeft;
-  return (double)energyLeft;
+  eret = energyLeft;
+  }
+  if (live) {
+    gst(B.r_newEnergyWO + i, ewo);
+    gst(B.r_newState + i, (uint8_t)ns_out);
+    if (done) gst(B.r_newEnergy + i, eret);
+  }
+  return eret;
 }
+#undef SETQG
 #undef SETQ
 
 __global__ __launch_bounds__(BA_BLOCK) void k_ba_linearize(const BaDev* __restrict__ wins, int cond = 0) {
@@ -711,7 +732,7 @@ __device__ __forceinline__ void top_emit(const BaDev& B, const float* x, const f
     double s = R[off];
 #pragma unroll
     for (int w = 1; w < BA_BLOCK / 64; w++) s += R[off + (t < 91 ? w * 256 : w)];
-    B.top_part[(size_t)chunk * 92 + t] = s;
+    gst(B.top_part + (size_t)chunk * 92 + t, s);
   }
 }
 
@@ -807,20 +828,25 @@ __global__ __launch_bounds__(BA_BLOCK) void k_ba_accum_top(const BaDev* __restri
 // one workgroup per chunk of one (host,target) pair, J is written to HBM only when MATERIALIZE
 // (the reference API keeps RawResidualJacobian; the solver itself never reads it again).
 // Linearized residuals are untouched (their accumulation is the separate mode-1 pass).
-// Workgroups per CU: four without the Jacobian stores (124 VGPRs, 40 KB of LDS each); with them the kernel needs 152 VGPRs
-// (capping it at 128 spills 22-38 of them and loses more than the fourth wave per SIMD gains), so three.
+// Workgroups per CU: four, with and without the Jacobian stores (102 / 101 VGPRs, 40 KB of LDS each); the register count rests on the
+// per-pixel sums being completed pixel by pixel (linearize_coop), tests/test_lin_isa_cpu.py holds it.
 // The 32 taps of a residual come in through the cooperative quad gather (linearize_coop).  (Rounds 1-4 kept two more gathers for A/B — one
 // residual's taps on one lane, and LDS-DMA rounds; both lost or tied, profiles/README.md.)  One chunk per workgroup: a persistent workgroup
 // that requested the next chunk's inputs under the current one's work was 26-28 % slower (spills at three waves per SIMD,
 // profiles/r06_lin_pk_ab.txt).
+// The kernel asks for everything as early as its address is known and waits once per batch, so that a wave waits for few memory round
+// trips one after the other (tools/isa_waits.py prints the waits of a listing; tests/test_lin_isa_cpu.py
+// holds them): the wave-uniform tables through the scalar cache at entry; the residual's eight scalars in one round trip; the point's
+// 80 bytes in a second, ahead of the projection's early exits; four batches of eight tap loads, one wait each; nothing behind the
+// Jacobian stores — no value this lane stored is read back, and the record's address is known since the first round trip.  No access
+// is a flat_ one (ba_kernels.h: gld / gst / uld), so these waits count memory alone.  How the gain over the former kernel splits between
+// these waits and the fourth workgroup per CU has not been measured (profiles/lin_waits_ab.txt).
 // The workgroup barriers behind the linearisation exchange data through LDS only (the gather stage handed over to the reduction's panels, the
-// energy sum, the waves' tiles).  They are plain `__syncthreads()` (s_waitcnt vmcnt(0) lgkmcnt(0) + s_barrier), which also waits for the
-// wave's outstanding Jacobian-record stores; waiting for the LDS traffic alone made no difference (0.772-0.777 against 0.770-0.774 ms,
-// profiles/r06_lin_barriers_ab.txt: two other workgroups per CU run under a wave's wait).
+// energy sum, the waves' tiles); the first stands behind the record stores, which touch no LDS.
 template <bool MATERIALIZE>
-__global__ __launch_bounds__(BA_BLOCK, (MATERIALIZE ? 3 : 4)) void k_ba_lin_fused(const BaDev* __restrict__ wins) {
-  // by-value copy first: every pointer of the descriptor is read before the kernel's first store, so the
-  // compiler can prove them global (global_load / s_load instead of flat_load) and keep them in SGPRs
+__global__ __launch_bounds__(BA_BLOCK, 4) void k_ba_lin_fused(const BaDev* __restrict__ wins) {
+  // by-value copy: the descriptor's fields come in through s_load and stay in SGPRs.  Its pointers are still generic ones to the compiler;
+  // every access below says "global" (gld / gst) or "uniform" (uld) itself, ba_kernels.h
   const BaDev B = wins[blockIdx.y];
   if (ba_finished_lin(B)) return;
   if ((int)blockIdx.x >= B.nchunks) return;
@@ -829,8 +855,19 @@ __global__ __launch_bounds__(BA_BLOCK, (MATERIALIZE ? 3 : 4)) void k_ba_lin_fuse
   __shared__ float red[RED_FLOATS];    // the gather stage of the linearisation, then the MFMA panels of the reduction
   double* const lds = (double*)red;    // (the energy reduction runs between the two uses; 40 KB in all = four workgroups per CU)
   const int chunk = blockIdx.x;
-  const int4 ch = B.chunks[blockIdx.x];
-  const int pair = __builtin_amdgcn_readfirstlane(ch.x);   // one (host,target) per workgroup: precalc, image, thresholds are wave-uniform
+  // One (host,target) pair per workgroup: the chunk, the pair's 27 precalc floats, the target's image pointer and the two frames' thresholds
+  // are wave-uniform and written by earlier kernels only — requested once, here, through the scalar cache
+  const i32x4 ch = uld((const i32x4*)(B.chunks + blockIdx.x));
+  const int pair = ch.x;
+  const int h = pair % B.nf, t = pair / B.nf;
+  float pre[27];
+  {
+    const float* prep = B.t_precalc + (size_t)(h * B.nf + t) * 27;
+#pragma unroll
+    for (int k = 0; k < 27; k++) pre[k] = uld(prep + k);
+  }
+  const tap_rsrc_t img = __builtin_amdgcn_make_buffer_rsrc((void*)uld((const unsigned long long*)B.t_img + t), 0, TAP_RANGE, TAP_RSRC_FLAGS);
+  const float th = fmaxf(uld(B.t_frameTH + h), uld(B.t_frameTH + t));
   const int i = ch.y + threadIdx.x;
   float x[10], y[10], a = 0, b = 0, c = 0;
   float TR00 = 0, TR10 = 0, TR01 = 0, TR11 = 0, TR02 = 0, TR12 = 0;
@@ -838,24 +875,41 @@ __global__ __launch_bounds__(BA_BLOCK, (MATERIALIZE ? 3 : 4)) void k_ba_lin_fuse
 #pragma unroll
   for (int k = 0; k < 10; k++) { x[k] = 0; y[k] = 0; }
   bool on = false;
-  double e = 0;
-  const bool live = (int)threadIdx.x < ch.z && !B.r_lin[i];
+  // first round trip: everything the kernel reads of the residual itself
+  uint8_t lin, st, jsel, act_old;
+  int pt, orig;
+  float energy_old, newEnergy_old;
+  {
+    const int il = (int)threadIdx.x < ch.z ? i : ch.y;   // lanes past the chunk's end read its first residual's (a chunk is never empty): no branch, no extra line
+    lin = gld(B.r_lin + il); st = gld(B.r_state + il); pt = gld(B.r_point + il); jsel = gld(B.r_jsel + il); orig = gld(B.r_orig + il);
+    energy_old = gld(B.r_energy + il); newEnergy_old = gld(B.r_newEnergy + il); act_old = gld(B.r_act + il);
+  }
+  vm_wait_all();
+  const bool live = (int)threadIdx.x < ch.z && !lin;
+  if (!live) st = 1;
+  // second round trip: the point's 80 bytes, ahead of the projection and its early exits
+  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 pg = z4, c0 = z4, c1 = z4, w0 = z4, w1 = z4;
+  if (st != 1) {
+    pg = gld((const f32x4*)B.p_geo + pt);
+    c0 = gld((const f32x4*)(B.p_color + (size_t)pt * 8)); c1 = gld((const f32x4*)(B.p_color + (size_t)pt * 8 + 4));
+    w0 = gld((const f32x4*)(B.p_weights + (size_t)pt * 8)); w1 = gld((const f32x4*)(B.p_weights + (size_t)pt * 8 + 4));
+  }
   float jl[76];
   float rs5[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
   int ns = 1;
-  uint8_t st = 1;
-  if (live) st = B.r_state[i];
-  e = linearize_coop<MATERIALIZE, 2>(B, i, live, pair % B.nf, pair / B.nf, jl, ns, rs5, red + (threadIdx.x >> 6) * CG_WAVE_FLOATS);
-  __syncthreads();   // the reduction below reuses the stage of all waves
+  const float ef = linearize_coop<MATERIALIZE, 2>(B, i, live, st != 1, pre, img, th, pg, c0, c1, w0, w1, jsel, energy_old, jl, ns, rs5,
+                                                  red + (threadIdx.x >> 6) * CG_WAVE_FLOATS);
+  double e = (double)ef;
   if (live) {
-    float* rec = B.r_rec + (size_t)B.r_orig[i] * 16;
+    float* rec = B.r_rec + (size_t)orig * 16;
     // the 64-byte record of this residual (BaDev::r_rec): written once, whole, at the end (four 16-byte stores of one half line)
     float o8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, rbd = 0.f, rhdd = 0.f, rhcd[4] = {0.f, 0.f, 0.f, 0.f};
     uint8_t act = 0;
     if (st != 1) {  // applyRes(true): OOB is sticky
       if (ns == 0) {
         act = 1;
-        if (MATERIALIZE && !B.jfix) B.r_jsel[i] ^= 1;
+        if (MATERIALIZE && !B.jfix) gst(B.r_jsel + i, (uint8_t)(jsel ^ 1));
         const float jdd0 = JV(J_DD + 0), jdd1 = JV(J_DD + 1);
         const float v0 = JV(J_IDX2 + 0) * jdd0 + JV(J_IDX2 + 1) * jdd1;
         const float v1 = JV(J_IDX2 + 2) * jdd0 + JV(J_IDX2 + 3) * jdd1;
@@ -864,12 +918,12 @@ __global__ __launch_bounds__(BA_BLOCK, (MATERIALIZE ? 3 : 4)) void k_ba_lin_fuse
         o8[6] = JV(J_ABIDX + 0) * jdd0 + JV(J_ABIDX + 1) * jdd1;
         o8[7] = JV(J_ABIDX + 2) * jdd0 + JV(J_ABIDX + 3) * jdd1;
       }
-      B.r_act[i] = act;
-      B.r_state[i] = (uint8_t)ns;
-      B.r_energy[i] = B.r_newEnergy[i];
+      gst(B.r_act + i, act);
+      gst(B.r_state + i, (uint8_t)ns);
+      gst(B.r_energy + i, ns != 1 ? ef : newEnergy_old);   // r_newEnergy[i]: this launch's where the linearisation ran to its end, else the one it left
       on = act != 0;
     } else {
-      on = B.r_act[i] != 0;   // (an OOB residual is never active)
+      on = act_old != 0;   // (an OOB residual is never active)
     }
     if (on) {   // AccumulatedTopHessianSSE::addPoint<0>, resApprox = resF
       const float JI_r0 = rs5[0], JI_r1 = rs5[1], Jab_r0 = rs5[2], Jab_r1 = rs5[3], rr = rs5[4];
@@ -890,14 +944,15 @@ __global__ __launch_bounds__(BA_BLOCK, (MATERIALIZE ? 3 : 4)) void k_ba_lin_fuse
       for (int k = 0; k < 4; k++) rhcd[k] = x[k] * q0 + y[k] * q1;
     }
     if (st != 1) {   // (a sticky-OOB residual keeps the records its last applyRes wrote: flags 0)
-      *(float4*)(rec) = make_float4(o8[0], o8[1], o8[2], o8[3]);
-      *(float4*)(rec + 4) = make_float4(o8[4], o8[5], o8[6], o8[7]);
-      *(float4*)(rec + 8) = make_float4(rbd, rhdd, rhcd[0], rhcd[1]);
-      *(float4*)(rec + 12) = make_float4(rhcd[2], rhcd[3], (float)act, 0.f);
+      gst((f32x4*)rec, (f32x4){o8[0], o8[1], o8[2], o8[3]});
+      gst((f32x4*)(rec + 4), (f32x4){o8[4], o8[5], o8[6], o8[7]});
+      gst((f32x4*)(rec + 8), (f32x4){rbd, rhdd, rhcd[0], rhcd[1]});
+      gst((f32x4*)(rec + 12), (f32x4){rhcd[2], rhcd[3], (float)act, 0.f});
     }
   }
+  __syncthreads();   // the reduction below reuses the stage of all waves (behind the record stores: they touch no LDS and need not wait here)
   e = block_sum_d(e, lds);
-  if (threadIdx.x == 0) B.e_part[chunk] = e;
+  if (threadIdx.x == 0) gst(B.e_part + chunk, e);
   __syncthreads();
   top_emit(B, x, y, a, b, c, TR00, TR10, TR01, TR11, TR02, TR12, br, on, red);
 }
@@ -1005,6 +1060,8 @@ __global__ __launch_bounds__(128) void k_ba_zero_topL(const BaDev* __restrict__ 
 // all active residuals go to the A sums, and the records of a residual that is not active hold zeros — x + 0 is exact — so no flag is read
 // on the value lanes.  clearL: also store zeros into the L sums of p_out (a launch with linearised residuals left values there).
 // Two workgroups per CU: 217 VGPRs (the f64 tiles), 51 KB of LDS.
+// Its global accesses go through gld / gst (ba_kernels.h): a flat store counts in lgkmcnt too, so an LDS read of phase 1 would wait for
+// the r_cj stores issued in front of it (110 against 112 us per 256-window launch, profiles/lin_waits_ab.txt).
 constexpr int SCH_REC = 1024;                         // floats of one record buffer: 16 points x 8 records x 8 floats
 constexpr int SCH_WAVE = 3 * SCH_REC + 16 * 8;        // two JpJdF buffers (double-buffered), one term buffer, the points' phase-2 operands
 // WPH ("wave per host", the form of a large batch): every WAVE takes a whole host frame — all its 16-point groups in a row — and a workgroup
@@ -1060,10 +1117,10 @@ __global__ __launch_bounds__(BA_BLOCK, 2) void k_ba_sc_host(const BaDev* __restr
     const int npts = min(16, pe - p0);
     g.rb = 0; g.prior = 0.f; g.delta = 0.f; g.order = 0xffffffffu; g.on = 0;
     if (npts <= 0) return;
-    g.rb = B.p_rbeg[p0 + min(lane, npts)];
+    g.rb = gld(B.p_rbeg + p0 + min(lane, npts));
     if (pl < npts) {
-      g.prior = B.p_prior[p0 + pl]; g.delta = B.p_delta[p0 + pl]; g.order = B.p_order[p0 + pl];
-      g.on = pflag ? (int)pflag[p0 + pl] : 1;
+      g.prior = gld(B.p_prior + p0 + pl); g.delta = gld(B.p_delta + p0 + pl); g.order = gld(B.p_order + p0 + pl);
+      g.on = pflag ? (int)gld(pflag + p0 + pl) : 1;
     }
   };
   // records [r0, r0 + nrec) -> LDS: 16-byte piece c (record c / 2, half c % 2) of the JpJdF halves lands at float 4 c of dstA, of the term
@@ -1108,7 +1165,7 @@ __global__ __launch_bounds__(BA_BLOCK, 2) void k_ba_sc_host(const BaDev* __restr
 #pragma unroll
       for (int k = 0; k < 4; k++) {
         const int c = lane + 64 * k;
-        if (c < npieces) *(float4*)(dst + (size_t)c * 4) = *(const float4*)(curA + c * 4);
+        if (c < npieces) gst((f32x4*)(dst + (size_t)c * 4), *(const f32x4*)(curA + c * 4));
       }
     }
     SCSUB(1);
@@ -1157,16 +1214,16 @@ __global__ __launch_bounds__(BA_BLOCK, 2) void k_ba_sc_host(const BaDev* __restr
       const float H0 = quad_bcast<0>(H);
       if (pl < npts && onp) {
         float* po = B.p_out + (size_t)(p0 + pl) * 16;
-        if (jq == 0) *(float4*)(po + PO_HDD_A) = make_float4(ay, ax, any ? hdi : 0.f, any ? bds : 0.f);
-        else if (jq < 3) *(float2*)(po + PO_HCD_A + 2 * (jq - 1)) = make_float2(ax, ay);
+        if (jq == 0) gst((f32x4*)(po + PO_HDD_A), (f32x4){ay, ax, any ? hdi : 0.f, any ? bds : 0.f});
+        else if (jq < 3) gst((f32x2*)(po + PO_HCD_A + 2 * (jq - 1)), (f32x2){ax, ay});
         else {
           float* tr = (float*)(B.p_track + p0 + pl);
-          *(float2*)(tr + 2) = make_float2(any ? H0 : 0.f, __int_as_float(mbits));   // p->data->idepth_hessian (:46, :56); the active records for k_ba_resub*
-          if (!any) tr[0] = 0.f;                                                       // p->data->maxRelBaseline = 0 (:47)
+          gst((f32x2*)(tr + 2), (f32x2){any ? H0 : 0.f, __int_as_float(mbits)});   // p->data->idepth_hessian (:46, :56); the active records for k_ba_resub*
+          if (!any) gst(tr, 0.f);                                                      // p->data->maxRelBaseline = 0 (:47)
         }
         if (!PLAIN || clearL) {
-          if (jq == 0) *(float2*)(po + PO_HDD_L) = make_float2(ly, lx);
-          else if (jq < 3) *(float2*)(po + PO_HCD_L + 2 * (jq - 1)) = make_float2(lx, ly);
+          if (jq == 0) gst((f32x2*)(po + PO_HDD_L), (f32x2){ly, lx});
+          else if (jq < 3) gst((f32x2*)(po + PO_HCD_L + 2 * (jq - 1)), (f32x2){lx, ly});
         }
       }
       // the point's operands of phase 2: HdiF, bdSumF, Hcd[4] (zeros without an active residual), the target -> record map, its first record
@@ -1286,24 +1343,24 @@ __global__ __launch_bounds__(BA_BLOCK, 2) void k_ba_sc_host(const BaDev* __restr
             if (t2 < nf) {
               float* blk = accD + (size_t)(h + t1 * nf + t2 * nf2) * 64 + cc;
 #pragma unroll
-              for (int v = 0; v < 4; v++) blk[(ro + v) * 8] = d[v];
-              if (a != b) *(float4*)(accD + (size_t)(h + t2 * nf + t1 * nf2) * 64 + cc * 8 + ro) = make_float4(d[0], d[1], d[2], d[3]);   // the mirror image
+              for (int v = 0; v < 4; v++) gst(blk + (ro + v) * 8, d[v]);
+              if (a != b) gst((f32x4*)(accD + (size_t)(h + t2 * nf + t1 * nf2) * 64 + cc * 8 + ro), (f32x4){d[0], d[1], d[2], d[3]});   // the mirror image
             }
           } else if (cc < 4) {                                 // the special block's columns: Hcd ...
 #pragma unroll
-            for (int v = 0; v < 4; v++) accE[(size_t)(h + t1 * nf) * 32 + (ro + v) * 4 + cc] = d[v];
+            for (int v = 0; v < 4; v++) gst(accE + (size_t)(h + t1 * nf) * 32 + (ro + v) * 4 + cc, d[v]);
           } else if (cc == 4) {                                // ... and bdSumF
 #pragma unroll
-            for (int v = 0; v < 4; v++) accEB[(size_t)(h + t1 * nf) * 8 + ro + v] = d[v];
+            for (int v = 0; v < 4; v++) gst(accEB + (size_t)(h + t1 * nf) * 8 + ro + v, d[v]);
           }
         } else if (b == 3 && t1p == 7 && t2p == 7 && ro == 0) {   // special x special: Hcc (16) and bc (4) of this host; the fold adds the hosts
           float* hp = B.sc_part + (size_t)h * 20;
           if (cc < 4) {
 #pragma unroll
-            for (int v = 0; v < 4; v++) hp[v * 4 + cc] = d[v];
+            for (int v = 0; v < 4; v++) gst(hp + v * 4 + cc, d[v]);
           } else if (cc == 4) {
 #pragma unroll
-            for (int v = 0; v < 4; v++) hp[16 + v] = d[v];
+            for (int v = 0; v < 4; v++) gst(hp + 16 + v, d[v]);
           }
         }
       }
@@ -1313,10 +1370,10 @@ __global__ __launch_bounds__(BA_BLOCK, 2) void k_ba_sc_host(const BaDev* __restr
       const int t = k >> 1;
       if ((k & 1) && t == h) continue;
       const int t1 = (k & 1) ? t : h, t2 = (k & 1) ? h : t;
-      accD[(size_t)(h + t1 * nf + t2 * nf2) * 64 + lane] = 0.f;
+      gst(accD + (size_t)(h + t1 * nf + t2 * nf2) * 64 + lane, 0.f);
     }
-    if (lane < 32) accE[(size_t)(h + h * nf) * 32 + lane] = 0.f;
-    else if (lane < 40) accEB[(size_t)(h + h * nf) * 8 + lane - 32] = 0.f;
+    if (lane < 32) gst(accE + (size_t)(h + h * nf) * 32 + lane, 0.f);
+    else if (lane < 40) gst(accEB + (size_t)(h + h * nf) * 8 + lane - 32, 0.f);
   };
   if (WPH) {
     store_bins(bufA);
