@@ -59,7 +59,7 @@ int sdso_ctx_sync(sdso_ctx* ctx);
 int sdso_ctx_partition_cus(sdso_ctx* ctx, int aux_cus, int stride);
 
 /* Optional kernel timing with HIP events recorded on the ctx stream around launches.  on = 1: the dominant kernel of each workload
- * ("k_track_eval", "k_track_lm", "k_ba_lin_fused", "k_ba_linearize", "k_trace_stereo", ...); on = 2: also the secondary ones
+ * ("k_track_eval", "k_track_lm", "k_ba_lin_fused", "k_ba_linearize", "k_trace_stereo", "k_ingest_level0", ...); on = 2: also the secondary ones
  * ("k_ba_sc", "k_ba_tail", "k_ba_accum_top") — every bracket costs two event records on the stream, which a timed loop should only
  * pay for the kernel it reports; on = 0: off.
  * sdso_prof_read synchronises the stream and returns the accumulated milliseconds / launch count. */
@@ -93,6 +93,63 @@ int sdso_download_pyramid_level(sdso_ctx* ctx, int frame_slot, int lvl, float* d
 /* FrameHessian::absSquaredGrad[lvl] (HessianBlocks.h:109) as the device holds it: w_l*h_l floats */
 int sdso_download_abs_grad(sdso_ctx* ctx, int frame_slot, int lvl, float* out);
 int sdso_release_pyramid(sdso_ctx* ctx, int frame_slot);
+
+/* ------------------------------------------------------------------ frame ingest
+ * Undistort::undistort<T> (src/util/Undistort.cpp:398-489, called from DatasetReader.h:222) followed by FrameHessian::makeImages
+ * (HessianBlocks.cpp:141-203): raw 8- or 16-bit camera images go in, device pyramids come out, with the bits of the reference's
+ * undistort followed by sdso_make_pyramid.  Reading calibration and image files (readFromFile's sscanfs, ImageRW) stays with the caller.
+ * Not built: the benchmark-only geometric noise (benchmark_varNoise, :416-451), applyBlurNoise (:494-583) — both zero by default
+ * (settings.cpp:126-127) — and PhotometricUndistorter::unMapFloatImage (:195-219).
+ *
+ * sdso_undistort_make_remap — host only, no ctx — is the part of Undistort::readFromFile behind the parsing (:793-949) for callers that
+ * have no Undistort object:
+ *   model      : which distortCoordinates body runs (:974-1236), in the reference's float / double promotion
+ *   parsOrg    : 5 doubles (Pinhole, FOV) or 8 (RadTan, Equidistant, KannalaBrandt), in pixels; when parsOrg[2] < 1 && parsOrg[3] < 1 the
+ *                "relative format" rescale of :793-809 is applied first
+ *   out_mode   : SDSO_RECTIFY_CROP = makeOptimalK_crop (:586-709; SDSO_ERR_ARG where the reference exits after 500 shrink steps);
+ *                SDSO_RECTIFY_NONE (:882-895) needs w == wOrg && h == hOrg and sets *passthrough; SDSO_RECTIFY_EXPLICIT takes
+ *                out_calib = relative fx fy cx cy (:896-909); SDSO_RECTIFY_FULL is assert(false) in the reference (:711-714): SDSO_ERR_ARG
+ *   K          : the rectified fx fy cx cy (Undistort::getK)
+ *   remapX/Y   : w*h floats each as the loop of :919-949 leaves them, -1 where the source lies outside — its quirks included: :937 assigns
+ *                ix in the iy == hOrg-1 case and :939 tests iy < wOrg-1 */
+#define SDSO_CAM_PINHOLE 0
+#define SDSO_CAM_FOV 1
+#define SDSO_CAM_RADTAN 2
+#define SDSO_CAM_EQUIDISTANT 3
+#define SDSO_CAM_KANNALABRANDT 4
+#define SDSO_RECTIFY_CROP 0
+#define SDSO_RECTIFY_NONE 1
+#define SDSO_RECTIFY_FULL 2
+#define SDSO_RECTIFY_EXPLICIT 3
+int sdso_undistort_make_remap(int model, const double* parsOrg, int wOrg, int hOrg, int w, int h, int out_mode,
+                              const float* out_calib /* 4, SDSO_RECTIFY_EXPLICIT only */, double* K /* 4 */,
+                              float* remapX /* w*h */, float* remapY /* w*h */, int* passthrough);
+/* One camera's undistortion tables, uploaded once and resident under the caller-chosen id `calib` (an id in use is replaced once the new
+ * tables are complete; if the call fails the id keeps its old ones).  w x h must give pyramid levels of at least 8 pixels each way:
+ *   remapX/Y        : Undistort::remapX / remapY (w*h each) — the reference's own arrays or sdso_undistort_make_remap's; NULL = passthrough
+ *                     (:481-483; needs w == wOrg && h == hOrg).  A negative remapX yields 0 (:454-456).  An entry that passed :939 but whose
+ *                     four taps (int)x, (int)y, +1, +1 do not all lie inside wOrg x hOrg is an out-of-bounds read in the reference; like
+ *                     the unrepresentable projections of sdso_distmap_make it counts as outside the image and yields 0.
+ *   pixel_bytes     : 1 (MinimalImageB) or 2 (MinimalImage<unsigned short>)
+ *   G               : PhotometricUndistorter::G after the normalisation of :114-123, 256 floats for 1-byte pixels, 65536 for 2-byte
+ *                     ones; NULL = the reference's !valid
+ *   vignetteMapInv  : wOrg*hOrg floats (:179-181) or NULL; required with G in mode 2
+ *   photometricCalibration, useExposure : setting_photometricCalibration (settings.cpp:88) 0, 1 or 2 and setting_useExposure (:89) */
+int sdso_ingest_calib_create(sdso_ctx* ctx, int calib, int wOrg, int hOrg, int w, int h, const float* remapX, const float* remapY,
+                             int pixel_bytes, const float* G, const float* vignetteMapInv, int photometricCalibration, int useExposure);
+int sdso_ingest_calib_release(sdso_ctx* ctx, int calib);
+/* Undistort::undistort<T>(raw[i], exposure[i], timestamp, factor) steps 1 and 2 and makeImages into pyramid slot frame_slots[i], for the
+ * n_images (1 or 2: left and right) images of one frame.  Step 1 is PhotometricUndistorter::processFrame (:222-260): factor * raw when G is
+ * NULL, exposure[i] <= 0 or the mode is 0, else G[raw], times vignetteMapInv in mode 2; exposure_out[i] (may be NULL) is exposure[i], or 1
+ * with useExposure off (:258-259).  The gamma weighting of sdso_set_gamma applies as for any pyramid built after it.
+ * The call only ENQUEUES, like sdso_ba_upload_window: the raw bytes are copied into pinned staging before it returns (the caller's
+ * buffers may go away), everything is issued on the ctx stream and nothing synchronises — with one exception: a slot that holds a
+ * pyramid of another shape is released and allocated anew, as sdso_make_pyramid does, and that release synchronises the stream (a slot
+ * of the calibration's shape, or an empty one, does not).  An unknown calib, a NULL image, a slot named twice or n_images outside 1..2
+ * return SDSO_ERR_ARG before any device work and before any slot or staging buffer is touched; a w x h whose pyramid would hold a level
+ * below 8 pixels is refused by sdso_ingest_calib_create already, so no slot's shape can fail here. */
+int sdso_ingest_frame(sdso_ctx* ctx, int calib, int n_images, const int* frame_slots, const void* const* raw, const float* exposure,
+                      float factor, float* exposure_out);
 
 /* ------------------------------------------------------------------ coarse tracker
  * CoarseTracker::calcRes + calcGSSSE (src/FullSystem/CoarseTracker.cpp:600-792, :537-596),

@@ -94,48 +94,16 @@ static int dmalloc(sdso_ctx* ctx, BaWindowDev* W, void** p, size_t bytes, bool z
   W->allocs.emplace_back(*p, got);
   return SDSO_OK;
 }
-// pinned host staging of the ctx (window uploads, table refreshes): grown on demand, released with the ctx's windows.  The caller
-// synchronises the stream before the next reservation is written.
-// Two buffers taken in turn, each with an event that marks the last copy enqueued from it (stage_commit): a caller that commits need not
-// synchronise the stream — the buffer is only waited for when its turn comes again, two reservations later.  A caller that does not commit
-// synchronises the stream itself before the ctx reserves again (upload_tables, opt_finish).
-struct StageBuf { char* p[2] = {nullptr, nullptr}; size_t cap[2] = {0, 0}; hipEvent_t ev[2] = {nullptr, nullptr}; bool busy[2] = {false, false}; int cur = 0; };
 struct OptBufs;
 struct OptRun;
 // the BA state of a ctx besides its windows (sdso_ctx::ba): created by the first call that needs it, freed with the windows
 struct BaCtxState {
-  StageBuf stage;
+  StageBuf stage;             // pinned host staging of window uploads and table refreshes (sdso_internal.h), released with the ctx's windows
   BaBatch* batch = nullptr;   // sdso_ba_batch_create
   OptBufs* bufs = nullptr;    // scratch of the resident GN loop
   OptRun* run = nullptr;      // the batch loop in flight between sdso_ba_batch_optimize_begin and _end
 };
 static BaCtxState& ba_state(sdso_ctx* ctx) { if (!ctx->ba) ctx->ba = new BaCtxState(); return *ctx->ba; }
-static int stage_reserve(sdso_ctx* ctx, size_t bytes, char** out) {
-  StageBuf& b = ba_state(ctx).stage;
-  b.cur ^= 1;
-  const int k = b.cur;
-  if (b.busy[k]) { SDSO_HIP(ctx, hipEventSynchronize(b.ev[k])); b.busy[k] = false; }
-  if (bytes > b.cap[k]) {
-    if (b.p[k]) { SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream)); hipHostFree(b.p[k]); }
-    b.p[k] = nullptr; b.cap[k] = 0;
-    const size_t want = (bytes * 3 / 2 + 4095) & ~(size_t)4095;
-    SDSO_HIP(ctx, hipHostMalloc((void**)&b.p[k], want));
-    b.cap[k] = want;
-  }
-  *out = b.p[k];
-  return SDSO_OK;
-}
-static int stage_commit(sdso_ctx* ctx) {      // everything that reads the latest reservation has been enqueued on ctx->stream
-  StageBuf& b = ba_state(ctx).stage;
-  const int k = b.cur;
-  if (!b.ev[k]) SDSO_HIP(ctx, hipEventCreateWithFlags(&b.ev[k], hipEventDisableTiming));
-  SDSO_HIP(ctx, hipEventRecord(b.ev[k], ctx->stream));
-  b.busy[k] = true;
-  return SDSO_OK;
-}
-static void stage_free(StageBuf& b) {
-  for (int k = 0; k < 2; k++) { if (b.ev[k]) hipEventDestroy(b.ev[k]); if (b.p[k]) hipHostFree(b.p[k]); }
-}
 #define DM(ptr, T, count)                                                   \
   do {                                                                      \
     void* _p = nullptr;                                                     \
@@ -226,7 +194,7 @@ static int upload_tables(sdso_ctx* ctx, BaWindowDev* W, bool adjoints, bool sync
   const int nf = W->d.nf, n = W->d.n;
   if (!built) build_tables(W, adjoints);
   if (!stage) {
-    int rc = stage_reserve(ctx, W->tbl_bytes, &stage);
+    int rc = stage_reserve(ctx, ba_state(ctx).stage, W->tbl_bytes, &stage);
     if (rc) return rc;
     sync = true;
   }
@@ -492,7 +460,7 @@ static int upload_window_impl(sdso_ctx* ctx, int win, const sdso_ba_window_t* Wi
   W->tbl_first = (char*)W->dt_precalc; W->tbl_bytes = (size_t)((char*)W->d_self + sizeof(BaDev) - (char*)W->dt_precalc);
   char* stage = nullptr;
   {
-    int rc2 = stage_reserve(ctx, init_bytes, &stage);
+    int rc2 = stage_reserve(ctx, ba_state(ctx).stage, init_bytes, &stage);
     if (rc2) return rc2;
     std::memset(stage, 0, init_bytes);
   }
@@ -570,7 +538,7 @@ static int upload_window_impl(sdso_ctx* ctx, int win, const sdso_ba_window_t* Wi
   SDSO_HIP(ctx, hipGetLastError());
   // no synchronisation: the upload is ENQUEUED (copy, clear, init kernel) and whatever the caller does next on this ctx queues behind it;
   // the staging buffer is marked in flight (round 5 waited here: 38 of the call's 160 us)
-  { const int rcc = stage_commit(ctx); if (rcc) return rcc; }
+  { const int rcc = stage_commit(ctx, ba_state(ctx).stage); if (rcc) return rcc; }
   mark("copy + clear + init kernel (enqueue)");
   return SDSO_OK;
 }
@@ -1975,7 +1943,7 @@ static int opt_finish(sdso_ctx* ctx, OptRun& R, sdso_ba_opt_result_t* out) {
   size_t tb = 0;
   for (BaWindowDev* W : R.W) tb = std::max(tb, (W->tbl_bytes + 255) & ~(size_t)255);
   char* tstage = nullptr;
-  if ((rc = stage_reserve(ctx, tb * nwin, &tstage))) return rc;      // released for reuse by the synchronisation of opt_collect below
+  if ((rc = stage_reserve(ctx, ba_state(ctx).stage, tb * nwin, &tstage))) return rc;      // released for reuse by the synchronisation of opt_collect below
   for (int w = 0; w < nwin; w++) {
     BaWindowDev* W = R.W[w];
     if ((rc = upload_tables(ctx, W, true, false, true, tstage + tb * w))) return rc;

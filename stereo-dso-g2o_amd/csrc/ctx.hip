@@ -133,6 +133,7 @@ void release_stereo(sdso_ctx* ctx);
 void release_selector(sdso_ctx* ctx);
 void release_g2o(sdso_ctx* ctx);
 void release_distmap(sdso_ctx* ctx);
+void release_ingest(sdso_ctx* ctx);
 void release_comm(sdso_ctx* ctx);
 }
 
@@ -153,6 +154,7 @@ extern "C" void sdso_ctx_destroy(sdso_ctx* ctx) {
   release_selector(ctx);
   release_g2o(ctx);
   release_distmap(ctx);
+  release_ingest(ctx);
   release_comm(ctx);
   if (ctx->gammaB) hipFree(ctx->gammaB);
   if (ctx->scratch) hipFree(ctx->scratch);
@@ -336,26 +338,43 @@ extern "C" int sdso_download_abs_grad(sdso_ctx* ctx, int frame_slot, int lvl, fl
   return SDSO_OK;
 }
 
-extern "C" int sdso_make_pyramid(sdso_ctx* ctx, int frame_slot, int w, int h, const float* color) {
-  if (!ctx) return SDSO_ERR_STATE;
-  SDSO_HIP(ctx, hipSetDevice(ctx->device));
-  SDSO_REQUIRE(ctx, color, "null argument");
+namespace sdso {
+// the slot's device pyramid for a w x h level 0 (globalCalib.cpp:52-58 decides the level count); buffers of the same shape are kept
+int pyramid_prepare(sdso_ctx* ctx, int frame_slot, int w, int h, PyramidDev** out) {
   int levels = sdso_pyramid_levels(w, h);
   int ws[SDSO_PYR_LEVELS], hs[SDSO_PYR_LEVELS];
   for (int l = 0; l < levels; l++) { ws[l] = w >> l; hs[l] = h >> l; }
   int rc = alloc_pyramid(ctx, frame_slot, levels, ws, hs);
   if (rc) return rc;
-  PyramidDev& P = ctx->pyr[frame_slot];
+  *out = &ctx->pyr[frame_slot];
+  return SDSO_OK;
+}
+// HessianBlocks.cpp:160-199 once level 0 holds the intensities: gradients of level 0, then box mean + gradients level by level
+int pyramid_finish_levels(sdso_ctx* ctx, PyramidDev& P) {
+  for (int l = 0; l < P.levels; l++) {
+    if (l > 0) hipLaunchKernelGGL(k_downsample, dim3((P.w[l] + 255) / 256, P.h[l]), dim3(256), 0, ctx->stream, P.d[l - 1], P.w[l - 1], P.d[l], P.w[l], P.h[l]);
+    int ng = P.w[l] * (P.h[l] - 2);
+    hipLaunchKernelGGL(k_gradients, dim3((ng + 255) / 256), dim3(256), 0, ctx->stream, P.d[l], P.w[l], P.h[l], (const float*)ctx->gammaB);
+  }
+  SDSO_HIP(ctx, hipGetLastError());
+  return SDSO_OK;
+}
+}  // namespace sdso
+
+extern "C" int sdso_make_pyramid(sdso_ctx* ctx, int frame_slot, int w, int h, const float* color) {
+  if (!ctx) return SDSO_ERR_STATE;
+  SDSO_HIP(ctx, hipSetDevice(ctx->device));
+  SDSO_REQUIRE(ctx, color, "null argument");
+  PyramidDev* Pp = nullptr;
+  int rc = pyramid_prepare(ctx, frame_slot, w, h, &Pp);
+  if (rc) return rc;
+  PyramidDev& P = *Pp;
   rc = ensure_scratch(ctx, (size_t)w * h * sizeof(float));
   if (rc) return rc;
   SDSO_HIP(ctx, hipMemcpyAsync(ctx->scratch, color, (size_t)w * h * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL(k_set_level0, dim3((w * h + 255) / 256), dim3(256), 0, ctx->stream, (const float*)ctx->scratch, P.d[0], w * h);
-  for (int l = 0; l < levels; l++) {
-    if (l > 0) hipLaunchKernelGGL(k_downsample, dim3((ws[l] + 255) / 256, hs[l]), dim3(256), 0, ctx->stream, P.d[l - 1], ws[l - 1], P.d[l], ws[l], hs[l]);
-    int ng = ws[l] * (hs[l] - 2);
-    hipLaunchKernelGGL(k_gradients, dim3((ng + 255) / 256), dim3(256), 0, ctx->stream, P.d[l], ws[l], hs[l], (const float*)ctx->gammaB);
-  }
-  SDSO_HIP(ctx, hipGetLastError());
+  rc = pyramid_finish_levels(ctx, P);
+  if (rc) return rc;
   SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SDSO_OK;
 }

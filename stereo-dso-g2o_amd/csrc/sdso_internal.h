@@ -54,6 +54,7 @@ struct StereoState;  // stereo.hip
 struct SelState;     // selector.hip
 struct G2oState;     // g2o_factors.hip
 struct DistMapState; // distmap.hip
+struct IngestState;  // ingest.hip
 struct Comm;         // comm.hip
 
 }  // namespace sdso
@@ -72,6 +73,7 @@ struct sdso_ctx {
   sdso::SelState* sel = nullptr;        // the pixel selector's random pattern
   sdso::G2oState* g2o = nullptr;        // edge sets and partial systems of the g2o factors
   sdso::DistMapState* dm = nullptr;     // the level-1 CoarseDistanceMap
+  sdso::IngestState* ingest = nullptr;  // calibration tables and raw-image staging of sdso_ingest_frame
   std::shared_ptr<sdso::Comm> comm;     // shared with the contexts joined by sdso_comm_attach
   // generic scratch
   void* scratch = nullptr;
@@ -160,8 +162,40 @@ inline void launch_timed(sdso_ctx* ctx, const char* name, int level, K kernel, c
   hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, args...);
 }
 int ensure_pinned(sdso_ctx* ctx, size_t bytes);
+// Pinned host staging for the enqueue-only entry points (window uploads and table refreshes of the BA, raw images of the frame ingest),
+// grown on demand.  Two buffers taken in turn, each with an event that marks the last copy enqueued from it (stage_commit): a caller that
+// commits need not synchronise the stream — the buffer is only waited for when its turn comes again, two reservations later.  A caller
+// that does not commit synchronises the stream itself before the same StageBuf is reserved again.
+struct StageBuf { char* p[2] = {nullptr, nullptr}; size_t cap[2] = {0, 0}; hipEvent_t ev[2] = {nullptr, nullptr}; bool busy[2] = {false, false}; int cur = 0; };
+inline int stage_reserve(sdso_ctx* ctx, StageBuf& b, size_t bytes, char** out) {
+  b.cur ^= 1;
+  const int k = b.cur;
+  if (b.busy[k]) { SDSO_HIP(ctx, hipEventSynchronize(b.ev[k])); b.busy[k] = false; }
+  if (bytes > b.cap[k]) {
+    if (b.p[k]) { SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream)); hipHostFree(b.p[k]); }
+    b.p[k] = nullptr; b.cap[k] = 0;
+    const size_t want = (bytes * 3 / 2 + 4095) & ~(size_t)4095;
+    SDSO_HIP(ctx, hipHostMalloc((void**)&b.p[k], want));
+    b.cap[k] = want;
+  }
+  *out = b.p[k];
+  return SDSO_OK;
+}
+inline int stage_commit(sdso_ctx* ctx, StageBuf& b) {   // everything that reads the latest reservation has been enqueued on ctx->stream
+  const int k = b.cur;
+  if (!b.ev[k]) SDSO_HIP(ctx, hipEventCreateWithFlags(&b.ev[k], hipEventDisableTiming));
+  SDSO_HIP(ctx, hipEventRecord(b.ev[k], ctx->stream));
+  b.busy[k] = true;
+  return SDSO_OK;
+}
+inline void stage_free(StageBuf& b) {
+  for (int k = 0; k < 2; k++) { if (b.ev[k]) hipEventDestroy(b.ev[k]); if (b.p[k]) hipHostFree(b.p[k]); }
+  b = StageBuf();
+}
 int ensure_tiled0(sdso_ctx* ctx, PyramidDev& P);   // ctx.hip
 int ensure_plane0(sdso_ctx* ctx, PyramidDev& P);   // ctx.hip
+int pyramid_prepare(sdso_ctx* ctx, int frame_slot, int w, int h, PyramidDev** out);   // ctx.hip
+int pyramid_finish_levels(sdso_ctx* ctx, PyramidDev& P);                              // ctx.hip
 // pixel (x, y) of a 4x2-tiled level-0 image with T tiles per row
 __host__ __device__ inline int tiled_index(int x, int y, int T) { return (((y >> 1) * T + (x >> 2)) << 3) + ((y & 1) << 2) + (x & 3); }
 

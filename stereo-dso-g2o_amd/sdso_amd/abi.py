@@ -459,6 +459,10 @@ def load():
     L.sdso_distmap_add.argtypes = [vp, C.c_int, c_int_p, c_int_p]
     L.sdso_distmap_get.argtypes = [vp, c_float_p]
     L.sdso_activate_select.argtypes = [vp, C.POINTER(ActivateSelect), c_u8_p, c_int_p, c_int_p, c_int_p]
+    L.sdso_undistort_make_remap.argtypes = [C.c_int, c_double_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_double_p, c_float_p, c_float_p, c_int_p]
+    L.sdso_ingest_calib_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, C.c_int, c_float_p, c_float_p, C.c_int, C.c_int]
+    L.sdso_ingest_calib_release.argtypes = [vp, C.c_int]
+    L.sdso_ingest_frame.argtypes = [vp, C.c_int, C.c_int, c_int_p, C.POINTER(vp), c_float_p, C.c_float, c_float_p]
     _lib = L
     return L
 
@@ -484,6 +488,7 @@ EXPORTED_SYMBOLS = [
     "sdso_comm_unique_id", "sdso_comm_init", "sdso_comm_init_host", "sdso_comm_attach", "sdso_comm_info", "sdso_comm_destroy", "sdso_ba_allreduce", "sdso_ba_allreduce_window",
     "sdso_g2o_track_add_edges", "sdso_g2o_track_linearize", "sdso_g2o_track_newest_coarse", "sdso_g2o_lba_eval", "sdso_trace_set_gn_mode",
     "sdso_distmap_make", "sdso_distmap_add", "sdso_distmap_get", "sdso_activate_select",
+    "sdso_undistort_make_remap", "sdso_ingest_calib_create", "sdso_ingest_calib_release", "sdso_ingest_frame",
 ]
 
 
@@ -520,6 +525,16 @@ class Context:
         n = C.c_long(0)
         self.check(self.L.sdso_prof_read(self.h, kernel.encode(), C.byref(ms), C.byref(n)))
         return ms.value, n.value
+
+    def ingest_frame(self, calib, slots, raws, exposure, factor=1.0):
+        """sdso_ingest_frame for 1 or 2 raw images (uint8 / uint16 arrays); enqueue-only.  Returns exposure_out."""
+        n = len(slots)
+        arrs = [np.ascontiguousarray(r) for r in raws]
+        ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
+        ex = np.ascontiguousarray(exposure, np.float32)
+        out = np.zeros(n, np.float32)
+        self.check(self.L.sdso_ingest_frame(self.h, calib, n, (C.c_int * n)(*slots), ptrs, fp(ex), factor, fp(out)))
+        return out
 
     def upload_pyramid(self, slot, pyr):
         n = len(pyr)
