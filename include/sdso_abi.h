@@ -754,6 +754,68 @@ typedef struct {
 int sdso_stereo_match_batch(sdso_ctx* ctx, int slot_a, int slot_b, const float K[4], float baseline,
                             int mode_right_first, sdso_stereo_match_t* m);
 
+/* ------------------------------------------------------------------ the device-resident immature points
+ * One set per ctx: the ImmaturePoint objects of every keyframe of the window (host->immaturePoints, HessianBlocks.h), grouped by a
+ * caller-chosen host_id, each group in the order of the reference's vector.  Stored per point, exactly the members the reference carries
+ * (ImmaturePoint.h:60-102): u, v, my_type, idepth_min, idepth_max, quality, color[8], weights[8], gradH[4], energyTH, lastTraceStatus,
+ * lastTraceUV[2], lastTracePixelInterval.  The order of a host's points is part of the state (activatePointsMT STEP 2,
+ * FullSystem.cpp:837-902, walks it in index order).  The set has buffers of its own: no other entry point reads or writes them.
+ * A call that needs a host's count on the host side waits for the add that made it (an event, not the stream); nothing else synchronises
+ * unless stated. */
+
+/* FullSystem::makeNewTraces, the loop at FullSystem.cpp:1611-1626: for y in [3, h-4), x in [3, w-4) (patternPadding = 2) every pixel with
+ * map != 0 becomes ImmaturePoint(x, y, frame, map[i]) (ImmaturePoint.cpp:33-62: idepth_min 0, idepth_max NaN, quality 10000,
+ * IPS_UNINITIALIZED; lastTraceUV and lastTracePixelInterval, which the reference leaves uninitialised, are 0); a point whose energyTH is
+ * not finite is dropped (:1619-1621); the survivors become the points of host_id in raster order.  Both compactions (map entries, then
+ * survivors) run on the device in order.
+ *   selection_map : w*h host floats, or NULL = the map of the latest sdso_pixel_select of this ctx, which must have been made on
+ *                   frame_slot (SDSO_ERR_STATE otherwise)
+ *   n_out         : the number of points stored; NULL = enqueue only (reading the count waits for the device)
+ * SDSO_ERR_ARG for a host_id that already has points (sdso_imm_release_host first). */
+int sdso_imm_add_frame(sdso_ctx* ctx, int host_id, int frame_slot, const float* selection_map, int* n_out);
+
+/* FullSystem::traceNewCoarseKey (FullSystem.cpp:745-781, right_slot < 0) and traceNewCoarseNonKey (:632-742, right_slot >= 0) on the set,
+ * in place.  geom[g] names a host and carries what the caller computes at :654-665: KRKi = K R K^-1, Kt = K t, aff =
+ * AffLight::fromToVecExposure(...), KRi = K R^-1, t, all as floats; Ki is the caller's K.inverse() (:645); K = {fx,fy,cx,cy}.  Hosts of
+ * the set that geom does not name are left untouched.  At most SDSO_IMM_MAX_HOSTS geometries per call.
+ *   every point of every named host: ImmaturePoint::traceOn(frame_slot, KRKi, Kt, aff) (ImmaturePoint.cpp:459-828)
+ *   non-key, for every point whose traceOn returned IPS_GOOD (floats, one rounding per operation, row products summed left to right):
+ *     idepth_{min,max}_project = 1 / (KRKi * (Vec3f(u,v,1) / idepth_{min,max}) + Kt)[2]                                   (:675-679)
+ *     fwd  = ImmaturePoint(lastTraceUV, frame_slot) with idepth_min = idepth_min_stereo = min_project, idepth_max_stereo =
+ *            max_project, traced by traceStereo(right_slot, K, 1)                                                         (:672-689)
+ *     back = if fwd is IPS_GOOD: ImmaturePoint(fwd.lastTraceUV, right_slot) with the projected interval, traceStereo(frame_slot, K, 0);
+ *            its status is not examined                                                                                   (:691-700)
+ *     if |fwd.u_stereo - back.lastTraceUV[0]| > 1 and fwd.u_stereo - fwd.lastTraceUV[0] < 10: lastTraceStatus = IPS_OUTLIER, nothing
+ *     else changes; otherwise idepth_{min,max} = 1 / (KRi * (Ki * Vec3f(fwd.u_stereo, fwd.v_stereo, 1) / fwd.idepth_{min,max}_stereo
+ *     - t))[2]                                                                                                            (:703-720)
+ *   Both traceStereo launches use the ctx's refinement mode (sdso_trace_set_gn_mode).  A GOOD lastTraceUV outside [2, w-3) x [2, h-3),
+ *   where the reference's constructor would read outside the image, takes no (further) stereo step and is counted as unreadable.
+ *   counts : NULL = enqueue only.  Otherwise SDSO_IMM_NCOUNTS ints, after a synchronisation: [0..5] the histogram of lastTraceStatus over
+ *            the traced points as the call leaves it, [6] forward traces that were IPS_GOOD, [7] points set IPS_OUTLIER by the stereo
+ *            rule, [8] intervals updated, [9] unreadable points ([6..9] are 0 for the key form).
+ * SDSO_ERR_ARG before any device work for an unknown host_id, one named twice, or a frame of another size than the host's. */
+#define SDSO_IMM_MAX_HOSTS 8
+#define SDSO_IMM_NCOUNTS 10
+typedef struct { int host_id; float KRKi[9]; float Kt[3]; float aff[2]; float KRi[9]; float t[3]; } sdso_imm_geom_t;
+int sdso_imm_trace(sdso_ctx* ctx, int frame_slot, int right_slot, int ngeom, const sdso_imm_geom_t* geom, const float K[4],
+                   const float Ki[9], float baseline, int* counts);
+
+/* host->immaturePoints.size() (0 for a host the set does not hold), and one host's points copied back in the traceOn convention of
+ * sdso_trace_points_t: u_stereo / v_stereo = u / v, idepth_min_stereo / idepth_max_stereo = idepth_min / idepth_max; out->idepth_min and
+ * out->idepth_stereo are not written; null members are skipped; out->n is set.  This is the per-keyframe download that feeds
+ * sdso_activate_select and sdso_activate_points_batch.  sdso_imm_get returns SDSO_ERR_ARG for an unknown host_id. */
+int sdso_imm_count(sdso_ctx* ctx, int host_id, int* n);
+int sdso_imm_get(sdso_ctx* ctx, int host_id, sdso_trace_points_t* out, float* my_type);
+
+/* FullSystem::activatePointsMT STEP 5 (FullSystem.cpp:948-957): `if entry i is flagged: entry i = back(); pop_back(); i--`, the entry moved
+ * in being examined again.  Host only: src[j] (j < *n_out) is the old index of the entry that ends at index j.
+ * sdso_imm_remove applies that order to a host's arrays with a gather on the device (enqueue only); n must be the host's count. */
+int sdso_imm_remove_order(int n, const uint8_t* flags, int* n_out, int* src);
+int sdso_imm_remove(sdso_ctx* ctx, int host_id, int n, const uint8_t* flags);
+/* the points of a frame that leaves the window (`delete` of FrameHessian::immaturePoints, HessianBlocks.h); an unknown host_id is not an
+ * error */
+int sdso_imm_release_host(sdso_ctx* ctx, int host_id);
+
 /* ------------------------------------------------------------------ the fork's live g2o factors
  * gyubeomim/stereo-dso-g2o routes tracking, window optimisation and the sub-pixel trace refinement through g2o edges
  * (src/FullSystem/dso_g2o_edge.cpp, dso_g2o_vertex.cpp).  The edges' own arithmetic is specified by the reference tree and

@@ -134,6 +134,7 @@ void release_selector(sdso_ctx* ctx);
 void release_g2o(sdso_ctx* ctx);
 void release_distmap(sdso_ctx* ctx);
 void release_ingest(sdso_ctx* ctx);
+void release_immature(sdso_ctx* ctx);
 void release_comm(sdso_ctx* ctx);
 }
 
@@ -155,6 +156,7 @@ extern "C" void sdso_ctx_destroy(sdso_ctx* ctx) {
   release_g2o(ctx);
   release_distmap(ctx);
   release_ingest(ctx);
+  release_immature(ctx);
   release_comm(ctx);
   if (ctx->gammaB) hipFree(ctx->gammaB);
   if (ctx->scratch) hipFree(ctx->scratch);
@@ -249,6 +251,7 @@ extern "C" int sdso_release_pyramid(sdso_ctx* ctx, int frame_slot) {
   auto it = ctx->pyr.find(frame_slot);
   if (it == ctx->pyr.end()) return SDSO_OK;
   SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  selector_forget_slot(ctx, frame_slot);
   free_pyramid(it->second);
   ctx->pyr.erase(it);
   return SDSO_OK;
@@ -260,7 +263,7 @@ static int alloc_pyramid(sdso_ctx* ctx, int frame_slot, int levels, const int* w
   if (it != ctx->pyr.end()) {
     bool same = it->second.levels == levels;
     for (int l = 0; same && l < levels; l++) same = it->second.w[l] == w[l] && it->second.h[l] == h[l];
-    if (same) { it->second.tiled_ok = false; it->second.plane_ok = false; return SDSO_OK; }   // new content arrives in the same buffers
+    if (same) { selector_forget_slot(ctx, frame_slot); it->second.tiled_ok = false; it->second.plane_ok = false; return SDSO_OK; }   // new content arrives in the same buffers
     int rc = sdso_release_pyramid(ctx, frame_slot);
     if (rc) return rc;
   }

@@ -55,6 +55,7 @@ struct SelState;     // selector.hip
 struct G2oState;     // g2o_factors.hip
 struct DistMapState; // distmap.hip
 struct IngestState;  // ingest.hip
+struct ImmState;     // immature.hip (compiled with stereo.hip)
 struct Comm;         // comm.hip
 
 }  // namespace sdso
@@ -74,6 +75,7 @@ struct sdso_ctx {
   sdso::G2oState* g2o = nullptr;        // edge sets and partial systems of the g2o factors
   sdso::DistMapState* dm = nullptr;     // the level-1 CoarseDistanceMap
   sdso::IngestState* ingest = nullptr;  // calibration tables and raw-image staging of sdso_ingest_frame
+  sdso::ImmState* imm = nullptr;        // the device-resident immature points, per host keyframe (sdso_imm_*)
   std::shared_ptr<sdso::Comm> comm;     // shared with the contexts joined by sdso_comm_attach
   // generic scratch
   void* scratch = nullptr;
@@ -192,6 +194,10 @@ inline void stage_free(StageBuf& b) {
   for (int k = 0; k < 2; k++) { if (b.ev[k]) hipEventDestroy(b.ev[k]); if (b.p[k]) hipHostFree(b.p[k]); }
   b = StageBuf();
 }
+// the device copy of the map the latest sdso_pixel_select of this ctx made, if it was made on `frame_slot` at w x h; *num = the
+// number of its non-zero entries (selector.hip)
+void selector_forget_slot(sdso_ctx* ctx, int frame_slot);   // the slot is released or takes another image: that map is no longer its map
+bool selector_final_map(sdso_ctx* ctx, int frame_slot, int w, int h, const float** map, int* num);
 int ensure_tiled0(sdso_ctx* ctx, PyramidDev& P);   // ctx.hip
 int ensure_plane0(sdso_ctx* ctx, PyramidDev& P);   // ctx.hip
 int pyramid_prepare(sdso_ctx* ctx, int frame_slot, int w, int h, PyramidDev** out);   // ctx.hip

@@ -15,6 +15,7 @@
 // reference's operation order (no FP contraction) => statuses, bestIdx and all outputs are
 // bit-identical to the CPU path.
 #include "sdso_internal.h"
+#include <algorithm>
 #include <cmath>
 
 using namespace sdso;
@@ -386,13 +387,12 @@ __global__ __launch_bounds__(256) void k_trace_stereo_blk(TraceDev T) {
 
 // ImmaturePoint::traceOn (ImmaturePoint.cpp:459-828): the same search along a general epipolar line.  geom[pgeom[i]] is the
 // hostToFrame geometry of the point's host; T.idepth_min_stereo / idepth_max_stereo hold idepth_min / idepth_max.
-__global__ __launch_bounds__(256) void k_trace_on(TraceDev T, const sdso_trace_geom_t* __restrict__ geom, const int* __restrict__ pgeom) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int i = blockIdx.x * 4 + wv;
-  if (i >= T.n) return;
+// trace_on_point is the body for point i of T on the calling wave; getG() yields the point's geometry (read only once the point is
+// known to be traced).  k_trace_on runs it on uploaded arrays, k_imm_trace_on (immature.hip) on the resident set.
+template <class GetG>
+__device__ __forceinline__ void trace_on_point(const TraceDev& T, const int i, volatile float* errors, GetG getG) {
+  const int lane = threadIdx.x & 63;
   if (T.skip && T.skip[i]) { if (lane == 0 && T.status) T.status[i] = 255; return; }
-  __shared__ float s_err[4][128];
-  volatile float* errors = s_err[wv];
   const float4* __restrict__ dI = T.img;
   const int wG0 = T.w, hG0 = T.h;
   const float u_stereo = T.u_stereo[i], v_stereo = T.v_stereo[i];
@@ -404,7 +404,7 @@ __global__ __launch_bounds__(256) void k_trace_on(TraceDev T, const sdso_trace_g
   float quality = T.quality[i];
   const uint8_t prevStatus = T.lastTraceStatus[i];
   if (prevStatus == IPS_OOB) { if (lane == 0 && T.status) T.status[i] = IPS_OOB; return; }   // :466-468
-  const sdso_trace_geom_t G = geom[pgeom[i]];
+  const sdso_trace_geom_t G = getG();
 
   auto finish = [&](int st, float uvx, float uvy, float interval, bool writeUV) {
     if (lane == 0) {
@@ -591,6 +591,13 @@ __global__ __launch_bounds__(256) void k_trace_on(TraceDev T, const sdso_trace_g
   if (lane == 0) { T.idepth_min_stereo[i] = idepth_min_stereo; T.idepth_max_stereo[i] = idepth_max_stereo; }
   if (!isfinite(idepth_min_stereo) || !isfinite(idepth_max_stereo) || (idepth_max_stereo < 0)) { finish(IPS_OUTLIER, -1, -1, 0, true); return; }
   finish(IPS_GOOD, bestU, bestV, 2 * errorInPixel, true);
+}
+__global__ __launch_bounds__(256) void k_trace_on(TraceDev T, const sdso_trace_geom_t* __restrict__ geom, const int* __restrict__ pgeom) {
+  const int wv = threadIdx.x >> 6;
+  const int i = blockIdx.x * 4 + wv;
+  if (i >= T.n) return;
+  __shared__ float s_err[4][128];
+  trace_on_point(T, i, s_err[wv], [&] { return geom[pgeom[i]]; });
 }
 
 // ------------------------------------------------------------------ API
@@ -1084,3 +1091,5 @@ extern "C" int sdso_activate_points_batch(sdso_ctx* ctx, const sdso_activate_t* 
   SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SDSO_OK;
 }
+
+#include "immature.hip"   // the device-resident immature-point set (reuses TraceDev, the trace kernels and the match batches' helpers)

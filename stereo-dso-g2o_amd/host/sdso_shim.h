@@ -23,6 +23,7 @@
 //   EnergyFunctional::{calcLEnergyF_MT, calcMEnergyF, setDeltaF, setAdjointsF}                                       OptimizationBackend/EnergyFunctional.h:75-86
 //   CoarseDistanceMap::{makeK, makeDistanceMap, addIntoDistFinal, fwdWarpedIDDistFinal, K, Ki}                          FullSystem/CoarseTracker.h:165-197
 //   void FullSystem::activatePointsMT() STEP 1-2                                                                      FullSystem/FullSystem.cpp:796-902
+//   void FullSystem::makeNewTraces(FrameHessian*, FrameHessian*, float*), traceNewCoarseNonKey / traceNewCoarseKey(fh, fh_right)    FullSystem/FullSystem.cpp:1600, :632, :745
 //   Undistort::{undistort<T>, getK, getSize, getOriginalSize, getBl, isValid, loadPhotometricCalibration}               util/Undistort.h:63-104
 #pragma once
 #include <algorithm>
@@ -1057,15 +1058,23 @@ inline auto traceOn(Device& dev, ImmaturePointT* p, int frame_slot, const Mat33f
 // column summed left to right.
 namespace detail {
 template <class M> inline auto inverse33(const M& m, int) -> decltype(m.inverse()) { return m.inverse(); }
-template <class M> inline M inverse33(const M& m, long) {          // cofactors times 1 / det
+template <class M> inline M inverse33(const M& m, long) {          // cofactors times 1 / det, in the matrix's own scalar type
+  using S = typename std::decay<decltype(m(0, 0))>::type;
   M r;
-  const float c00 = m(1, 1) * m(2, 2) - m(1, 2) * m(2, 1), c10 = m(1, 2) * m(2, 0) - m(1, 0) * m(2, 2), c20 = m(1, 0) * m(2, 1) - m(1, 1) * m(2, 0);
-  const float id = 1.f / (c00 * m(0, 0) + c10 * m(0, 1) + c20 * m(0, 2));
+  const S c00 = m(1, 1) * m(2, 2) - m(1, 2) * m(2, 1), c10 = m(1, 2) * m(2, 0) - m(1, 0) * m(2, 2), c20 = m(1, 0) * m(2, 1) - m(1, 1) * m(2, 0);
+  const S id = S(1) / (c00 * m(0, 0) + c10 * m(0, 1) + c20 * m(0, 2));
   r(0, 0) = c00 * id; r(1, 0) = c10 * id; r(2, 0) = c20 * id;
   r(0, 1) = (m(0, 2) * m(2, 1) - m(0, 1) * m(2, 2)) * id; r(1, 1) = (m(0, 0) * m(2, 2) - m(0, 2) * m(2, 0)) * id; r(2, 1) = (m(0, 1) * m(2, 0) - m(0, 0) * m(2, 1)) * id;
   r(0, 2) = (m(0, 1) * m(1, 2) - m(0, 2) * m(1, 1)) * id; r(1, 2) = (m(0, 2) * m(1, 0) - m(0, 0) * m(1, 2)) * id; r(2, 2) = (m(0, 0) * m(1, 1) - m(0, 1) * m(1, 0)) * id;
   return r;
 }
+// a new ImmaturePoint object whose members the caller fills in: the stand-in types are default-constructible; the reference's class
+// only has its two pixel constructors (ImmaturePoint.h:85-86), so the int one is used, which reads host->dI on the host and whose
+// results are then overwritten
+template <class P, class FrameHessianT, class CalibHessianT>
+inline P* newImmaturePoint(std::true_type, float, float, FrameHessianT*, float, CalibHessianT*) { return new P(); }
+template <class P, class FrameHessianT, class CalibHessianT>
+inline P* newImmaturePoint(std::false_type, float u, float v, FrameHessianT* host, float type, CalibHessianT* HCalib) { return new P((int)u, (int)v, host, type, HCalib); }
 }  // namespace detail
 
 template <class Mat33fT>
@@ -1217,6 +1226,120 @@ inline void marginalizeFrame(int nFrames, int idx, const double* prior8, const d
     throw Error("sdso_ba_marginalize_frame: bad arguments");
   HM.swap(Ho); bM.swap(bo);
 }
+
+// =================================================================================== the device-resident immature points
+// FullSystem::makeNewTraces (FullSystem.cpp:1600-1629), traceNewCoarseNonKey (:632-742) and traceNewCoarseKey (:745-781) with the
+// reference's signatures, on the set the library keeps on the device (sdso_imm_*): the three bodies no longer touch
+// host->immaturePoints.  The object stands for the FullSystem members the bodies read: Hcalib, frameHessians, pixelSelector,
+// setting_desiredImmatureDensity and the stereo baseline.  slot_of(frame) is the frame's pyramid slot on the device; a keyframe's slot
+// is also its host_id in the set.  download(host) rebuilds host->immaturePoints from the set (what activatePointsMT reads, per
+// keyframe); remove(host, flags) is STEP 5 for the entries STEP 2 / STEP 4 set to 0; release(host) goes where the reference deletes a
+// marginalized frame's immature points (and before stereoMatch deletes its temporary frame).  A frame of frameHessians without points in
+// the set is not traced, like the reference's empty loop.  The benchmark-only and debug branches of the three functions are not mirrored.
+// Mat33fT is the reference's Eigen float matrix type (element access (i, j)); products are formed row times column, summed left to right.
+template <class FrameHessianT, class CalibHessianT, class Mat33fT>
+class ImmaturePoints {
+ public:
+  using ImmaturePointT = typename std::remove_pointer<typename std::remove_reference<decltype(std::declval<FrameHessianT>().immaturePoints[0])>::type>::type;
+  ImmaturePoints(Device& dev, PixelSelector& pixelSelector, CalibHessianT& Hcalib, std::vector<FrameHessianT*>& frameHessians,
+                 std::function<int(const FrameHessianT*)> slot_of, float baseline, float setting_desiredImmatureDensity)
+      : dev_(dev), sel_(pixelSelector), Hcalib_(Hcalib), frameHessians_(frameHessians), slot_of_(std::move(slot_of)), baseline_(baseline),
+        density_(setting_desiredImmatureDensity) {}
+
+  // void FullSystem::makeNewTraces(FrameHessian* newFrame, FrameHessian* newFrameRight, float* gtDepth): the selection map stays on the
+  // device between makeMaps and the constructor loop.  Only enqueues after makeMaps; returns makeMaps' numPointsTotal.
+  int makeNewTraces(FrameHessianT* newFrame, FrameHessianT* /*newFrameRight*/, float* /*gtDepth*/) {
+    const int slot = slot_of_(newFrame);
+    const int numPointsTotal = sel_.makeMaps(slot, nullptr, density_);
+    dev_.check(sdso_imm_add_frame(dev_.ctx(), slot, slot, nullptr, nullptr), "sdso_imm_add_frame");
+    return numPointsTotal;
+  }
+  void traceNewCoarseNonKey(FrameHessianT* fh, FrameHessianT* fh_right) { trace_(fh, fh_right); }
+  void traceNewCoarseKey(FrameHessianT* fh, FrameHessianT* /*fh_right*/) { trace_(fh, nullptr); }
+
+  // the geometry of :654-665 for one host
+  sdso_imm_geom_t geomOf(const FrameHessianT* host, const FrameHessianT* fh) const {
+    Mat33fT K, Ki;
+    makeK(K, Ki);
+    const auto hostToNew = fh->PRE_worldToCam * host->PRE_camToWorld;
+    const auto R = hostToNew.rotationMatrix();
+    const auto t = hostToNew.translation();
+    const auto Ri = detail::inverse33(R, 0);   // hostToNew.rotationMatrix().inverse(), in double (:658)
+    float Rf[9], Rif[9], KR[9];
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) { Rf[i * 3 + j] = (float)R(i, j); Rif[i * 3 + j] = (float)Ri(i, j); }
+    sdso_imm_geom_t g;
+    g.host_id = slot_of_(host);
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) KR[i * 3 + j] = (K(i, 0) * Rf[j] + K(i, 1) * Rf[3 + j]) + K(i, 2) * Rf[6 + j];
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) g.KRKi[i * 3 + j] = (KR[i * 3] * Ki(0, j) + KR[i * 3 + 1] * Ki(1, j)) + KR[i * 3 + 2] * Ki(2, j);
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) g.KRi[i * 3 + j] = (K(i, 0) * Rif[j] + K(i, 1) * Rif[3 + j]) + K(i, 2) * Rif[6 + j];
+    for (int i = 0; i < 3; i++) { g.t[i] = (float)t[i]; g.Kt[i] = (K(i, 0) * (float)t[0] + K(i, 1) * (float)t[1]) + K(i, 2) * (float)t[2]; }
+    using AffLightT = typename std::decay<decltype(host->aff_g2l())>::type;
+    const auto aff = AffLightT::fromToVecExposure(host->ab_exposure, fh->ab_exposure, host->aff_g2l(), fh->aff_g2l());
+    g.aff[0] = (float)aff[0]; g.aff[1] = (float)aff[1];
+    return g;
+  }
+  int count(const FrameHessianT* host) const {
+    int n = 0;
+    dev_.check(sdso_imm_count(dev_.ctx(), slot_of_(host), &n), "sdso_imm_count");
+    return n;
+  }
+  // host->immaturePoints <- the set's points of this host, in the set's order (the old objects are deleted)
+  void download(FrameHessianT* host) {
+    const int n = count(host);
+    std::vector<float> us(n), vs(n), ty(n), imin(n), imax(n), col(n * 8), wgt(n * 8), gH(n * 4), eth(n), q(n), uv(n * 2), itv(n);
+    std::vector<uint8_t> lts(n);
+    sdso_trace_points_t P{n, us.data(), vs.data(), nullptr, imin.data(), imax.data(), nullptr, col.data(), wgt.data(), gH.data(), eth.data(),
+                          q.data(), lts.data(), uv.data(), itv.data()};
+    if (n) dev_.check(sdso_imm_get(dev_.ctx(), slot_of_(host), &P, ty.data()), "sdso_imm_get");
+    for (ImmaturePointT* p : host->immaturePoints) delete p;
+    host->immaturePoints.assign(n, nullptr);
+    for (int i = 0; i < n; i++) {
+      ImmaturePointT* p = detail::newImmaturePoint<ImmaturePointT>(std::is_default_constructible<ImmaturePointT>(), us[i], vs[i], host, ty[i], &Hcalib_);
+      p->host = host; p->idxInImmaturePoints = i;
+      p->u = us[i]; p->v = vs[i]; p->my_type = ty[i]; p->idepth_min = imin[i]; p->idepth_max = imax[i]; p->quality = q[i]; p->energyTH = eth[i];
+      p->lastTraceStatus = static_cast<decltype(p->lastTraceStatus)>(lts[i]);
+      p->lastTraceUV[0] = uv[2 * i]; p->lastTraceUV[1] = uv[2 * i + 1]; p->lastTracePixelInterval = itv[i];
+      for (int k = 0; k < 8; k++) { p->color[k] = col[i * 8 + k]; p->weights[k] = wgt[i * 8 + k]; }
+      p->gradH(0, 0) = gH[i * 4 + 0]; p->gradH(0, 1) = gH[i * 4 + 1]; p->gradH(1, 0) = gH[i * 4 + 2]; p->gradH(1, 1) = gH[i * 4 + 3];
+      host->immaturePoints[i] = p;
+    }
+  }
+  // STEP 5 (:948-957) on the device: flags[i] != 0 where STEP 2 / STEP 4 set host->immaturePoints[i] = 0
+  void remove(const FrameHessianT* host, const std::vector<uint8_t>& flags) {
+    dev_.check(sdso_imm_remove(dev_.ctx(), slot_of_(host), (int)flags.size(), flags.data()), "sdso_imm_remove");
+  }
+  void release(const FrameHessianT* host) { dev_.check(sdso_imm_release_host(dev_.ctx(), slot_of_(host)), "sdso_imm_release_host"); }
+
+  // K and K.inverse() of :639-645
+  void makeK(Mat33fT& K, Mat33fT& Ki) const {
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) K(i, j) = i == j ? 1.f : 0.f;
+    K(0, 0) = Hcalib_.fxl(); K(1, 1) = Hcalib_.fyl(); K(0, 2) = Hcalib_.cxl(); K(1, 2) = Hcalib_.cyl();
+    Ki = detail::inverse33(K, 0);
+  }
+
+ private:
+  void trace_(FrameHessianT* fh, FrameHessianT* fh_right) {
+    Mat33fT K, Ki;
+    makeK(K, Ki);
+    std::vector<sdso_imm_geom_t> geom;
+    // a frame without points in the set (the first frame, pushed by initializeFromInitializer without makeNewTraces, :1487-1500; a
+    // keyframe all of whose points are gone) is an empty loop in the reference: it is not named
+    for (FrameHessianT* host : frameHessians_)
+      if (count(host) > 0) geom.push_back(geomOf(host, fh));
+    if (geom.empty()) return;
+    const float K4[4] = {K(0, 0), K(1, 1), K(0, 2), K(1, 2)};
+    float Ki9[9];
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) Ki9[i * 3 + j] = Ki(i, j);
+    dev_.check(sdso_imm_trace(dev_.ctx(), slot_of_(fh), fh_right ? slot_of_(fh_right) : -1, (int)geom.size(), geom.data(), K4, Ki9, baseline_, nullptr),
+               "sdso_imm_trace");
+  }
+  Device& dev_;
+  PixelSelector& sel_;
+  CalibHessianT& Hcalib_;
+  std::vector<FrameHessianT*>& frameHessians_;
+  std::function<int(const FrameHessianT*)> slot_of_;
+  float baseline_, density_;
+};
 
 // =================================================================================== Undistort
 // class Undistort (util/Undistort.h:63-104) with the members DatasetReader and main touch: getK, getSize, getOriginalSize, getBl,

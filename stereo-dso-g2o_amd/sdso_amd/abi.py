@@ -138,6 +138,15 @@ class TraceGeom(C.Structure):
     _fields_ = [("KRKi", C.c_float * 9), ("Kt", C.c_float * 3), ("aff", C.c_float * 2)]
 
 
+class ImmGeom(C.Structure):
+    """sdso_imm_geom_t: the geometry of one host keyframe into the newest frame (FullSystem.cpp:654-665)."""
+    _fields_ = [("host_id", C.c_int), ("KRKi", C.c_float * 9), ("Kt", C.c_float * 3), ("aff", C.c_float * 2), ("KRi", C.c_float * 9), ("t", C.c_float * 3)]
+
+
+IMM_MAX_HOSTS = 8
+IMM_NCOUNTS = 10   # lastTraceStatus histogram [0..5], forward GOOD, stereo outliers, intervals updated, unreadable
+
+
 class Activate(C.Structure):
     _fields_ = [("nf", C.c_int), ("w", C.c_int), ("h", C.c_int), ("n", C.c_int), ("minObs", C.c_int), ("K", C.c_float * 4),
                 ("pair_R", c_float_p), ("pair_t", c_float_p), ("pair_aff", c_float_p), ("frame_slot", c_int_p), ("dI", C.POINTER(c_float_p)),
@@ -463,6 +472,13 @@ def load():
     L.sdso_ingest_calib_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, C.c_int, c_float_p, c_float_p, C.c_int, C.c_int]
     L.sdso_ingest_calib_release.argtypes = [vp, C.c_int]
     L.sdso_ingest_frame.argtypes = [vp, C.c_int, C.c_int, c_int_p, C.POINTER(vp), c_float_p, C.c_float, c_float_p]
+    L.sdso_imm_add_frame.argtypes = [vp, C.c_int, C.c_int, c_float_p, c_int_p]
+    L.sdso_imm_trace.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(ImmGeom), c_float_p, c_float_p, C.c_float, c_int_p]
+    L.sdso_imm_count.argtypes = [vp, C.c_int, c_int_p]
+    L.sdso_imm_get.argtypes = [vp, C.c_int, C.POINTER(TracePoints), c_float_p]
+    L.sdso_imm_remove_order.argtypes = [C.c_int, c_u8_p, c_int_p, c_int_p]
+    L.sdso_imm_remove.argtypes = [vp, C.c_int, C.c_int, c_u8_p]
+    L.sdso_imm_release_host.argtypes = [vp, C.c_int]
     _lib = L
     return L
 
@@ -489,6 +505,7 @@ EXPORTED_SYMBOLS = [
     "sdso_g2o_track_add_edges", "sdso_g2o_track_linearize", "sdso_g2o_track_newest_coarse", "sdso_g2o_lba_eval", "sdso_trace_set_gn_mode",
     "sdso_distmap_make", "sdso_distmap_add", "sdso_distmap_get", "sdso_activate_select",
     "sdso_undistort_make_remap", "sdso_ingest_calib_create", "sdso_ingest_calib_release", "sdso_ingest_frame",
+    "sdso_imm_add_frame", "sdso_imm_trace", "sdso_imm_count", "sdso_imm_get", "sdso_imm_remove_order", "sdso_imm_remove", "sdso_imm_release_host",
 ]
 
 
@@ -535,6 +552,20 @@ class Context:
         out = np.zeros(n, np.float32)
         self.check(self.L.sdso_ingest_frame(self.h, calib, n, (C.c_int * n)(*slots), ptrs, fp(ex), factor, fp(out)))
         return out
+
+    def imm_get(self, host_id):
+        """sdso_imm_get: one host's immature points as a dict of numpy arrays (the members of ImmaturePoint, in the set's order)."""
+        n = C.c_int(0)
+        self.check(self.L.sdso_imm_count(self.h, host_id, C.byref(n)))
+        n = n.value
+        P, d = make_trace_points(n, np.zeros(n), np.zeros(n), np.zeros((n, 8)), np.zeros((n, 8)), np.zeros((n, 4)), np.zeros(n))
+        P.idepth_min = None; P.idepth_stereo = None
+        my_type = np.zeros(n, np.float32)
+        self.check(self.L.sdso_imm_get(self.h, host_id, C.byref(P), fp(my_type)))
+        assert P.n == n
+        return dict(u=d["u_stereo"], v=d["v_stereo"], my_type=my_type, idepth_min=d["idepth_min_stereo"], idepth_max=d["idepth_max_stereo"],
+                    quality=d["quality"], color=d["color"], weights=d["weights"], gradH=d["gradH"], energyTH=d["energyTH"],
+                    lastTraceStatus=d["lastTraceStatus"], lastTraceUV=d["lastTraceUV"], lastTracePixelInterval=d["lastTracePixelInterval"])
 
     def upload_pyramid(self, slot, pyr):
         n = len(pyr)
