@@ -257,7 +257,8 @@ static int upload_window_impl(sdso_ctx* ctx, int win, const sdso_ba_window_t* Wi
   SDSO_REQUIRE(ctx, Win, "null window");
   const int nf = Win->nf, np = Win->np, nr = Win->nr;
   SDSO_REQUIRE(ctx, nf >= 1 && nf <= 8 && np >= 0 && nr >= 0, "window sizes out of range (nf <= 8: setting_maxFrames is 7, settings.cpp:65)");
-  SDSO_REQUIRE(ctx, (size_t)((Win->w + 3) / 4) * (size_t)((Win->h + 1) / 2) * 128 < (size_t)sdso::TAP_RANGE,
+  static_assert(TILE0_MAX_BYTES == (size_t)sdso::TAP_RANGE, "the tiled image has to fit the taps' buffer descriptor");
+  SDSO_REQUIRE(ctx, Win->w >= 1 && Win->h >= 1 && tile0_bytes(Win->w, Win->h) < TILE0_MAX_BYTES,
                "image size out of range (k_ba_lin_fused reads a tiled level-0 image through a 2 GiB buffer descriptor with 32-bit offsets)");
   SDSO_REQUIRE(ctx, Win->evalPT && Win->state && Win->state_zero && Win->ab_exposure && Win->frameEnergyTH && Win->frameID && Win->frame_slot, "null frame arrays");
   SDSO_REQUIRE(ctx, np == 0 || (Win->u && Win->v && Win->idepth && Win->idepth_zero && Win->color && Win->weights && Win->host && Win->hasDepthPrior), "null point arrays");
@@ -295,7 +296,7 @@ static int upload_window_impl(sdso_ctx* ctx, int win, const sdso_ba_window_t* Wi
   for (int i = 0; i < 4; i++) W->calib.value_zero[i] = Win->calib_value_zero[i];
   W->calib.setValueScaled(Win->calib_value_scaled);
   W->frames.resize(nf);
-  std::vector<const float4*> imgs(nf);
+  std::vector<const char*> imgs(nf);
   for (int f = 0; f < nf; f++) {
     HostFrame& F = W->frames[f];
     std::memcpy(F.evalPT.R.data(), Win->evalPT + f * 12, 72);
@@ -308,7 +309,7 @@ static int upload_window_impl(sdso_ctx* ctx, int win, const sdso_ba_window_t* Wi
     auto ip = ctx->pyr.find(F.frame_slot);
     SDSO_REQUIRE(ctx, ip != ctx->pyr.end(), "window references a frame slot without an uploaded pyramid");
     SDSO_REQUIRE(ctx, ip->second.w[0] == Win->w && ip->second.h[0] == Win->h, "pyramid level-0 size differs from the window's w/h");
-    int rc = ensure_tiled0(ctx, ip->second);   // 4x2-tiled level-0 images for the linearisation
+    int rc = ensure_tiled0(ctx, ip->second);   // 5x2-tiled 12-byte level-0 images for the linearisation
     if (rc) return rc;
     imgs[f] = ip->second.tiled0;
   }
@@ -429,7 +430,7 @@ static int upload_window_impl(sdso_ctx* ctx, int win, const sdso_ba_window_t* Wi
   PL(W->dt_prior, double, nf * 16 + 4 + n, true); PL(W->d_self, BaDev, 1, true);
   PL(W->dt_frameTH, float, nf, true);
   PL(W->dt_HM, double, (size_t)n * n, true); PL(W->dt_bM, double, n, true); PL(W->dt_xAd, float, nf * nf * 8, false);
-  const float4** d_img; PL(d_img, const float4*, nf, true);
+  const char** d_img; PL(d_img, const char*, nf, true);
   int4* d_chunks; int* d_pair_beg; int4* d_items; int* d_host_beg;
   PL(d_chunks, int4, chunks.size(), true); PL(d_pair_beg, int, nf * nf + 1, true); PL(d_items, int4, items.size(), true); PL(d_host_beg, int, nf + 1, true);
   PL(d.top_part, double, (size_t)d.nchunks * 92, false); PL(d.sc_part, float, (size_t)nf * 20, false);
@@ -470,7 +471,7 @@ static int upload_window_impl(sdso_ctx* ctx, int win, const sdso_ba_window_t* Wi
   d.p_rbeg = p_rbeg; d.p_rcnt = p_rcnt; d.p_rlist = p_rlist; d.p_out = p_out;
   d.p_order = p_order; d.p_track = p_track; d.r_isnew = r_isnew;
   d.r_point = r_point; d.r_orig = r_orig; d.r_host = r_host; d.r_target = r_target;
-  d.tiledT = (Win->w + 3) / 4;
+  d.tiledT = tile0_tiles_per_row(Win->w);
   d.t_precalc = W->dt_precalc; d.t_adHTdelta = W->dt_adHTdelta; d.t_cdelta = W->dt_cdelta; d.t_frameTH = W->dt_frameTH; d.t_img = d_img;
   d.t_adHost = W->dt_adHost; d.t_adTarget = W->dt_adTarget; d.t_xAd = W->dt_xAd; d.t_prior = W->dt_prior; d.t_HM = W->dt_HM; d.t_bM = W->dt_bM; d.t_P = W->dt_P;
   d.chunks = d_chunks; d.pair_chunk_beg = d_pair_beg; d.items = d_items; d.host_item_beg = d_host_beg;
@@ -508,7 +509,7 @@ static int upload_window_impl(sdso_ctx* ctx, int win, const sdso_ba_window_t* Wi
   STG(p_rbeg, rbeg.data(), sizeof(int) * (np + 1)); STG(p_rcnt, rcnt.data(), sizeof(int) * np); STG(p_rlist, rlist.data(), sizeof(int) * nr);
   STG(p_order, order.data(), sizeof(unsigned) * np); STG(p_track, track.data(), sizeof(float4) * np); STG(r_isnew, isnew.data(), nr);
   STG(r_point, s_point.data(), sizeof(int) * nr); STG(r_orig, W->perm.data(), sizeof(int) * nr); STG(r_host, s_host.data(), nr); STG(r_target, s_target.data(), nr); STG(d.r_state, s_state.data(), nr);
-  STG(W->dt_frameTH, frameTH.data(), sizeof(float) * nf); STG(d_img, imgs.data(), sizeof(float4*) * nf);
+  STG(W->dt_frameTH, frameTH.data(), sizeof(float) * nf); STG(d_img, imgs.data(), sizeof(char*) * nf);
   STG(d_chunks, chunks.data(), sizeof(int4) * chunks.size()); STG(d_pair_beg, pair_beg.data(), sizeof(int) * (nf * nf + 1));
   STG(d_items, items.data(), sizeof(int4) * items.size()); STG(d_host_beg, host_beg.data(), sizeof(int) * (nf + 1));
   STG(W->dt_HM, W->HM.data(), sizeof(double) * n * n); STG(W->dt_bM, W->bM.data(), sizeof(double) * n);
@@ -633,9 +634,10 @@ static bool launch_sc_and_folds(sdso_ctx* ctx, const BaLaunch& L, const uint8_t*
 static bool launch_fused(sdso_ctx* ctx, const BaLaunch& L, bool materialize, int part = 3 /* bit 0: linearize+top, bit 1: Schur+folds */, bool defer_fold = false) {
   const int nf = L.nf;
   if ((part & 1) && L.max_chunks > 0) {
-    const dim3 g(L.max_chunks, L.nwin), b(BA_BLOCK);
-    if (materialize) launch_timed(ctx, "k_ba_lin_fused", 1, k_ba_lin_fused<true>, g, b, (const BaDev*)L.d_arr);
-    else launch_timed(ctx, "k_ba_lin_fused", 1, k_ba_lin_fused<false>, g, b, (const BaDev*)L.d_arr);
+    // a linear grid: the kernel deals (window, chunk) out so that a window's chunks share one XCD (k_ba_lin_fused)
+    const dim3 g((unsigned)((L.nwin + 7) / 8 * 8 * L.max_chunks)), b(BA_BLOCK);
+    if (materialize) launch_timed(ctx, "k_ba_lin_fused", 1, k_ba_lin_fused<true>, g, b, (const BaDev*)L.d_arr, (int)L.nwin, (int)L.max_chunks);
+    else launch_timed(ctx, "k_ba_lin_fused", 1, k_ba_lin_fused<false>, g, b, (const BaDev*)L.d_arr, (int)L.nwin, (int)L.max_chunks);
     if (L.any_lin) {
       hipLaunchKernelGGL(k_ba_fold_top, dim3(nf * nf, L.nwin), dim3(128), 0, ctx->stream, L.d_arr, 0);
       hipLaunchKernelGGL(k_ba_accum_top, dim3(L.max_chunks, L.nwin), dim3(BA_BLOCK), 0, ctx->stream, L.d_arr, 1, (const uint8_t*)nullptr);

@@ -87,7 +87,7 @@ struct BaOptDev {
 
 struct BaDev {
   int nf, np, nr, nrp, w, h, nchunks, nitems, n;
-  int tiledT;               // t_img are 4x2-tiled level-0 images with tiledT tiles per row
+  int tiledT;               // t_img are level-0 images of 12-byte pixels in 5x2 tiles (tile0_layout.h) with tiledT tiles (128-B lines) per row
   float wM3, hM3, fxl, fyl, cxl, cyl, fxli, fyli;
   int affA_fixed, affB_fixed;
   int jfix;                 // 1 (default): the fused kernel refreshes EFResidual::J IN PLACE (J[jsel]) instead of writing the other buffer and
@@ -140,7 +140,7 @@ struct BaDev {
   const float* t_adHTdelta; // [h+t*nf][8]
   const float* t_cdelta;    // 4
   float* t_frameTH;         // nf
-  const float4* const* t_img;  // nf level-0 images
+  const char* const* t_img;  // nf tiled level-0 images (PyramidDev::tiled0)
   const double* t_adHost; const double* t_adTarget;  // [h+t*nf][64]
   const float* t_xAd;       // [h*nf+t][8]  (resubstitute)
   const double* t_prior;    // nf*8 prior, nf*8 delta_prior, 4 cPrior, then delta (4+8nf)

@@ -47,17 +47,19 @@ __host__ __device__ constexpr int jdev(int f) {
 #define JV(f) jl[jdev(f)]
 typedef float te_f4 __attribute__((ext_vector_type(4)));
 
-// getInterpolatedElement33 on the 4x2-tiled level-0 image: the four taps of a sample and the samples of one 8-pixel pattern
-// fall into fewer 128-B lines than in the row-major image (6.4 instead of 8.3 per residual on average), the arithmetic is
-// the same expression as interp33
-__device__ __forceinline__ float3 interp33_tiled(const float4* __restrict__ img, float x, float y, int T) {
+// getInterpolatedElement33 on the tiled level-0 image (12-byte pixels in 5x2 tiles, tile0_layout.h): the four taps of a sample and the
+// samples of one 8-pixel pattern fall into fewer 128-B lines than in the row-major float4 image (5.7 instead of 8.3 per residual
+// on average; 16-byte pixels in 4x2 tiles: 6.25-6.4; profiles/lin_tiles_ab.txt), the arithmetic is the same expression as interp33
+struct tile0_px { float x, y, z; };
+__device__ __forceinline__ tile0_px tile0_load(const char* __restrict__ img, int x, int y, int T) { return *(const tile0_px*)(img + tile0_offset(x, y, T)); }
+__device__ __forceinline__ float3 interp33_tiled(const char* __restrict__ img, float x, float y, int T) {
   const int ix = (int)x;
   const int iy = (int)y;
   const float dx = x - ix;
   const float dy = y - iy;
   const float dxdy = dx * dy;
-  const float4 p00 = img[tiled_index(ix, iy, T)], p10 = img[tiled_index(ix + 1, iy, T)], p01 = img[tiled_index(ix, iy + 1, T)],
-               p11 = img[tiled_index(ix + 1, iy + 1, T)];
+  const tile0_px p00 = tile0_load(img, ix, iy, T), p10 = tile0_load(img, ix + 1, iy, T), p01 = tile0_load(img, ix, iy + 1, T),
+                 p11 = tile0_load(img, ix + 1, iy + 1, T);
   const float w11 = dxdy, w01 = dy - dxdy, w10 = dx - dxdy, w00 = 1 - dx - dy + dxdy;
   float3 r;
   r.x = w11 * p11.x + w01 * p01.x + w10 * p10.x + w00 * p00.x;
@@ -89,7 +91,7 @@ __device__ __forceinline__ double linearize_one(const BaDev& B, int i, int h, in
   const float affLL0 = pre[24], affLL1 = pre[25], b0 = pre[26];
   const float4 g = B.p_geo[pt];
   const float pu = g.x, pv = g.y, idepth_scaled = g.z, idepth_zero_scaled = g.w;
-  const float4* __restrict__ dIl = B.t_img[t];
+  const char* __restrict__ dIl = B.t_img[t];
   float* __restrict__ J = STORE ? (B.r_jsel[i] != 0 ? B.J[0] : B.J[1]) : nullptr;   // PointFrameResidual::J: the slot EFResidual::J is not in
   const int S = B.nrp;
   const float fxl = B.fxl, fyl = B.fyl, cxl = B.cxl, cyl = B.cyl, fxli = B.fxli, fyli = B.fyli;
@@ -277,7 +279,7 @@ __device__ __forceinline__ void coop_gather_hits(tap_rsrc_t img /* wave-uniform:
       const int x = (int)cx[r].x + (c & 1), y = (int)cx[r].y + (c >> 1);
       // a dead residual's lanes ask for an offset beyond the descriptor's range: the hardware returns zeros and touches no memory (no branch
       // around the load, so no wait inside one)
-      const u32x3 q = __builtin_amdgcn_raw_buffer_load_b96(img, cx[r].x >= 0 ? (unsigned)tiled_index(x, y, T) * 16u : TAP_OFF_DEAD, 0, 0);
+      const u32x3 q = __builtin_amdgcn_raw_buffer_load_b96(img, cx[r].x >= 0 ? tile0_offset(x, y, T) : TAP_OFF_DEAD, 0, 0);
       qx[r] = __uint_as_float(q.x); qy[r] = __uint_as_float(q.y); qz[r] = __uint_as_float(q.z);
     }
     vm_wait_all();
@@ -684,8 +686,7 @@ typedef double te_d4 __attribute__((ext_vector_type(4)));
 static_assert(TE_LDS_FLOATS * 4 >= ((BA_BLOCK / 64) * 256 + BA_BLOCK / 64) * 8, "the waves' f64 tiles lie over the panels");
 
 __device__ __forceinline__ void top_emit(const BaDev& B, const float* x, const float* y, float a, float b, float c, float TR00, float TR10, float TR01,
-                                         float TR11, float TR02, float TR12, const float* br, bool on, float* stage) {
-  const int chunk = blockIdx.x;
+                                         float TR11, float TR02, float TR12, const float* br, bool on, float* stage, int chunk) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   float* S = stage + wv * TE_WAVE_FLOATS;
   const int m = lane & 15, kq = lane >> 4;
@@ -818,7 +819,7 @@ __global__ __launch_bounds__(BA_BLOCK) void k_ba_accum_top(const BaDev* __restri
 #pragma unroll
     for (int k = 0; k < 4; k++) rec[RR_HCD + k] = x[k] * q0 + y[k] * q1;
   }
-  top_emit(B, x, y, a, b, c, TR00, TR10, TR01, TR11, TR02, TR12, br, on, red);
+  top_emit(B, x, y, a, b, c, TR00, TR10, TR01, TR11, TR02, TR12, br, on, red, blockIdx.x);
 }
 
 // ------------------------------------------------------------------ fused linearize + applyRes + accumulate (mode 0)
@@ -844,20 +845,28 @@ __global__ __launch_bounds__(BA_BLOCK) void k_ba_accum_top(const BaDev* __restri
 // The workgroup barriers behind the linearisation exchange data through LDS only (the gather stage handed over to the reduction's panels, the
 // energy sum, the waves' tiles); the first stands behind the record stores, which touch no LDS.
 template <bool MATERIALIZE>
-__global__ __launch_bounds__(BA_BLOCK, 4) void k_ba_lin_fused(const BaDev* __restrict__ wins) {
+__global__ __launch_bounds__(BA_BLOCK, 4) void k_ba_lin_fused(const BaDev* __restrict__ wins, int nwin, int max_chunks) {
+  // XCD-aware mapping (as k_track_eval, tracker.hip): linear workgroup id L runs on XCD (L % 8); every chunk of window `win` gets the same
+  // residue, so ONE L2 serves the window's points (a point's 80 bytes are read by its ~6.5 residuals, which sit in different chunks) and
+  // the image lines that the chunks of one target share.  The grid is ceil(nwin / 8) * 8 * max_chunks workgroups: (win, chunk) <-> L is
+  // one-to-one, and the ids of the windows that round nwin up to a multiple of 8 leave here.  Speed only; any placement is correct.
+  // (-2.0 % on the 256-window step, alone and on top of the 5x2 tiles: profiles/lin_tiles_ab.txt)
+  const int L = blockIdx.x;
+  const int win = ((L >> 3) / max_chunks) * 8 + (L & 7);
+  const int chunk = (L >> 3) % max_chunks;
+  if (win >= nwin) return;
   // by-value copy: the descriptor's fields come in through s_load and stay in SGPRs.  Its pointers are still generic ones to the compiler;
   // every access below says "global" (gld / gst) or "uniform" (uld) itself, ba_kernels.h
-  const BaDev B = wins[blockIdx.y];
+  const BaDev B = wins[win];
   if (ba_finished_lin(B)) return;
-  if ((int)blockIdx.x >= B.nchunks) return;
+  if (chunk >= B.nchunks) return;
   constexpr int STAGE_FLOATS = (BA_BLOCK / 64) * CG_WAVE_FLOATS;
   constexpr int RED_FLOATS = TE_LDS_FLOATS > STAGE_FLOATS ? TE_LDS_FLOATS : STAGE_FLOATS;
   __shared__ float red[RED_FLOATS];    // the gather stage of the linearisation, then the MFMA panels of the reduction
   double* const lds = (double*)red;    // (the energy reduction runs between the two uses; 40 KB in all = four workgroups per CU)
-  const int chunk = blockIdx.x;
   // One (host,target) pair per workgroup: the chunk, the pair's 27 precalc floats, the target's image pointer and the two frames' thresholds
   // are wave-uniform and written by earlier kernels only — requested once, here, through the scalar cache
-  const i32x4 ch = uld((const i32x4*)(B.chunks + blockIdx.x));
+  const i32x4 ch = uld((const i32x4*)(B.chunks + chunk));
   const int pair = ch.x;
   const int h = pair % B.nf, t = pair / B.nf;
   float pre[27];
@@ -954,7 +963,7 @@ __global__ __launch_bounds__(BA_BLOCK, 4) void k_ba_lin_fused(const BaDev* __res
   e = block_sum_d(e, lds);
   if (threadIdx.x == 0) gst(B.e_part + chunk, e);
   __syncthreads();
-  top_emit(B, x, y, a, b, c, TR00, TR10, TR01, TR11, TR02, TR12, br, on, red);
+  top_emit(B, x, y, a, b, c, TR00, TR10, TR01, TR11, TR02, TR12, br, on, red, chunk);
 }
 
 // ------------------------------------------------------------------ linearised energy (EnergyFunctional::calcLEnergyPt, EnergyFunctional.cpp:354-417)

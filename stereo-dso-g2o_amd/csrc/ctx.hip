@@ -74,9 +74,20 @@ __global__ void k_gradients(float4* __restrict__ img, int wl, int hl, const floa
   img[idx].w = abs_grad(img[idx].x, dx, dy, B);   // absSquaredGrad (:192) times the squared response gradient (:194-198)
 }
 
-__global__ void k_tile0(const float4* __restrict__ src, float4* __restrict__ dst, int w, int h, int T) {
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-  if (x < w && y < h) dst[tiled_index(x, y, T)] = src[x + y * w];
+// One thread per 4-byte word of the tiled copy (tile0_layout.h), so every byte of the allocation is written: the three channels of the
+// pixels inside the image, zeros for the pixels of partial edge tiles and for the two pad words of every line.
+__global__ void k_tile0(const float4* __restrict__ src, float* __restrict__ dst, int w, int h, int T, size_t nwords) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nwords) return;
+  const size_t tile = i >> 5;
+  const int j = (int)(i & 31), ty = (int)(tile / (size_t)T), tx = (int)(tile - (size_t)ty * T);
+  float v = 0.f;
+  if (j < 30) {
+    const int row = j / 15, k = j - 15 * row, px = k / 3, ch = k - 3 * px;
+    const int x = tx * sdso::TILE0_W + px, y = ty * sdso::TILE0_H + row;
+    if (x < w && y < h) v = ((const float*)(src + (x + (size_t)y * w)))[ch];
+  }
+  dst[i] = v;
 }
 __global__ void k_plane0(const float4* __restrict__ src, float* __restrict__ dst, int npix) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -94,9 +105,11 @@ int ensure_plane0(sdso_ctx* ctx, PyramidDev& P) {
 }
 int ensure_tiled0(sdso_ctx* ctx, PyramidDev& P) {
   if (P.tiled_ok) return SDSO_OK;
-  const int w = P.w[0], h = P.h[0], T = (w + 3) / 4, Th = (h + 1) / 2;
-  if (!P.tiled0) SDSO_HIP(ctx, hipMalloc(&P.tiled0, sizeof(float4) * 8 * (size_t)T * Th));
-  hipLaunchKernelGGL(k_tile0, dim3((w + 255) / 256, h), dim3(256), 0, ctx->stream, (const float4*)P.d[0], P.tiled0, w, h, T);
+  const int w = P.w[0], h = P.h[0];
+  const size_t bytes = tile0_bytes(w, h), nwords = bytes / 4;
+  if (!P.tiled0) SDSO_HIP(ctx, hipMalloc(&P.tiled0, bytes));
+  hipLaunchKernelGGL(k_tile0, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)P.d[0], (float*)P.tiled0, w, h,
+                     tile0_tiles_per_row(w), nwords);
   SDSO_HIP(ctx, hipGetLastError());
   P.tiled_ok = true;
   return SDSO_OK;

@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 #include "../../include/sdso_abi.h"
+#include "tile0_layout.h"
 
 namespace sdso {
 
@@ -28,8 +29,9 @@ struct PyramidDev {
   int levels = 0;
   int w[SDSO_PYR_LEVELS] = {0}, h[SDSO_PYR_LEVELS] = {0};
   float4* d[SDSO_PYR_LEVELS] = {nullptr};
-  // level 0 once more in 4x2-pixel tiles (one 128-B line per tile) for the BA linearisation, built on first use
-  float4* tiled0 = nullptr;
+  // level 0 once more as 12-byte pixels {I, dx, dy} in 5x2-pixel tiles (one 128-B line per tile, tile0_layout.h) for the BA
+  // linearisation, built on first use
+  char* tiled0 = nullptr;
   bool tiled_ok = false;
   // level-0 intensities alone (4 B per pixel) for the discrete epipolar search, which samples I only; built on first use
   float* plane0 = nullptr;
@@ -202,8 +204,6 @@ int ensure_tiled0(sdso_ctx* ctx, PyramidDev& P);   // ctx.hip
 int ensure_plane0(sdso_ctx* ctx, PyramidDev& P);   // ctx.hip
 int pyramid_prepare(sdso_ctx* ctx, int frame_slot, int w, int h, PyramidDev** out);   // ctx.hip
 int pyramid_finish_levels(sdso_ctx* ctx, PyramidDev& P);                              // ctx.hip
-// pixel (x, y) of a 4x2-tiled level-0 image with T tiles per row
-__host__ __device__ inline int tiled_index(int x, int y, int T) { return (((y >> 1) * T + (x >> 2)) << 3) + ((y & 1) << 2) + (x & 3); }
 
 // ------------------------------------------------------------------ device helpers
 // getInterpolatedElement33 (src/util/globalFuncs.h:73-86) on the float4 image.
