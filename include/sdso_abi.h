@@ -816,6 +816,70 @@ int sdso_imm_remove(sdso_ctx* ctx, int host_id, int n, const uint8_t* flags);
  * error */
 int sdso_imm_release_host(sdso_ctx* ctx, int host_id);
 
+/* The inverse of sdso_imm_get: installs the n = pts->n points of host_id from host arrays in sdso_imm_get's convention (u_stereo /
+ * v_stereo = u / v, idepth_min_stereo / idepth_max_stereo = idepth_min / idepth_max; pts->idepth_min and pts->idepth_stereo are not read)
+ * plus my_type, for a host image of w x h.  For a caller that switches to the resident set in mid-run or made the points on the host.
+ * n = 0 installs an empty group.  SDSO_ERR_ARG for a host_id that already has points, a null member with n > 0, or w, h < 16. */
+int sdso_imm_put_host(sdso_ctx* ctx, int host_id, int w, int h, const sdso_trace_points_t* pts, const float* my_type);
+
+/* FullSystem::activatePointsMT STEP 2-5 (FullSystem.cpp:837-957) on the set, in place, after sdso_distmap_make (STEP 1 and
+ * makeDistanceMap stay with the caller).  The candidates are the points of frames 0 .. nf-2 concatenated in frame order, each group in
+ * its set order; the group of the newest frame (the last one), if it has one, is neither walked nor changed.
+ *   STEP 2 (:845-901)  sdso_activate_select's rules and contract per candidate: the gates, then the distance test and addIntoDistFinal in
+ *                      candidate order on the ctx's map; the re-grown map is left in the ctx
+ *   STEP 3 (:907-917)  every SELECTed candidate goes through optimizeImmaturePoint (FullSystemOptPoint.cpp:52-238) against the other
+ *                      nf-1 frames at pyramid level 0: the status, currentIdepth and ResStates of sdso_activate_points_batch
+ *   STEP 4 (:919-945)  an entry leaves the set if STEP 2 decided DELETE, or it was selected and its status is 1 or -1, or it was
+ *                      selected with status 0 and its lastTraceStatus is IPS_OOB; a selected entry with status 0 that is not OOB stays
+ *   STEP 5 (:948-957)  every walked group is compacted in the order sdso_imm_remove_order defines, computed on the device
+ * One enqueue of the whole chain, one copy of the results back and one synchronisation (a second copy only past
+ * SDSO_IMM_ACT_FIRST_COPY selected points).
+ *   host_id[f]      : the group of frame f in the set; a frame without a group has no candidates (not an error)
+ *   frame_slot[f]   : pyramid slots, level 0 is read
+ *   host_flagged[f] : FrameHessian::flaggedForMarginalization
+ *   geom[f]         : KRKi / Kt of frame f into the newest (:841-842), f < nf-1
+ *   pair_R/t/aff    : host->targetPrecalc[target->idx] PRE_RTll / PRE_tTll / PRE_aff_mode, indexed host*nf+target, as in sdso_activate_t
+ *   minObs          : the reference passes 1 (FullSystem.cpp:790)
+ *   counts          : SDSO_IMM_ACT_NCOUNTS ints (may be NULL): [0] candidates, [1..3] STEP 2 decisions KEEP / DELETE / SELECT,
+ *                     [4] toOptimize.size(), [5..7] statuses -1 / 0 / 1, [8] entries removed in STEP 4, [9 + f] the new count of frame
+ *                     f's group (0 without a group, unused entries 0)
+ * Refused before any device work, the set and the map left as they were: SDSO_ERR_STATE without a map; SDSO_ERR_ARG for nf outside
+ * 2..8, a host_id named twice, an unknown frame_slot, a pyramid or a group of another size than w x h, w>>1, h>>1 other than the map's. */
+#define SDSO_IMM_ACT_NCOUNTS 17
+#define SDSO_IMM_ACT_FIRST_COPY 1024
+typedef struct {
+  int nf;                            /* frames of the window in frameHessians order, 2..8; the last one is the newest */
+  const int* host_id;
+  const int* frame_slot;
+  const uint8_t* host_flagged;
+  const sdso_distmap_geom_t* geom;   /* nf-1 */
+  const float* pair_R; const float* pair_t; const float* pair_aff;   /* nf*nf */
+  int w, h;
+  float K[4];                        /* fxl fyl cxl cyl */
+  int minObs;
+  float currentMinActDist;           /* after STEP 1 (:798-817) */
+  float minTraceQuality;             /* setting_minTraceQuality = 3 (settings.cpp:112) */
+} sdso_imm_activate_t;
+int sdso_imm_activate(sdso_ctx* ctx, const sdso_imm_activate_t* A, int* counts);
+
+/* The results of the latest sdso_imm_activate of this ctx, kept by the library until the next one (SDSO_ERR_STATE before the first).
+ * One entry per selected candidate in toOptimize order, n = counts[4]; arrays are caller-owned, null members are skipped, out->n and
+ * out->nf are set.
+ *   frame, index : the candidate's frame and idxInImmaturePoints, its index in the group BEFORE the removal
+ *   status, idepth, res_state[n * nf] : as sdso_activate_points_batch (255 for the host itself / not evaluated)
+ *   u .. weights : the members PointHessian::PointHessian(const ImmaturePoint*, ...) copies (HessianBlocks.cpp:35-70)
+ *   decision     : the STEP 2 decision of every candidate (counts[0] bytes: 0 KEEP, 1 DELETE, 2 SELECT), may be NULL */
+typedef struct {
+  int n, nf;
+  int* frame; int* index;
+  int8_t* status; float* idepth; uint8_t* res_state;
+  float* u; float* v; float* my_type; float* idepth_min; float* idepth_max; float* energyTH;
+  float* color;      /* n*8 */
+  float* weights;    /* n*8 */
+  uint8_t* lastTraceStatus;
+} sdso_imm_activated_t;
+int sdso_imm_activate_fetch(sdso_ctx* ctx, sdso_imm_activated_t* out, uint8_t* decision);
+
 /* ------------------------------------------------------------------ the fork's live g2o factors
  * gyubeomim/stereo-dso-g2o routes tracking, window optimisation and the sub-pixel trace refinement through g2o edges
  * (src/FullSystem/dso_g2o_edge.cpp, dso_g2o_vertex.cpp).  The edges' own arithmetic is specified by the reference tree and

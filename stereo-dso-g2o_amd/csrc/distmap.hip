@@ -9,6 +9,7 @@
 //   k_distmap_select : the order-dependent rest (:889-895): one workgroup holds the whole map in LDS, one wave walks the candidates in
 //                      order, 64 at a time, and re-grows the map around every selected pixel as addIntoDistFinal does (:1366-1372)
 #include "sdso_internal.h"
+#include "distmap_dev.h"
 #include <cmath>
 #include <cstring>
 
@@ -23,7 +24,6 @@ constexpr int DM_WIN = 2 * DM_R + 1;        // 79: an insert never leaves the 79
 constexpr int DM_LDS_MAP = 144 * 1024;      // the selection kernel keeps maps up to this many pixels in LDS (616x184 = 113 344)
 constexpr uint8_t DM_FAR = 255;             // untouched (1000 in the reference)
 constexpr uint8_t DM_OUTSIDE = 254;         // halo pixel outside the image: never assigned, never propagates
-enum { DM_KEEP = 0, DM_DELETE = 1, DM_SELECT = 2, DM_PENDING = 3 };
 
 struct DistMapState {
   int w1 = 0, h1 = 0;
@@ -39,20 +39,6 @@ void release_distmap(sdso_ctx* ctx) {
   if (ctx->dm->map) hipFree(ctx->dm->map);
   delete ctx->dm;
   ctx->dm = nullptr;
-}
-
-// KRKi * (u, v, 1) + Kt * idepth in the unfused left-to-right order of Eigen's 3x3 product, then the rounding of
-// CoarseTracker.cpp:1243-1246 / FullSystem.cpp:884-887.  A quotient that is not finite or does not fit an int is "outside".
-__device__ __forceinline__ bool dm_project(const sdso_distmap_geom_t& g, float u, float v, float idepth, int w1, int h1, int& iu, int& iv, float& ptp0) {
-  const float p0 = ((g.KRKi[0] * u + g.KRKi[1] * v) + g.KRKi[2] * 1.f) + g.Kt[0] * idepth;
-  const float p1 = ((g.KRKi[3] * u + g.KRKi[4] * v) + g.KRKi[5] * 1.f) + g.Kt[1] * idepth;
-  const float p2 = ((g.KRKi[6] * u + g.KRKi[7] * v) + g.KRKi[8] * 1.f) + g.Kt[2] * idepth;
-  const float qx = p0 / p2 + 0.5f, qy = p1 / p2 + 0.5f;
-  ptp0 = p0;
-  if (!(qx > -2.0e9f && qx < 2.0e9f && qy > -2.0e9f && qy < 2.0e9f)) return false;
-  iu = (int)qx;
-  iv = (int)qy;
-  return iu > 0 && iv > 0 && iu < w1 && iv < h1;
 }
 
 __global__ __launch_bounds__(256) void k_distmap_seed(int n, const sdso_distmap_geom_t* __restrict__ geom, const int* __restrict__ pg, const float* __restrict__ u,
@@ -125,32 +111,25 @@ struct SelDev {
   int *iu, *iv;
   float *frac, *thr;
 };
+// one candidate of the uploaded arrays, for dm_classify
+struct SelCand {
+  const SelDev& S; int i, g;
+  __device__ uint8_t status() const { return S.status[i]; }
+  __device__ float imax() const { return S.imax[i]; }
+  __device__ float imin() const { return S.imin[i]; }
+  __device__ float interval() const { return S.interval[i]; }
+  __device__ float quality() const { return S.quality[i]; }
+  __device__ bool flagged() const { return S.flagged[g] != 0; }
+  __device__ const sdso_distmap_geom_t& geom() const { return S.geom[g]; }
+  __device__ float u() const { return S.u[i]; }
+  __device__ float v() const { return S.v[i]; }
+};
 __global__ __launch_bounds__(256) void k_select_classify(SelDev S) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= S.n) return;
-  const uint8_t st = S.status[i];
-  const float imax = S.imax[i], imin = S.imin[i];
   int iu = 0, iv = 0;
   float frac = 0.f;
-  uint8_t d;
-  if (!isfinite(imax) || st == 2 /* IPS_OUTLIER */) {
-    d = DM_DELETE;                                                                   // :850-856
-  } else {
-    const bool can = (st == 0 || st == 3 || st == 4 || st == 1) && S.interval[i] < 8 && S.quality[i] > S.minTraceQuality && (imax + imin) > 0;   // :860-866
-    const int g = S.pg[i];
-    if (!can) {
-      d = (S.flagged[g] || st == 1 /* IPS_OOB */) ? DM_DELETE : DM_KEEP;             // :869-880
-    } else {
-      float p0;
-      if (dm_project(S.geom[g], S.u[i], S.v[i], 0.5f * (imax + imin), S.w1, S.h1, iu, iv, p0)) {   // :883-887
-        frac = p0 - floorf(p0);                                                      // :889 — ptp[0], not the quotient
-        d = DM_PENDING;
-      } else {
-        d = DM_DELETE;                                                               // :897-900
-      }
-    }
-  }
-  S.dec[i] = d;
+  S.dec[i] = dm_classify(SelCand{S, i, S.pg[i]}, S.minTraceQuality, S.w1, S.h1, iu, iv, frac);
   S.iu[i] = iu;
   S.iv[i] = iv;
   S.frac[i] = frac;
@@ -298,7 +277,7 @@ struct Stage {
   size_t add(size_t b) { const size_t o = bytes; bytes += (b + 15) & ~(size_t)15; return o; }
 };
 
-static int dm_run_select(sdso_ctx* ctx, int n, uint8_t* dec, const int* iu, const int* iv, const float* frac, const float* thr, int mode_add, int* n_selected) {
+int dm_run_select(sdso_ctx* ctx, int n, uint8_t* dec, const int* iu, const int* iv, const float* frac, const float* thr, int mode_add, int* n_selected) {
   DistMapState& D = *ctx->dm;
   if ((size_t)D.w1 * D.h1 <= (size_t)DM_LDS_MAP)
     launch_timed(ctx, "k_distmap_select", 1, k_distmap_select<true>, dim3(1), dim3(256), D.map, D.w1, D.h1, n, dec, iu, iv, frac, thr, mode_add, n_selected);
@@ -306,6 +285,12 @@ static int dm_run_select(sdso_ctx* ctx, int n, uint8_t* dec, const int* iu, cons
     launch_timed(ctx, "k_distmap_select", 1, k_distmap_select<false>, dim3(1), dim3(256), D.map, D.w1, D.h1, n, dec, iu, iv, frac, thr, mode_add, n_selected);
   SDSO_HIP(ctx, hipGetLastError());
   return SDSO_OK;
+}
+
+bool distmap_dims(sdso_ctx* ctx, int* w1, int* h1) {
+  if (!ctx->dm || !ctx->dm->valid) return false;
+  *w1 = ctx->dm->w1; *h1 = ctx->dm->h1;
+  return true;
 }
 
 }  // namespace sdso

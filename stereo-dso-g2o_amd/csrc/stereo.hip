@@ -15,6 +15,7 @@
 // reference's operation order (no FP contraction) => statuses, bestIdx and all outputs are
 // bit-identical to the CPU path.
 #include "sdso_internal.h"
+#include "distmap_dev.h"
 #include <algorithm>
 #include <cmath>
 
@@ -918,11 +919,13 @@ constexpr float kMinIdepthH_act = 100.f;
 constexpr int kGNItsOnPointActivation = 3;
 }  // namespace sdso
 
-__global__ __launch_bounds__(256) void k_activate_points(ActDev A) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int p = blockIdx.x * 4 + wv;
-  if (p >= A.n) return;
-  const int nf = A.nf, host = A.host[p];
+// optimizeImmaturePoint for one point by one wave.  A carries the window (nf, w, h, minObs, K, pair_*, img); the point's members come as
+// values — color and wgt are those of pattern pixel lane & 7 — and lane 0 writes *status_out, *idepth_out and res_state[0 .. nf).
+// Shared by k_activate_points (uploaded arrays) and k_imm_activate (the blobs of the resident set).
+__device__ __forceinline__ void activate_point(const ActDev& A, const int lane, const int host, const float pu, const float pv, const float color, const float wgt,
+                                               const float energyTH, const float idepth_min, const float idepth_max, int8_t* status_out,
+                                               float* idepth_out, uint8_t* res_state) {
+  const int nf = A.nf;
   const int r = lane >> 3, idx = lane & 7;
   const int nres = nf - 1;
   const int tgt = r < host ? r : r + 1;                  // r-th frame != host, in frame order
@@ -938,9 +941,6 @@ __global__ __launch_bounds__(256) void k_activate_points(ActDev A) {
   const float fxl = A.fx, fyl = A.fy, cxl = A.cx, cyl = A.cy;
   const float fxli = 1.0f / fxl, fyli = 1.0f / fyl;
   const float wM3G = A.w - 3, hM3G = A.h - 3;
-  const float pu = A.u[p], pv = A.v[p];
-  const float color = A.color[(size_t)p * 8 + idx], wgt = A.weights[(size_t)p * 8 + idx];
-  const float energyTH = A.energyTH[p];
   const int pdx = c_pat[idx][0], pdy = c_pat[idx][1];
 
   // per-lane terms of one linearizeResidual pass at `idepth`
@@ -1001,7 +1001,7 @@ __global__ __launch_bounds__(256) void k_activate_points(ActDev A) {
   };
 
   float lastHdd = 0, lastbd = 0;
-  float currentIdepth = (A.idepth_max[p] + A.idepth_min[p]) * 0.5f;
+  float currentIdepth = (idepth_max + idepth_min) * 0.5f;
   float lastEnergy = pass(currentIdepth, 1000.f, lastHdd, lastbd);
 #pragma unroll
   for (int i = 0; i < 7; i++) { st[i] = nst[i]; en[i] = nen[i]; }
@@ -1028,19 +1028,28 @@ __global__ __launch_bounds__(256) void k_activate_points(ActDev A) {
     }
   }
   if (lane == 0) {
-    for (int f = 0; f < nf; f++) A.res_state[(size_t)p * nf + f] = 255;
-    A.idepth_out[p] = currentIdepth;
+    for (int f = 0; f < nf; f++) res_state[f] = 255;
+    *idepth_out = currentIdepth;
     if (!done) {
       if (!isfinite(currentIdepth)) status = -1;
       else {
         int good = 0;
 #pragma unroll
-        for (int i = 0; i < 7; i++) if (i < nres) { good += st[i] == 0; A.res_state[(size_t)p * nf + (i < host ? i : i + 1)] = (uint8_t)st[i]; }
+        for (int i = 0; i < 7; i++) if (i < nres) { good += st[i] == 0; res_state[i < host ? i : i + 1] = (uint8_t)st[i]; }
         if (good < A.minObs || !isfinite(energyTH)) status = -1;
       }
     }
-    A.status[p] = status;
+    *status_out = status;
   }
+}
+
+__global__ __launch_bounds__(256) void k_activate_points(ActDev A) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int p = blockIdx.x * 4 + wv;
+  if (p >= A.n) return;
+  const int idx = lane & 7;
+  activate_point(A, lane, A.host[p], A.u[p], A.v[p], A.color[(size_t)p * 8 + idx], A.weights[(size_t)p * 8 + idx], A.energyTH[p], A.idepth_min[p], A.idepth_max[p],
+                 A.status + p, A.idepth_out + p, A.res_state + (size_t)p * A.nf);
 }
 
 extern "C" int sdso_activate_points_batch(sdso_ctx* ctx, const sdso_activate_t* A, int8_t* status, float* idepth_out, uint8_t* res_state) {

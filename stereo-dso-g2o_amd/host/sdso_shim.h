@@ -1232,8 +1232,9 @@ inline void marginalizeFrame(int nFrames, int idx, const double* prior8, const d
 // reference's signatures, on the set the library keeps on the device (sdso_imm_*): the three bodies no longer touch
 // host->immaturePoints.  The object stands for the FullSystem members the bodies read: Hcalib, frameHessians, pixelSelector,
 // setting_desiredImmatureDensity and the stereo baseline.  slot_of(frame) is the frame's pyramid slot on the device; a keyframe's slot
-// is also its host_id in the set.  download(host) rebuilds host->immaturePoints from the set (what activatePointsMT reads, per
-// keyframe); remove(host, flags) is STEP 5 for the entries STEP 2 / STEP 4 set to 0; release(host) goes where the reference deletes a
+// is also its host_id in the set.  activatePointsMT runs STEP 2-5 on the set and returns the activated records; upload(host) installs
+// host->immaturePoints as the host's group.  download(host) rebuilds host->immaturePoints from the set (what stereoMatch and the older
+// activation path read); remove(host, flags) is STEP 5 for the entries STEP 2 / STEP 4 set to 0; release(host) goes where the reference deletes a
 // marginalized frame's immature points (and before stereoMatch deletes its temporary frame).  A frame of frameHessians without points in
 // the set is not traced, like the reference's empty loop.  The benchmark-only and debug branches of the three functions are not mirrored.
 // Mat33fT is the reference's Eigen float matrix type (element access (i, j)); products are formed row times column, summed left to right.
@@ -1309,6 +1310,92 @@ class ImmaturePoints {
     dev_.check(sdso_imm_remove(dev_.ctx(), slot_of_(host), (int)flags.size(), flags.data()), "sdso_imm_remove");
   }
   void release(const FrameHessianT* host) { dev_.check(sdso_imm_release_host(dev_.ctx(), slot_of_(host)), "sdso_imm_release_host"); }
+
+  // the set's points of this host <- host->immaturePoints, in the vector's order: the counterpart of download, for a caller that switches
+  // to the resident set in mid-run or made the points on the host (the host must not have points in the set: release first)
+  void upload(const FrameHessianT* host, int w, int h) {
+    const int n = (int)host->immaturePoints.size();
+    std::vector<float> us(n), vs(n), ty(n), imin(n), imax(n), col(n * 8), wgt(n * 8), gH(n * 4), eth(n), q(n), uv(n * 2), itv(n);
+    std::vector<uint8_t> lts(n);
+    for (int i = 0; i < n; i++) {
+      const ImmaturePointT* p = host->immaturePoints[i];
+      us[i] = p->u; vs[i] = p->v; ty[i] = p->my_type; imin[i] = p->idepth_min; imax[i] = p->idepth_max; q[i] = p->quality; eth[i] = p->energyTH;
+      lts[i] = (uint8_t)p->lastTraceStatus; uv[2 * i] = p->lastTraceUV[0]; uv[2 * i + 1] = p->lastTraceUV[1]; itv[i] = p->lastTracePixelInterval;
+      for (int k = 0; k < 8; k++) { col[i * 8 + k] = p->color[k]; wgt[i * 8 + k] = p->weights[k]; }
+      gH[i * 4 + 0] = p->gradH(0, 0); gH[i * 4 + 1] = p->gradH(0, 1); gH[i * 4 + 2] = p->gradH(1, 0); gH[i * 4 + 3] = p->gradH(1, 1);
+    }
+    sdso_trace_points_t P{n, us.data(), vs.data(), nullptr, imin.data(), imax.data(), nullptr, col.data(), wgt.data(), gH.data(), eth.data(),
+                          q.data(), lts.data(), uv.data(), itv.data()};
+    dev_.check(sdso_imm_put_host(dev_.ctx(), slot_of_(host), w, h, &P, ty.data()), "sdso_imm_put_host");
+  }
+
+  // One entry of toOptimize after STEP 3: what optimizeImmaturePoint returned for it (status 1 = a PointHessian, 0 = null, -1 =
+  // (PointHessian*)-1; FullSystemOptPoint.cpp:52-238) and the members PointHessian::PointHessian(const ImmaturePoint*, ...) copies
+  // (HessianBlocks.cpp:35-70).  res_state[f] is the final ResState of the residual to frameHessians[f] (0 IN, 1 OOB, 2 OUTLIER; 255 for
+  // the host itself and for a status-0 exit).
+  struct Activated {
+    FrameHessianT* host;
+    int idxInImmaturePoints;       // in the host's group BEFORE this call's removal
+    int status;
+    float idepth;                  // currentIdepth: setIdepthZero / setIdepth (:208-209)
+    uint8_t res_state[SDSO_IMM_MAX_HOSTS];
+    float u, v, my_type, idepth_min, idepth_max, energyTH, color[8], weights[8];
+    int lastTraceStatus;
+  };
+  // FullSystem::activatePointsMT STEP 2-5 (FullSystem.cpp:837-957) on the set, after coarseDistanceMap->makeDistanceMap(frameHessians,
+  // newestHs): no ImmaturePoint object is built.  Reads what the reference's body reads — cdm.geomOf (:841-842),
+  // host->targetPrecalc[target->idx].PRE_RTll / PRE_tTll / PRE_aff_mode (ImmaturePoint.cpp:897-901), flaggedForMarginalization, the
+  // frames' pyramid slots — and returns the entries of toOptimize.  The caller's STEP 3 tail and STEP 4 become one loop over them: for
+  // status 1 `new PointHessian`, setIdepthZero, the PointFrameResiduals of the IN targets, lastResiduals[0/1], ef->insertPoint /
+  // insertResidual (FullSystemOptPoint.cpp:196-237, FullSystem.cpp:923-933).  The removal of STEP 4 / STEP 5 has already happened in
+  // the set; host->immaturePoints is not touched.  minObs: the reference passes 1 (FullSystem.cpp:790).
+  template <class CoarseDistanceMapT>
+  std::vector<Activated> activatePointsMT(CoarseDistanceMapT& cdm, std::vector<FrameHessianT*>& frameHessians, float currentMinActDist,
+                                          float setting_minTraceQuality, int minObs = 1) {
+    const int nf = (int)frameHessians.size();
+    if (nf < 2 || nf > SDSO_IMM_MAX_HOSTS) throw Error("activatePointsMT: 2..8 frames");
+    FrameHessianT* newestHs = frameHessians.back();
+    std::vector<int> host_id(nf), slot(nf);
+    std::vector<uint8_t> flagged(nf);
+    std::vector<sdso_distmap_geom_t> geom;
+    std::vector<float> pR((size_t)nf * nf * 9), pt((size_t)nf * nf * 3), pa((size_t)nf * nf * 2);
+    for (int f = 0; f < nf; f++) {
+      const FrameHessianT* host = frameHessians[f];
+      host_id[f] = slot[f] = slot_of_(host);
+      flagged[f] = host->flaggedForMarginalization ? 1 : 0;
+      if (host != newestHs) geom.push_back(cdm.geomOf(host, newestHs));
+      for (int t = 0; t < nf; t++) {
+        const auto& pre = host->targetPrecalc[frameHessians[t]->idx];
+        const size_t k = (size_t)f * nf + t;
+        for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) pR[k * 9 + i * 3 + j] = pre.PRE_RTll(i, j);
+        for (int i = 0; i < 3; i++) pt[k * 3 + i] = pre.PRE_tTll[i];
+        pa[k * 2] = pre.PRE_aff_mode[0]; pa[k * 2 + 1] = pre.PRE_aff_mode[1];
+      }
+    }
+    sdso_imm_activate_t A{nf, host_id.data(), slot.data(), flagged.data(), geom.data(), pR.data(), pt.data(), pa.data(), cdm.w[0], cdm.h[0],
+                          {Hcalib_.fxl(), Hcalib_.fyl(), Hcalib_.cxl(), Hcalib_.cyl()}, minObs, currentMinActDist, setting_minTraceQuality};
+    int counts[SDSO_IMM_ACT_NCOUNTS];
+    dev_.check(sdso_imm_activate(dev_.ctx(), &A, counts), "sdso_imm_activate");
+    cdm.markStale();
+    const int n = counts[4];
+    std::vector<int> frame(n), index(n);
+    std::vector<int8_t> status(n);
+    std::vector<uint8_t> rs((size_t)n * nf), lts(n);
+    std::vector<float> idepth(n), us(n), vs(n), ty(n), imin(n), imax(n), eth(n), col((size_t)n * 8), wgt((size_t)n * 8);
+    sdso_imm_activated_t O{n, nf, frame.data(), index.data(), status.data(), idepth.data(), rs.data(), us.data(), vs.data(), ty.data(), imin.data(), imax.data(),
+                           eth.data(), col.data(), wgt.data(), lts.data()};
+    dev_.check(sdso_imm_activate_fetch(dev_.ctx(), &O, nullptr), "sdso_imm_activate_fetch");
+    std::vector<Activated> out(n);
+    for (int p = 0; p < n; p++) {
+      Activated& a = out[p];
+      a.host = frameHessians[frame[p]]; a.idxInImmaturePoints = index[p]; a.status = status[p]; a.idepth = idepth[p];
+      for (int f = 0; f < SDSO_IMM_MAX_HOSTS; f++) a.res_state[f] = f < nf ? rs[(size_t)p * nf + f] : 255;
+      a.u = us[p]; a.v = vs[p]; a.my_type = ty[p]; a.idepth_min = imin[p]; a.idepth_max = imax[p]; a.energyTH = eth[p];
+      for (int k = 0; k < 8; k++) { a.color[k] = col[(size_t)p * 8 + k]; a.weights[k] = wgt[(size_t)p * 8 + k]; }
+      a.lastTraceStatus = lts[p];
+    }
+    return out;
+  }
 
   // K and K.inverse() of :639-645
   void makeK(Mat33fT& K, Mat33fT& Ki) const {

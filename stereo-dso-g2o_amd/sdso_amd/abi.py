@@ -147,6 +147,23 @@ IMM_MAX_HOSTS = 8
 IMM_NCOUNTS = 10   # lastTraceStatus histogram [0..5], forward GOOD, stereo outliers, intervals updated, unreadable
 
 
+IMM_ACT_NCOUNTS = 17   # candidates, KEEP / DELETE / SELECT, toOptimize.size(), statuses -1 / 0 / 1, removed, the new count of every frame's group
+
+
+class ImmActivate(C.Structure):
+    """sdso_imm_activate_t: activatePointsMT STEP 2-5 on the resident set (FullSystem.cpp:837-957)."""
+    _fields_ = [("nf", C.c_int), ("host_id", c_int_p), ("frame_slot", c_int_p), ("host_flagged", c_u8_p), ("geom", C.c_void_p),
+                ("pair_R", c_float_p), ("pair_t", c_float_p), ("pair_aff", c_float_p), ("w", C.c_int), ("h", C.c_int), ("K", C.c_float * 4),
+                ("minObs", C.c_int), ("currentMinActDist", C.c_float), ("minTraceQuality", C.c_float)]
+
+
+class ImmActivated(C.Structure):
+    """sdso_imm_activated_t: one entry per selected candidate, in toOptimize order."""
+    _fields_ = [("n", C.c_int), ("nf", C.c_int), ("frame", c_int_p), ("index", c_int_p), ("status", C.POINTER(C.c_int8)), ("idepth", c_float_p),
+                ("res_state", c_u8_p), ("u", c_float_p), ("v", c_float_p), ("my_type", c_float_p), ("idepth_min", c_float_p), ("idepth_max", c_float_p),
+                ("energyTH", c_float_p), ("color", c_float_p), ("weights", c_float_p), ("lastTraceStatus", c_u8_p)]
+
+
 class Activate(C.Structure):
     _fields_ = [("nf", C.c_int), ("w", C.c_int), ("h", C.c_int), ("n", C.c_int), ("minObs", C.c_int), ("K", C.c_float * 4),
                 ("pair_R", c_float_p), ("pair_t", c_float_p), ("pair_aff", c_float_p), ("frame_slot", c_int_p), ("dI", C.POINTER(c_float_p)),
@@ -479,6 +496,9 @@ def load():
     L.sdso_imm_remove_order.argtypes = [C.c_int, c_u8_p, c_int_p, c_int_p]
     L.sdso_imm_remove.argtypes = [vp, C.c_int, C.c_int, c_u8_p]
     L.sdso_imm_release_host.argtypes = [vp, C.c_int]
+    L.sdso_imm_put_host.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(TracePoints), c_float_p]
+    L.sdso_imm_activate.argtypes = [vp, C.POINTER(ImmActivate), c_int_p]
+    L.sdso_imm_activate_fetch.argtypes = [vp, C.POINTER(ImmActivated), c_u8_p]
     _lib = L
     return L
 
@@ -506,6 +526,7 @@ EXPORTED_SYMBOLS = [
     "sdso_distmap_make", "sdso_distmap_add", "sdso_distmap_get", "sdso_activate_select",
     "sdso_undistort_make_remap", "sdso_ingest_calib_create", "sdso_ingest_calib_release", "sdso_ingest_frame",
     "sdso_imm_add_frame", "sdso_imm_trace", "sdso_imm_count", "sdso_imm_get", "sdso_imm_remove_order", "sdso_imm_remove", "sdso_imm_release_host",
+    "sdso_imm_put_host", "sdso_imm_activate", "sdso_imm_activate_fetch",
 ]
 
 
@@ -566,6 +587,57 @@ class Context:
         return dict(u=d["u_stereo"], v=d["v_stereo"], my_type=my_type, idepth_min=d["idepth_min_stereo"], idepth_max=d["idepth_max_stereo"],
                     quality=d["quality"], color=d["color"], weights=d["weights"], gradH=d["gradH"], energyTH=d["energyTH"],
                     lastTraceStatus=d["lastTraceStatus"], lastTraceUV=d["lastTraceUV"], lastTracePixelInterval=d["lastTracePixelInterval"])
+
+    def imm_put(self, host_id, S, w, h):
+        """sdso_imm_put_host: installs a group from a dict of arrays as imm_get returns it."""
+        n = len(S["u"])
+        a = {k: np.ascontiguousarray(S[k], np.uint8 if k == "lastTraceStatus" else np.float32) for k in
+             ("u", "v", "my_type", "idepth_min", "idepth_max", "quality", "color", "weights", "gradH", "energyTH", "lastTraceStatus", "lastTraceUV",
+              "lastTracePixelInterval")}
+        P = TracePoints()
+        P.n = n
+        P.u_stereo = fp(a["u"]); P.v_stereo = fp(a["v"]); P.idepth_min_stereo = fp(a["idepth_min"]); P.idepth_max_stereo = fp(a["idepth_max"])
+        for k in ("color", "weights", "gradH", "energyTH", "quality", "lastTraceUV", "lastTracePixelInterval"):
+            setattr(P, k, fp(a[k]))
+        P.lastTraceStatus = bp(a["lastTraceStatus"])
+        self.check(self.L.sdso_imm_put_host(self.h, host_id, w, h, C.byref(P), fp(a["my_type"])))
+
+    def imm_activate_raw(self, host_id, frame_slot, host_flagged, KRKi, Kt, pair_R, pair_t, pair_aff, w, h, K4, min_obs, min_act_dist, min_trace_quality=3.0):
+        """sdso_imm_activate without the fetch -> (return code, counts)."""
+        nf = len(host_id)
+        keep = [np.ascontiguousarray(host_id, np.int32), np.ascontiguousarray(frame_slot, np.int32), np.ascontiguousarray(host_flagged, np.uint8),
+                np.ascontiguousarray(pair_R, np.float32), np.ascontiguousarray(pair_t, np.float32), np.ascontiguousarray(pair_aff, np.float32)]
+        G = make_distmap_geoms(KRKi, Kt)
+        A = ImmActivate()
+        A.nf = nf; A.host_id = ip(keep[0]); A.frame_slot = ip(keep[1]); A.host_flagged = bp(keep[2]); A.geom = C.cast(G, C.c_void_p)
+        A.pair_R = fp(keep[3]); A.pair_t = fp(keep[4]); A.pair_aff = fp(keep[5])
+        A.w, A.h, A.minObs, A.currentMinActDist, A.minTraceQuality = w, h, min_obs, min_act_dist, min_trace_quality
+        A.K[:] = [float(x) for x in K4]
+        counts = np.full(IMM_ACT_NCOUNTS, -1, np.int32)
+        rc = self.L.sdso_imm_activate(self.h, C.byref(A), ip(counts))
+        return rc, counts
+
+    def imm_activate_fetch(self, n_candidates, n_selected, nf):
+        """sdso_imm_activate_fetch -> dict of arrays (one entry per selected candidate) with `decision` (one per candidate)."""
+        n = n_selected
+        d = dict(frame=np.zeros(n, np.int32), index=np.zeros(n, np.int32), status=np.zeros(n, np.int8), idepth=np.zeros(n, np.float32),
+                 res_state=np.zeros((n, nf), np.uint8), u=np.zeros(n, np.float32), v=np.zeros(n, np.float32), my_type=np.zeros(n, np.float32),
+                 idepth_min=np.zeros(n, np.float32), idepth_max=np.zeros(n, np.float32), energyTH=np.zeros(n, np.float32),
+                 color=np.zeros((n, 8), np.float32), weights=np.zeros((n, 8), np.float32), lastTraceStatus=np.zeros(n, np.uint8))
+        O = ImmActivated()
+        for k, a in d.items():
+            setattr(O, k, a.ctypes.data_as(C.POINTER(C.c_int8)) if a.dtype == np.int8 else {np.dtype(np.float32): fp, np.dtype(np.int32): ip, np.dtype(np.uint8): bp}[a.dtype](a))
+        dec = np.zeros(n_candidates, np.uint8)
+        self.check(self.L.sdso_imm_activate_fetch(self.h, C.byref(O), bp(dec)))
+        assert O.n == n and O.nf == nf
+        d["decision"] = dec
+        return d
+
+    def imm_activate(self, host_id, *args, **kw):
+        """sdso_imm_activate + sdso_imm_activate_fetch -> (counts, dict of the activated records)."""
+        rc, counts = self.imm_activate_raw(host_id, *args, **kw)
+        self.check(rc)
+        return counts, self.imm_activate_fetch(int(counts[0]), int(counts[4]), len(host_id))
 
     def upload_pyramid(self, slot, pyr):
         n = len(pyr)
