@@ -17,8 +17,8 @@ AFFS = ((0.02, 1.5), (0.03, 2.0), (0.01, 1.0), (0.0, 0.5))
 NOISE = ((21, 22), (31, 32), (41, 42), (51, 52))
 
 
-def calib():
-    cal = synth.kitti_calib(W, H)
+def calib(w=W, h=H):
+    cal = synth.kitti_calib(w, h)
     K4 = np.array([cal["fx"], cal["fy"], cal["cx"], cal["cy"]], f32)
     K = np.array([[K4[0], 0, K4[2]], [0, K4[1], K4[3]], [0, 0, 1]], f32)
     Ki = np.linalg.inv(K.astype(np.float64)).astype(f32)            # the caller's K.inverse()
@@ -34,18 +34,18 @@ def geom(K, Ki, T_host, T_frame, aff_frame):
                 KRi=(K @ R.T).astype(f32).ravel(), t=t)
 
 
-def images(scene, K4, T, noise, aff=(0.0, 0.0), baseline=None):
+def images(scene, K4, T, noise, aff=(0.0, 0.0), baseline=None, w=W, h=H):
     """level-0 {I, dx, dy} of the left camera at world-to-camera T and, with a baseline, of the right one"""
     out = []
     for k, Tc in enumerate([T] if baseline is None else [T, (T[0], T[1] + np.array([-float(baseline), 0.0, 0.0]))]):
-        img, idepth = scene.render(W, H, K4, Tc, noise_seed=noise[k], aff=aff)
+        img, idepth = scene.render(w, h, K4, Tc, noise_seed=noise[k], aff=aff)
         out.append((np.ascontiguousarray(synth.make_pyramid(img, 1)[0]), idepth))
     return out
 
 
-def selection_map(dI0, idepth, n, seed):
+def selection_map(dI0, idepth, n, seed, w=W, h=H):
     """n selected pixels with types 1 / 2 / 4 in turn (a PixelSelector map), away from the border"""
-    m = np.zeros((H, W), f32)
+    m = np.zeros((h, w), f32)
     if n:
         u, v = synth.select_points(dI0, n, seed, idepth=idepth, min_idepth=0.0075)
         m[v, u] = np.array([1, 2, 4], f32)[np.arange(n) % 3]
