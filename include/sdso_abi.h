@@ -180,6 +180,36 @@ int sdso_track_release_ref(sdso_ctx* ctx, int ref_slot);
  * and sqrtf(1e-3 / (HdiF + 1e-12)), :350.) */
 int sdso_track_make_ref(sdso_ctx* ctx, int ref_slot, int frame_slot, int n, const int* u, const int* v,
                         const float* new_idepth, const float* weight, int* pc_n_out);
+/* CoarseTracker::setCoarseTrackingRef -> makeCoarseDepthL0 (CoarseTracker.cpp:275-534, 807-826) from the device-resident window `win`
+ * after sdso_ba_optimize: STEP1's gather, the L->R->L stereo re-observation, the accept rule and the weight, then STEP2-5, without any
+ * per-point data crossing the bus.  lastRef = the window's last frame (its frame_slot), K = the window's current calibration
+ * (Hcalib.fxl() .. cyl() after the optimize).
+ *   selection : a point is splatted iff its residual into the newest keyframe is in activeResiduals, active and IN after the closing
+ *               linearizeAll(true) — lastResiduals[0].first != 0 && lastResiduals[0].second == ResState::IN (:295)
+ *   per point : centerProjectedTo as sdso_ba_get_post_state returns it; u = int(cpt[0] + 0.5f), v likewise; both traces take the
+ *               interval [0.1f, 1.9f] * cpt[2]; the accept rule of :329-341; weight = sqrtf(1e-3 / (HdiF + 1e-12))
+ *   order     : the splat adds the points of one pixel in the order of point_order (window point indices) restricted to the selected
+ *               points — pass FrameHessian::pointHessians order, frame by frame, which differs from the window's order once points
+ *               have been removed (EnergyFunctional.cpp:755-771 swaps, FullSystem.cpp:1047-1053 compacts).  NULL: window order.
+ *   border    : a selected point whose rounded pixel lies outside [2, w-3) x [2, h-3) takes no stereo (new_idepth = cpt[2]); one
+ *               outside the image is not splatted.  Both are counted in n_border_out.  The reference reads / writes outside its
+ *               arrays there, and sdso_stereo_match_batch refuses such a point; an IN residual has its pattern inside (1.1, w-3), so
+ *               the count is expected to be 0.
+ *   refusals  : decided before any device work.  SDSO_ERR_STATE: the window has no valid post-state (no optimize call has ended on it,
+ *               or sdso_ba_window_update has edited it since), is inside a batch, or holds a linearised residual.  SDSO_ERR_ARG: an
+ *               unknown window or frame slot, a right pyramid of another size, a point_order entry out of range or named twice.
+ *   sync      : the call reads the number of selected points back once (the launches of the stereo chain and of the splat are sized
+ *               by it) and otherwise only enqueues: the templates are allocated for the most points STEP5 can keep, and pc_n reaches
+ *               the host behind an event that the next reader of the reference (sdso_track_newest_coarse, sdso_track_get_ref, ...)
+ *               waits for.  Asking for pc_n_out waits for that event in the call.  A template that has to grow is allocated anew,
+ *               which synchronises once.  sdso_trace_set_gn_mode applies as in sdso_stereo_match_batch.
+ * The reference is installed exactly as by sdso_track_make_ref; n_points_out = the selected points, pc_n_out[levels]; each may be NULL. */
+int sdso_track_make_ref_from_window(sdso_ctx* ctx, int ref_slot, int win, int right_slot, float baseline,
+                                    const int* point_order /* n_order window point indices, or NULL: window order */, int n_order,
+                                    int* n_points_out, int* n_border_out, int* pc_n_out /* levels; each may be NULL */);
+/* tests / debugging: STEP1's per-point results of the latest call on ref_slot, in splat order; arrays may be NULL */
+int sdso_track_get_ref_points(sdso_ctx* ctx, int ref_slot, int* n, int* point /* window index */, int* u, int* v,
+                              float* centerProjectedTo2, uint8_t* status_fwd, uint8_t* status_back, float* new_idepth, float* weight);
 /* read a template level back (tests); n_out = pc_n[lvl]; arrays may be NULL */
 int sdso_track_get_ref(sdso_ctx* ctx, int ref_slot, int lvl, int* n_out, float* pc_u, float* pc_v,
                        float* pc_idepth, float* pc_color);

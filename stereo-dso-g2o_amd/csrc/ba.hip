@@ -2310,4 +2310,20 @@ extern "C" int sdso_ba_get_counts(sdso_ctx* ctx, int win, int* resInA, int* resI
 }
 
 
+// The window as sdso_track_make_ref_from_window reads it (sdso_internal.h): its device descriptor after a finished optimize call.
+namespace sdso {
+int ba_ref_view(sdso_ctx* ctx, int win, BaRefView* out) {
+  BaWindowDev* W = find_win(ctx, win);
+  if (!W) return sdso::fail(ctx, SDSO_ERR_ARG, "unknown window");
+  if (!W->post_valid) return sdso::fail(ctx, SDSO_ERR_STATE, "the window has no post-state: sdso_ba_optimize first (sdso_ba_window_update discards it)");
+  if (W->in_batch) return sdso::fail(ctx, SDSO_ERR_STATE, "the window is a member of a batch");
+  if (W->has_lin_cached) return sdso::fail(ctx, SDSO_ERR_STATE, "the window holds a linearised residual");
+  out->dev = W->d_self;
+  out->nf = W->d.nf; out->np = W->d.np; out->nr = W->d.nr; out->w = W->d.w; out->h = W->d.h;
+  out->last_frame_slot = W->frames[W->d.nf - 1].frame_slot;
+  out->K[0] = W->d.fxl; out->K[1] = W->d.fyl; out->K[2] = W->d.cxl; out->K[3] = W->d.cyl;
+  return SDSO_OK;
+}
+}  // namespace sdso
+
 #include "ba_update.hip"   // sdso_ba_window_plan / _update / _get_order (same translation unit: upload_window_impl is the builder)

@@ -17,6 +17,7 @@
 //     instead of float atomics whose order is not defined).
 //   * compaction: per-row counts -> exclusive scan over rows -> in-row ranks by ballot prefix: raster order, no atomics.
 #include "sdso_internal.h"
+#include <algorithm>
 #include <vector>
 
 using namespace sdso;
@@ -129,7 +130,7 @@ __global__ __launch_bounds__(256) void k_cd_scan(int* __restrict__ rowcnt, int n
 }
 // pass 2: scatter in raster order (kept pixels are those with idepth > 0 after pass 1)
 __global__ __launch_bounds__(256) void k_cd_scatter(const float* __restrict__ idl, const float4* __restrict__ ref, int wl, int hl, const int* __restrict__ rowoff,
-                                                    float4* __restrict__ pc) {
+                                                    float4* __restrict__ pc, int cap /* entries of pc: never written past */) {
   const int y = 2 + blockIdx.x;
   __shared__ int s_cnt[4];
   int base = rowoff[blockIdx.x];
@@ -145,7 +146,7 @@ __global__ __launch_bounds__(256) void k_cd_scatter(const float* __restrict__ id
     int off = base;
     for (int k = 0; k < wv; k++) off += s_cnt[k];
     off += __popcll(m & ((1ull << lane) - 1ull));
-    if (keep) pc[off] = make_float4((float)x, (float)y, v, c);
+    if (keep && off < cap) pc[off] = make_float4((float)x, (float)y, v, c);
     base += s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
     __syncthreads();
   }
@@ -157,41 +158,59 @@ __global__ void k_cd_unpack(const float4* __restrict__ pc, int n, float* __restr
   out[i] = q.x; out[n + i] = q.y; out[2 * (size_t)n + i] = q.z; out[3 * (size_t)n + i] = q.w;
 }
 
+// bytes of ctx->scratch track_make_ref_dev lays its maps, row counts and level totals out in (a multiple of 16)
+size_t make_ref_scratch_bytes(const PyramidDev& P) {
+  size_t tot = 0, rows = 0;
+  for (int l = 0; l < P.levels; l++) { tot += (size_t)P.w[l] * P.h[l]; rows += (size_t)P.h[l]; }
+  return (sizeof(float) * 3 * tot + sizeof(int) * (rows + SDSO_PYR_LEVELS) + 15) & ~(size_t)15;
+}
+
 }  // namespace
 
-extern "C" int sdso_track_make_ref(sdso_ctx* ctx, int ref_slot, int frame_slot, int n, const int* u, const int* v, const float* new_idepth,
-                                   const float* weight, int* pc_n_out) {
-  if (!ctx) return SDSO_ERR_STATE;
-  SDSO_HIP(ctx, hipSetDevice(ctx->device));
-  auto ip = ctx->pyr.find(frame_slot);
-  SDSO_REQUIRE(ctx, ip != ctx->pyr.end(), "unknown frame slot");
-  SDSO_REQUIRE(ctx, n >= 0 && (n == 0 || (u && v && new_idepth && weight)), "null point arrays");
-  const PyramidDev& P = ip->second;
-  const int L = P.levels, w0 = P.w[0], h0 = P.h[0];
-  for (int i = 0; i < n; i++) SDSO_REQUIRE(ctx, u[i] >= 0 && u[i] < w0 && v[i] >= 0 && v[i] < h0, "point outside the image");
-  // maps of all levels in one allocation: idepth, weightSums, weightSums_bak
-  size_t tot = 0, off[SDSO_PYR_LEVELS];
-  for (int l = 0; l < L; l++) { off[l] = tot; tot += (size_t)P.w[l] * P.h[l]; }
-  const size_t need = sizeof(float) * 3 * tot + sizeof(int) * ((size_t)h0 + 8) + sizeof(float) * 2 * (size_t)std::max(n, 1) + sizeof(int) * 2 * (size_t)std::max(n, 1);
-  int rc = ensure_scratch(ctx, need);
+// STEP1's splat and STEP2-5 on device-resident points (u, v: n ints; new_idepth, weight: n floats; none of them inside ctx->scratch,
+// which holds the maps), installed as reference `ref_slot`.  Nothing here waits for the device in the steady state: a level's template
+// is allocated for the most pixels STEP5 can keep — a pixel carries weight only where one of the n points fell into it (at most n per
+// level, the 2x2 sums of STEP2 included) or where STEP3/4 dilated one of its four neighbours into it (at most 4 per such pixel): 5 n,
+// and never more than the (w-4) x (h-4) pixels STEP5 scans — and reused while it is large enough; the counts travel to the host behind
+// an event, and ref_counts() (every reader of RefDev::n calls it) waits for that event only.  pc_n_out (levels entries, optional) waits for the
+// counts, not for the scatter; sync_end: the call returns a finished template, as sdso_track_make_ref does.
+// The caller has validated the frame slot and the points.
+namespace sdso {
+int track_make_ref_dev(sdso_ctx* ctx, int ref_slot, int frame_slot, int n, const int* d_u, const int* d_v, const float* d_idp, const float* d_wgt,
+                       int* pc_n_out, bool sync_end) {
+  const PyramidDev& P = ctx->pyr.find(frame_slot)->second;
+  const int L = P.levels, w0 = P.w[0];
+  // maps of all levels in one allocation: idepth, weightSums, weightSums_bak; then the row counts of every level and the level totals
+  size_t tot = 0, off[SDSO_PYR_LEVELS], roff[SDSO_PYR_LEVELS], rows = 0;
+  for (int l = 0; l < L; l++) { off[l] = tot; tot += (size_t)P.w[l] * P.h[l]; roff[l] = rows; rows += (size_t)P.h[l]; }
+  int rc = ensure_scratch(ctx, make_ref_scratch_bytes(P));
   if (rc) return rc;
   float* idm = (float*)ctx->scratch;
   float* wsm = idm + tot;
   float* bak = wsm + tot;
   int* rowcnt = (int*)(bak + tot);
-  int* d_total = rowcnt + h0 + 4;
-  float* d_idp = (float*)(rowcnt + h0 + 8);
-  float* d_wgt = d_idp + std::max(n, 1);
-  int* d_u = (int*)(d_wgt + std::max(n, 1));
-  int* d_v = d_u + std::max(n, 1);
-  SDSO_HIP(ctx, hipMemsetAsync(idm, 0, sizeof(float) * 2 * tot, ctx->stream));
-  if (n) {
-    SDSO_HIP(ctx, hipMemcpyAsync(d_idp, new_idepth, sizeof(float) * n, hipMemcpyHostToDevice, ctx->stream));
-    SDSO_HIP(ctx, hipMemcpyAsync(d_wgt, weight, sizeof(float) * n, hipMemcpyHostToDevice, ctx->stream));
-    SDSO_HIP(ctx, hipMemcpyAsync(d_u, u, sizeof(int) * n, hipMemcpyHostToDevice, ctx->stream));
-    SDSO_HIP(ctx, hipMemcpyAsync(d_v, v, sizeof(int) * n, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_cd_splat, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, w0, d_u, d_v, d_idp, d_wgt, idm, wsm);
+  int* d_total = rowcnt + rows;
+  RefDev& R = ctx->refs[ref_slot];
+  if (!R.counts_host) SDSO_HIP(ctx, hipHostMalloc((void**)&R.counts_host, sizeof(int) * SDSO_PYR_LEVELS));
+  if (!R.counts_ev) SDSO_HIP(ctx, hipEventCreateWithFlags(&R.counts_ev, hipEventDisableTiming));
+  rc = ref_counts(ctx, R);   // (a template of this slot still on its way: its counts are about to be replaced)
+  if (rc) return rc;
+  // the templates: kept while they are large enough (earlier kernels that read them are ahead of the scatter on the stream)
+  int need[SDSO_PYR_LEVELS] = {0, 0, 0, 0, 0, 0};
+  for (int l = 0; l < L; l++) {
+    const long long area = (long long)std::max(P.w[l] - 4, 0) * std::max(P.h[l] - 4, 0);
+    need[l] = (int)std::min<long long>(area, 5LL * n);
   }
+  for (int l = 0; l < SDSO_PYR_LEVELS; l++) {
+    if (R.cap[l] >= need[l]) continue;
+    if (R.pc[l]) { SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream)); hipFree(R.pc[l]); R.pc[l] = nullptr; R.cap[l] = 0; }
+    const long long area = (long long)std::max(P.w[l] - 4, 0) * std::max(P.h[l] - 4, 0);
+    const int cap = (int)std::min<long long>(area, (long long)need[l] + need[l] / 4 + 1024);
+    SDSO_HIP(ctx, hipMalloc(&R.pc[l], sizeof(float4) * (size_t)cap));
+    R.cap[l] = cap;
+  }
+  SDSO_HIP(ctx, hipMemsetAsync(idm, 0, sizeof(float) * 2 * tot, ctx->stream));
+  if (n) hipLaunchKernelGGL(k_cd_splat, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, w0, d_u, d_v, d_idp, d_wgt, idm, wsm);
   for (int l = 1; l < L; l++)
     hipLaunchKernelGGL(k_cd_down, dim3((P.w[l] + 255) / 256, P.h[l]), dim3(256), 0, ctx->stream, idm + off[l - 1], wsm + off[l - 1], P.w[l - 1], idm + off[l],
                        wsm + off[l], P.w[l], P.h[l]);
@@ -202,31 +221,57 @@ extern "C" int sdso_track_make_ref(sdso_ctx* ctx, int ref_slot, int frame_slot, 
     if (cnt > 0)
       hipLaunchKernelGGL(k_cd_dilate, dim3((cnt + 255) / 256), dim3(256), 0, ctx->stream, idm + off[l], wsm + off[l], bak + off[l], P.w[l], P.h[l], l < 2 ? 1 : 0);
   }
-  RefDev& R = ctx->refs[ref_slot];
-  SDSO_HIP(ctx, hipGetLastError());
-  for (int l = 0; l < SDSO_PYR_LEVELS; l++) {
-    if (R.pc[l]) { SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream)); hipFree(R.pc[l]); R.pc[l] = nullptr; }
-    R.n[l] = 0;
-  }
+  SDSO_HIP(ctx, hipMemsetAsync(d_total, 0, sizeof(int) * SDSO_PYR_LEVELS, ctx->stream));
   for (int l = 0; l < L; l++) {
     const int nrows = P.h[l] - 4;
-    int total = 0;
-    if (nrows > 0 && P.w[l] > 4) {
-      hipLaunchKernelGGL(k_cd_flag, dim3(nrows), dim3(256), 0, ctx->stream, idm + off[l], wsm + off[l], P.d[l], P.w[l], P.h[l], rowcnt);
-      hipLaunchKernelGGL(k_cd_scan, dim3(1), dim3(256), 0, ctx->stream, rowcnt, nrows, d_total);
-      SDSO_HIP(ctx, hipMemcpyAsync(&total, d_total, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-      SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      if (total > 0) {
-        SDSO_HIP(ctx, hipMalloc(&R.pc[l], sizeof(float4) * (size_t)total));
-        hipLaunchKernelGGL(k_cd_scatter, dim3(nrows), dim3(256), 0, ctx->stream, idm + off[l], P.d[l], P.w[l], P.h[l], rowcnt, R.pc[l]);
-      }
-    }
-    R.n[l] = total;
-    if (pc_n_out) pc_n_out[l] = total;
+    if (nrows <= 0 || P.w[l] <= 4) continue;
+    hipLaunchKernelGGL(k_cd_flag, dim3(nrows), dim3(256), 0, ctx->stream, idm + off[l], wsm + off[l], P.d[l], P.w[l], P.h[l], rowcnt + roff[l]);
+    hipLaunchKernelGGL(k_cd_scan, dim3(1), dim3(256), 0, ctx->stream, rowcnt + roff[l], nrows, d_total + l);
+  }
+  SDSO_HIP(ctx, hipMemcpyAsync(R.counts_host, d_total, sizeof(int) * SDSO_PYR_LEVELS, hipMemcpyDeviceToHost, ctx->stream));
+  SDSO_HIP(ctx, hipEventRecord(R.counts_ev, ctx->stream));
+  R.counts_pending = true;
+  for (int l = 0; l < L; l++) {
+    const int nrows = P.h[l] - 4;
+    if (nrows <= 0 || P.w[l] <= 4 || need[l] == 0) continue;
+    hipLaunchKernelGGL(k_cd_scatter, dim3(nrows), dim3(256), 0, ctx->stream, idm + off[l], P.d[l], P.w[l], P.h[l], rowcnt + roff[l], R.pc[l], R.cap[l]);
   }
   SDSO_HIP(ctx, hipGetLastError());
-  SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (sync_end) SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (sync_end || pc_n_out) {
+    rc = ref_counts(ctx, R);
+    if (rc) return rc;
+    if (pc_n_out) for (int l = 0; l < L; l++) pc_n_out[l] = R.n[l];
+  }
   return SDSO_OK;
+}
+}  // namespace sdso
+
+extern "C" int sdso_track_make_ref(sdso_ctx* ctx, int ref_slot, int frame_slot, int n, const int* u, const int* v, const float* new_idepth,
+                                   const float* weight, int* pc_n_out) {
+  if (!ctx) return SDSO_ERR_STATE;
+  SDSO_HIP(ctx, hipSetDevice(ctx->device));
+  auto ip = ctx->pyr.find(frame_slot);
+  SDSO_REQUIRE(ctx, ip != ctx->pyr.end(), "unknown frame slot");
+  SDSO_REQUIRE(ctx, n >= 0 && (n == 0 || (u && v && new_idepth && weight)), "null point arrays");
+  const PyramidDev& P = ip->second;
+  const int w0 = P.w[0], h0 = P.h[0];
+  for (int i = 0; i < n; i++) SDSO_REQUIRE(ctx, u[i] >= 0 && u[i] < w0 && v[i] >= 0 && v[i] < h0, "point outside the image");
+  // the points travel behind the maps of track_make_ref_dev in the ctx scratch
+  const size_t maps = make_ref_scratch_bytes(P), m = (size_t)std::max(n, 1);
+  int rc = ensure_scratch(ctx, maps + (sizeof(float) * 2 + sizeof(int) * 2) * m);
+  if (rc) return rc;
+  float* d_idp = (float*)((char*)ctx->scratch + maps);
+  float* d_wgt = d_idp + m;
+  int* d_u = (int*)(d_wgt + m);
+  int* d_v = d_u + m;
+  if (n) {
+    SDSO_HIP(ctx, hipMemcpyAsync(d_idp, new_idepth, sizeof(float) * n, hipMemcpyHostToDevice, ctx->stream));
+    SDSO_HIP(ctx, hipMemcpyAsync(d_wgt, weight, sizeof(float) * n, hipMemcpyHostToDevice, ctx->stream));
+    SDSO_HIP(ctx, hipMemcpyAsync(d_u, u, sizeof(int) * n, hipMemcpyHostToDevice, ctx->stream));
+    SDSO_HIP(ctx, hipMemcpyAsync(d_v, v, sizeof(int) * n, hipMemcpyHostToDevice, ctx->stream));
+  }
+  return track_make_ref_dev(ctx, ref_slot, frame_slot, n, d_u, d_v, d_idp, d_wgt, pc_n_out, true);
 }
 
 extern "C" int sdso_track_get_ref(sdso_ctx* ctx, int ref_slot, int lvl, int* n_out, float* pc_u, float* pc_v, float* pc_idepth, float* pc_color) {
@@ -235,6 +280,8 @@ extern "C" int sdso_track_get_ref(sdso_ctx* ctx, int ref_slot, int lvl, int* n_o
   auto ir = ctx->refs.find(ref_slot);
   SDSO_REQUIRE(ctx, ir != ctx->refs.end(), "unknown ref slot");
   SDSO_REQUIRE(ctx, lvl >= 0 && lvl < SDSO_PYR_LEVELS, "bad level");
+  int rc0 = ref_counts(ctx, ir->second);
+  if (rc0) return rc0;
   const int n = ir->second.n[lvl];
   if (n_out) *n_out = n;
   if (n == 0 || !(pc_u || pc_v || pc_idepth || pc_color)) return SDSO_OK;

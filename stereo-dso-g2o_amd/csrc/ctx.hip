@@ -149,6 +149,7 @@ void release_distmap(sdso_ctx* ctx);
 void release_ingest(sdso_ctx* ctx);
 void release_immature(sdso_ctx* ctx);
 void release_comm(sdso_ctx* ctx);
+void release_refwin(sdso_ctx* ctx);
 }
 
 extern "C" void sdso_ctx_destroy(sdso_ctx* ctx) {
@@ -159,8 +160,7 @@ extern "C" void sdso_ctx_destroy(sdso_ctx* ctx) {
   if (ctx->ev_main) hipEventDestroy(ctx->ev_main);
   if (ctx->ev_aux) hipEventDestroy(ctx->ev_aux);
   for (auto& kv : ctx->pyr) free_pyramid(kv.second);
-  for (auto& kv : ctx->refs)
-    for (int l = 0; l < SDSO_PYR_LEVELS; l++) if (kv.second.pc[l]) hipFree(kv.second.pc[l]);
+  for (auto& kv : ctx->refs) ref_free(kv.second);
   release_all_windows(ctx);
   for (auto& b : ctx->ba_pool) hipFree(b.first);
   release_track_batch(ctx);
@@ -170,6 +170,7 @@ extern "C" void sdso_ctx_destroy(sdso_ctx* ctx) {
   release_distmap(ctx);
   release_ingest(ctx);
   release_immature(ctx);
+  release_refwin(ctx);
   release_comm(ctx);
   if (ctx->gammaB) hipFree(ctx->gammaB);
   if (ctx->scratch) hipFree(ctx->scratch);

@@ -349,6 +349,8 @@ extern "C" int sdso_g2o_track_add_edges(sdso_ctx* ctx, int ref_slot, int frame_s
   const int lvl = ev->lvl;
   SDSO_REQUIRE(ctx, lvl >= 0 && lvl < ip->second.levels, "level out of range");
   SDSO_REQUIRE(ctx, ev->w == ip->second.w[lvl] && ev->h == ip->second.h[lvl], "level size does not match the uploaded pyramid");
+  int rc0 = ref_counts(ctx, ir->second);
+  if (rc0) return rc0;
   const int n = ir->second.n[lvl];
   if (!ctx->g2o) ctx->g2o = new G2oState();
   G2oState& st = *ctx->g2o;
@@ -465,6 +467,8 @@ extern "C" int sdso_g2o_track_newest_coarse(sdso_ctx* ctx, int ref_slot, int fra
   out->good = 0; out->evaluations = 0; out->point_evals = 0;
   auto ir = ctx->refs.find(ref_slot);
   SDSO_REQUIRE(ctx, ir != ctx->refs.end(), "unknown reference slot");
+  int rc0 = ref_counts(ctx, ir->second);
+  if (rc0) return rc0;
   Se3 pose;
   std::memcpy(pose.R.data(), lastToNew->R, 72);
   std::memcpy(pose.t.data(), lastToNew->t, 24);

@@ -41,6 +41,12 @@ struct PyramidDev {
 struct RefDev {
   int n[SDSO_PYR_LEVELS] = {0};
   float4* pc[SDSO_PYR_LEVELS] = {nullptr};
+  int cap[SDSO_PYR_LEVELS] = {0};   // entries pc[l] was allocated for (>= n[l])
+  // A template built on the device without waiting for it (track_make_ref_dev): its counts are on their way into `counts_host`
+  // (pinned) behind `counts_ev`; ref_counts() brings n[] up to date.  Every reader of n[] calls it first.
+  bool counts_pending = false;
+  int* counts_host = nullptr;
+  hipEvent_t counts_ev = nullptr;
 };
 
 struct ProfEntry {
@@ -59,6 +65,8 @@ struct DistMapState; // distmap.hip
 struct IngestState;  // ingest.hip
 struct ImmState;     // immature.hip (compiled with stereo.hip)
 struct Comm;         // comm.hip
+struct RefWinState;  // ref_window.hip
+struct BaDev;        // ba_kernels.h
 
 }  // namespace sdso
 
@@ -78,6 +86,7 @@ struct sdso_ctx {
   sdso::DistMapState* dm = nullptr;     // the level-1 CoarseDistanceMap
   sdso::IngestState* ingest = nullptr;  // calibration tables and raw-image staging of sdso_ingest_frame
   sdso::ImmState* imm = nullptr;        // the device-resident immature points, per host keyframe (sdso_imm_*)
+  sdso::RefWinState* refwin = nullptr;  // STEP1 records of sdso_track_make_ref_from_window, per reference slot
   std::shared_ptr<sdso::Comm> comm;     // shared with the contexts joined by sdso_comm_attach
   // generic scratch
   void* scratch = nullptr;
@@ -125,6 +134,20 @@ inline int fail(sdso_ctx* ctx, int code, const std::string& msg) {
   } while (0)
 
 int ensure_scratch(sdso_ctx* ctx, size_t bytes);
+// n[] of a reference whose template was enqueued without a synchronisation: waits for that template's counts only
+inline int ref_counts(sdso_ctx* ctx, RefDev& R) {
+  if (!R.counts_pending) return SDSO_OK;
+  SDSO_HIP(ctx, hipEventSynchronize(R.counts_ev));
+  for (int l = 0; l < SDSO_PYR_LEVELS; l++) R.n[l] = R.counts_host[l] < R.cap[l] ? R.counts_host[l] : R.cap[l];   // (never past the allocation)
+  R.counts_pending = false;
+  return SDSO_OK;
+}
+inline void ref_free(RefDev& R) {
+  for (int l = 0; l < SDSO_PYR_LEVELS; l++) { if (R.pc[l]) hipFree(R.pc[l]); R.pc[l] = nullptr; R.n[l] = 0; R.cap[l] = 0; }
+  if (R.counts_host) hipHostFree(R.counts_host);
+  if (R.counts_ev) hipEventDestroy(R.counts_ev);
+  R.counts_host = nullptr; R.counts_ev = nullptr; R.counts_pending = false;
+}
 // Bracket the launches of one named kernel with HIP events when profiling is enabled.
 // The A/B and diagnostic switches of the library (SDSO_BA_*, SDSO_TRK_*, SDSO_OPT_*, SDSO_PROF_BRACKET) exist only under SDSO_DEBUG_ENV=1,
 // which is read ONCE per process: without it no environment variable changes what the library computes or launches, and no call reads
@@ -204,6 +227,18 @@ int ensure_tiled0(sdso_ctx* ctx, PyramidDev& P);   // ctx.hip
 int ensure_plane0(sdso_ctx* ctx, PyramidDev& P);   // ctx.hip
 int pyramid_prepare(sdso_ctx* ctx, int frame_slot, int w, int h, PyramidDev** out);   // ctx.hip
 int pyramid_finish_levels(sdso_ctx* ctx, PyramidDev& P);                              // ctx.hip
+
+// ---- the pieces sdso_track_make_ref_from_window (ref_window.hip) chains on the device
+// where the L->R->L chain of sdso_stereo_match_batch leaves its results (device pointers into the ctx's match batches)
+struct MatchChainOut { const float *idepth_stereo, *idepth_min, *idepth_max, *fwd_uv, *back_uv; const uint8_t *status_fwd, *status_back; };
+int stereo_match_chain_dev(sdso_ctx* ctx, int slot_a, int slot_b, const float K[4], float baseline, int mode_right_first, int n,
+                           const float* const in[6], const uint8_t* skip_fwd, MatchChainOut* out);                            // stereo.hip
+int track_make_ref_dev(sdso_ctx* ctx, int ref_slot, int frame_slot, int n, const int* d_u, const int* d_v, const float* d_idp, const float* d_wgt,
+                       int* pc_n_out, bool sync_end);                                                                         // coarse_depth.hip
+// what a BA window offers a reader of its post-state (ba.hip): SDSO_ERR_ARG for an unknown window, SDSO_ERR_STATE unless an optimize
+// call has ended on it and nothing has edited it since, it is outside a batch and none of its residuals is linearised
+struct BaRefView { const BaDev* dev; int nf, np, nr, w, h, last_frame_slot; float K[4]; };
+int ba_ref_view(sdso_ctx* ctx, int win, BaRefView* out);
 
 // ------------------------------------------------------------------ device helpers
 // getInterpolatedElement33 (src/util/globalFuncs.h:73-86) on the float4 image.

@@ -831,6 +831,55 @@ __global__ __launch_bounds__(256) void k_match_back_points(int n, TraceDev F, Tr
   Bk.lastTraceUV[2 * p] = 0.f; Bk.lastTraceUV[2 * p + 1] = 0.f; Bk.lastTracePixelInterval[p] = 0.f;
 }
 
+// The launch sequence of the chain on device-resident inputs: in[0..5] = u, v, idepth_min_stereo, idepth_max_stereo, and the back
+// trace's two bounds (each n floats in device memory; 2..5 may be null: 0 / NaN, a fresh ImmaturePoint), skip_fwd (optional, n bytes): 1 =
+// the point takes no trace at all (both statuses 255; its u, v must still address a readable pattern).  Enqueue only: the results stay
+// in the ctx's two match batches (*out points into them) until the next chain of this ctx.  The caller has validated the slots.
+namespace sdso {
+int stereo_match_chain_dev(sdso_ctx* ctx, int slot_a, int slot_b, const float K[4], float baseline, int mode_right_first, int n,
+                           const float* const in[6], const uint8_t* skip_fwd, MatchChainOut* out) {
+  PyramidDev& PA = ctx->pyr.find(slot_a)->second;
+  PyramidDev& PB = ctx->pyr.find(slot_b)->second;
+  const int w = PA.w[0], h = PA.h[0];
+  StereoState& S = stereo_state(ctx);
+  TraceBatch& A = S.match[0];
+  TraceBatch& Bk = S.match[1];
+  int rc = trace_reserve(ctx, A, n);
+  if (rc) return rc;
+  rc = trace_reserve(ctx, Bk, n);
+  if (rc) return rc;
+  trace_bind(A, n); trace_bind(Bk, n);
+  rc = ensure_plane0(ctx, PA);
+  if (rc) return rc;
+  rc = ensure_plane0(ctx, PB);
+  if (rc) return rc;
+  auto geom = [&](TraceDev& T, const float4* img, const float* plane, int mode_right) {
+    T.w = w; T.h = h; T.mode_right = mode_right; T.img = img; T.plane = plane;
+    T.fx = K[0]; T.fy = K[1]; T.cx = K[2]; T.cy = K[3]; T.baseline = baseline;
+  };
+  geom(A.T, PB.d[0], PB.plane0, mode_right_first ? 1 : 0);       // forward: points of frame A searched in frame B
+  geom(Bk.T, PA.d[0], PA.plane0, mode_right_first ? 0 : 1);      // back: points of frame B searched in frame A
+  const dim3 g1((n + 255) / 256), b1(256);
+  uint8_t* skip = Bk.bytes + 2 * (size_t)Bk.n;
+  hipLaunchKernelGGL(k_match_prepare, g1, b1, 0, ctx->stream, n, in[0], in[1], in[2], in[3], A.T);
+  hipLaunchKernelGGL(k_immature_init, g1, b1, 0, ctx->stream, PA.d[0], w, n, (const float*)A.T.u_stereo, (const float*)A.T.v_stereo,
+                     (float*)A.T.color, (float*)A.T.weights, (float*)A.T.gradH, (float*)A.T.energyTH);
+  TraceDev Tf = A.T;
+  Tf.skip = skip_fwd;
+  launch_trace_stereo(ctx, Tf, true);       // (timed under k_trace_stereo when profiling is on: the match chain's two traces)
+  hipLaunchKernelGGL(k_match_back_points, g1, b1, 0, ctx->stream, n, A.T, Bk.T, skip, in[4], in[5]);
+  hipLaunchKernelGGL(k_immature_init, g1, b1, 0, ctx->stream, PB.d[0], w, n, (const float*)Bk.T.u_stereo, (const float*)Bk.T.v_stereo,
+                     (float*)Bk.T.color, (float*)Bk.T.weights, (float*)Bk.T.gradH, (float*)Bk.T.energyTH);
+  TraceDev Tb = Bk.T;
+  Tb.skip = skip;
+  launch_trace_stereo(ctx, Tb, true);
+  SDSO_HIP(ctx, hipGetLastError());
+  out->idepth_stereo = A.T.idepth_stereo; out->idepth_min = A.T.idepth_min_stereo; out->idepth_max = A.T.idepth_max_stereo;
+  out->fwd_uv = A.T.lastTraceUV; out->back_uv = Bk.T.lastTraceUV; out->status_fwd = A.T.status; out->status_back = Bk.T.status;
+  return SDSO_OK;
+}
+}  // namespace sdso
+
 extern "C" int sdso_stereo_match_batch(sdso_ctx* ctx, int slot_a, int slot_b, const float K[4], float baseline, int mode_right_first,
                                        sdso_stereo_match_t* M) {
   if (!ctx) return SDSO_ERR_STATE;
@@ -844,56 +893,26 @@ extern "C" int sdso_stereo_match_batch(sdso_ctx* ctx, int slot_a, int slot_b, co
   SDSO_REQUIRE(ctx, M->u && M->v, "null point arrays");
   for (int i = 0; i < n; i++)
     SDSO_REQUIRE(ctx, M->u[i] >= 2 && M->v[i] >= 2 && M->u[i] < w - 3 && M->v[i] < h - 3, "immature point too close to the image border");
-  StereoState& S = stereo_state(ctx);
-  TraceBatch& A = S.match[0];
-  TraceBatch& Bk = S.match[1];
-  int rc = trace_reserve(ctx, A, n);
-  if (rc) return rc;
-  rc = trace_reserve(ctx, Bk, n);
-  if (rc) return rc;
-  trace_bind(A, n); trace_bind(Bk, n);
-  rc = ensure_plane0(ctx, ia->second);
-  if (rc) return rc;
-  rc = ensure_plane0(ctx, ib->second);
-  if (rc) return rc;
-  auto geom = [&](TraceDev& T, const float4* img, const float* plane, int mode_right) {
-    T.w = w; T.h = h; T.mode_right = mode_right; T.img = img; T.plane = plane;
-    T.fx = K[0]; T.fy = K[1]; T.cx = K[2]; T.cy = K[3]; T.baseline = baseline;
-  };
-  geom(A.T, ib->second.d[0], ib->second.plane0, mode_right_first ? 1 : 0);       // forward: points of frame A searched in frame B
-  geom(Bk.T, ia->second.d[0], ia->second.plane0, mode_right_first ? 0 : 1);      // back: points of frame B searched in frame A
-  // host inputs -> device (the unused tail of the back batch's float blob is the staging area: 32N..36N)
-  float* stage = Bk.blob + 32 * (size_t)Bk.n;
+  // host inputs -> device
   const float* d_in[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   const float* h_in[6] = {M->u, M->v, M->idepth_min_stereo, M->idepth_max_stereo, M->back_idepth_min_stereo, M->back_idepth_max_stereo};
-  rc = ensure_scratch(ctx, sizeof(float) * 6 * (size_t)n);
+  int rc = ensure_scratch(ctx, sizeof(float) * 6 * (size_t)n);
   if (rc) return rc;
-  (void)stage;
   for (int k = 0; k < 6; k++)
     if (h_in[k]) {
       float* d = (float*)ctx->scratch + (size_t)k * n;
       SDSO_HIP(ctx, hipMemcpyAsync(d, h_in[k], sizeof(float) * n, hipMemcpyHostToDevice, ctx->stream));
       d_in[k] = d;
     }
-  const dim3 g1((n + 255) / 256), b1(256), gw((n + 3) / 4);
-  uint8_t* skip = Bk.bytes + 2 * (size_t)Bk.n;
-  hipLaunchKernelGGL(k_match_prepare, g1, b1, 0, ctx->stream, n, d_in[0], d_in[1], d_in[2], d_in[3], A.T);
-  hipLaunchKernelGGL(k_immature_init, g1, b1, 0, ctx->stream, ia->second.d[0], w, n, (const float*)A.T.u_stereo, (const float*)A.T.v_stereo,
-                     (float*)A.T.color, (float*)A.T.weights, (float*)A.T.gradH, (float*)A.T.energyTH);
-  launch_trace_stereo(ctx, A.T, true);      // (timed under k_trace_stereo when profiling is on: the match chain's two traces)
-  hipLaunchKernelGGL(k_match_back_points, g1, b1, 0, ctx->stream, n, A.T, Bk.T, skip, d_in[4], d_in[5]);
-  hipLaunchKernelGGL(k_immature_init, g1, b1, 0, ctx->stream, ib->second.d[0], w, n, (const float*)Bk.T.u_stereo, (const float*)Bk.T.v_stereo,
-                     (float*)Bk.T.color, (float*)Bk.T.weights, (float*)Bk.T.gradH, (float*)Bk.T.energyTH);
-  TraceDev Tb = Bk.T;
-  Tb.skip = skip;
-  launch_trace_stereo(ctx, Tb, true);
-  SDSO_HIP(ctx, hipGetLastError());
+  MatchChainOut o;
+  rc = stereo_match_chain_dev(ctx, slot_a, slot_b, K, baseline, mode_right_first, n, d_in, nullptr, &o);
+  if (rc) return rc;
 #define DN(dst, src, cnt) if (dst) SDSO_HIP(ctx, hipMemcpyAsync((dst), (src), sizeof(float) * (size_t)(cnt), hipMemcpyDeviceToHost, ctx->stream))
-  DN(M->idepth_stereo, A.T.idepth_stereo, n); DN(M->idepth_min_out, A.T.idepth_min_stereo, n); DN(M->idepth_max_out, A.T.idepth_max_stereo, n);
-  DN(M->fwd_uv, A.T.lastTraceUV, 2 * n); DN(M->back_uv, Bk.T.lastTraceUV, 2 * n);
+  DN(M->idepth_stereo, o.idepth_stereo, n); DN(M->idepth_min_out, o.idepth_min, n); DN(M->idepth_max_out, o.idepth_max, n);
+  DN(M->fwd_uv, o.fwd_uv, 2 * n); DN(M->back_uv, o.back_uv, 2 * n);
 #undef DN
-  if (M->status_fwd) SDSO_HIP(ctx, hipMemcpyAsync(M->status_fwd, A.T.status, n, hipMemcpyDeviceToHost, ctx->stream));
-  if (M->status_back) SDSO_HIP(ctx, hipMemcpyAsync(M->status_back, Bk.T.status, n, hipMemcpyDeviceToHost, ctx->stream));
+  if (M->status_fwd) SDSO_HIP(ctx, hipMemcpyAsync(M->status_fwd, o.status_fwd, n, hipMemcpyDeviceToHost, ctx->stream));
+  if (M->status_back) SDSO_HIP(ctx, hipMemcpyAsync(M->status_back, o.status_back, n, hipMemcpyDeviceToHost, ctx->stream));
   SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SDSO_OK;
 }

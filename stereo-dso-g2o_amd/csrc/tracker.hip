@@ -350,8 +350,10 @@ extern "C" int sdso_track_set_ref(sdso_ctx* ctx, int ref_slot, int lvl, int n, c
   SDSO_REQUIRE(ctx, lvl >= 0 && lvl < SDSO_PYR_LEVELS && n >= 0, "bad level / n");
   SDSO_REQUIRE(ctx, n == 0 || (pc_u && pc_v && pc_idepth && pc_color), "null pc arrays");
   RefDev& R = ctx->refs[ref_slot];
+  int rc0 = ref_counts(ctx, R);
+  if (rc0) return rc0;
   if (R.pc[lvl]) { SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream)); hipFree(R.pc[lvl]); R.pc[lvl] = nullptr; }
-  R.n[lvl] = n;
+  R.n[lvl] = n; R.cap[lvl] = n;
   if (n == 0) return SDSO_OK;
   std::vector<float4> h(n);
   for (int i = 0; i < n; i++) h[i] = make_float4(pc_u[i], pc_v[i], pc_idepth[i], pc_color[i]);
@@ -367,7 +369,7 @@ extern "C" int sdso_track_release_ref(sdso_ctx* ctx, int ref_slot) {
   if (it == ctx->refs.end()) return SDSO_OK;
   SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   sdso::release_g2o_ref(ctx, ref_slot);
-  for (int l = 0; l < SDSO_PYR_LEVELS; l++) if (it->second.pc[l]) hipFree(it->second.pc[l]);
+  ref_free(it->second);
   ctx->refs.erase(it);
   return SDSO_OK;
 }
@@ -377,6 +379,8 @@ static int resolve_prob(sdso_ctx* ctx, int ref_slot, int frame_slot, const sdso_
   SDSO_REQUIRE(ctx, ir != ctx->refs.end(), "unknown ref slot");
   auto ip = ctx->pyr.find(frame_slot);
   SDSO_REQUIRE(ctx, ip != ctx->pyr.end(), "unknown frame slot");
+  int rc0 = ref_counts(ctx, ir->second);
+  if (rc0) return rc0;
   const int lvl = ev.lvl;
   SDSO_REQUIRE(ctx, lvl >= 0 && lvl < ip->second.levels, "level not in pyramid");
   // the kernel indexes the image with (w,h) from the eval: they must be the uploaded level's size
@@ -1219,6 +1223,8 @@ static int resolve_job(sdso_ctx* ctx, int ref_slot, int frame_slot, const sdso_t
   auto ip = ctx->pyr.find(frame_slot);
   SDSO_REQUIRE(ctx, ip != ctx->pyr.end(), "unknown frame slot");
   SDSO_REQUIRE(ctx, p.coarsestLvl < ip->second.levels, "level not in pyramid");
+  int rc0 = ref_counts(ctx, ir->second);
+  if (rc0) return rc0;
   for (int l = 0; l < SDSO_PYR_LEVELS; l++) { J.pc[l] = nullptr; J.img[l] = nullptr; J.n[l] = 0; }
   for (int l = 0; l <= p.coarsestLvl; l++) {
     // the kernel indexes the image with (w,h) of the params: they must be the uploaded level's size

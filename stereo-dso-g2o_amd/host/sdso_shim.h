@@ -199,6 +199,33 @@ class CoarseTracker {
     }
     installRef_(lastRef, n, iu.data(), iv.data(), nid.data(), wgt.data());
   }
+  // The same member on the DEVICE-RESIDENT window of `ba` (a WindowedBA whose optimize() has just run): STEP1's walk over the pointer graph,
+  // the uploads of the match batch, its download, the accept rule and the uploads of sdso_track_make_ref all stay on the device
+  // (sdso_track_make_ref_from_window).  What remains here is the ORDER: STEP1 adds the points of one pixel in frameHessians[*]->pointHessians
+  // order (:290-354), which differs from the window's order (EFFrame::points) once flagPointsForRemoval's compaction (FullSystem.cpp:1047-1053)
+  // and removePoint's swap-with-back (EnergyFunctional.cpp:755-771) have both run — every pointHessian is looked up in the window and the
+  // indices travel as point_order.  K is the window's calibration after the optimize (= Hcalib.fxl() .. cyl()), lastRef its last frame.
+  // Nothing on this path reads PointFrameResidual::centerProjectedTo / projectedTo: see WindowedBA::writeBackProjections.
+  int n_points = 0, n_border = 0;                            // of the latest call: points splatted; of them, too close to the border for stereo
+  template <class WindowedBAT, class FrameHessianT>
+  void setCoarseTrackingRef(WindowedBAT& ba, std::vector<FrameHessianT*> frameHessians, FrameHessianT* fh_right) {
+    if (frameHessians.empty() || !slot_of) throw Error("setCoarseTrackingRef: no frames / slot_of not set");
+    FrameHessianT* lastRef = frameHessians.back();
+    std::vector<int> order;
+    for (FrameHessianT* fh : frameHessians)
+      for (auto* ph : fh->pointHessians) {
+        const int i = ba.pointIndexOf(ph->efPoint);
+        if (i < 0) throw Error("setCoarseTrackingRef: a pointHessian is not part of the device window (a point the WindowedBA was not told about?)");
+        order.push_back(i);
+      }
+    dev_.check(sdso_track_make_ref_from_window(dev_.ctx(), ref_slot_, ba.win(), slot_of(fh_right), baseline, order.data(), (int)order.size(), &n_points,
+                                               &n_border, pc_n), "sdso_track_make_ref_from_window");
+    refFrameID = lastRef->shell->id;                         // :821-825
+    lastRef_aff_g2l = lastRef->aff_g2l();
+    prm_.ref_exposure = lastRef->ab_exposure;
+    prm_.ref_aff_g2l.a = lastRef_aff_g2l.a; prm_.ref_aff_g2l.b = lastRef_aff_g2l.b;
+    firstCoarseRMSE = -1;
+  }
   // void setCTRefForFirstFrame(std::vector<FrameHessian*> frameHessians) — CoarseTracker.cpp:794-805 with makeCoarseDepthForFirstFrame
   // (:138-271): the first keyframe's own points at int(u + 0.5f), their idepth, no stereo refinement; STEP2-5 are makeCoarseDepthL0's.
   template <class FrameHessianT>
@@ -558,8 +585,8 @@ class WindowedBA {
     std::memset(&P, 0, sizeof(P));
     P.idepth = idp.data(); P.step = pstep.data(); P.HdiF = hdi.data(); P.bdSumF = bds.data(); P.idepth_hessian = idh.data();
     P.maxRelBaseline = mrb.data(); P.numGoodResiduals = ngood.data();
-    P.state_state = rs.data(); P.isActiveAndIsGoodNEW = act.data(); P.state_energy = energy.data(); P.centerProjectedTo = cpt.data();
-    P.projectedTo = prj.data(); P.toRemove = rem.data();
+    P.state_state = rs.data(); P.isActiveAndIsGoodNEW = act.data(); P.state_energy = energy.data(); P.toRemove = rem.data();
+    if (writeBackProjections) { P.centerProjectedTo = cpt.data(); P.projectedTo = prj.data(); }
     P.state = st.data(); P.state_zero = stz.data(); P.evalPT = ev.data(); P.frame_step = fstep.data(); P.frameEnergyTH = eth.data();
     P.lastX = lx.data(); P.lastHS = lhs.data(); P.lastbS = lbs.data();
     dev_.check(sdso_ba_get_post_state(dev_.ctx(), win_, &P), "sdso_ba_get_post_state");
@@ -602,7 +629,7 @@ class WindowedBA {
       pfr->state_NewState = static_cast<ResStateT>(rs[i]);
       pfr->state_energy = energy[i]; pfr->state_NewEnergy = energy[i];
       r->isActiveAndIsGoodNEW = act[i] != 0;
-      if (act[i]) {
+      if (act[i] && writeBackProjections) {
         for (int k = 0; k < 3; k++) pfr->centerProjectedTo[k] = cpt[(size_t)i * 3 + k];
         for (int k = 0; k < 8; k++) { pfr->projectedTo[k][0] = prj[(size_t)i * 16 + 2 * k]; pfr->projectedTo[k][1] = prj[(size_t)i * 16 + 2 * k + 1]; }
       }
@@ -638,6 +665,13 @@ class WindowedBA {
     return (float)out.rmse;
   }
   int lastRemoved = 0;
+  // false: optimize() does not fetch PointFrameResidual::centerProjectedTo / projectedTo (nr x 19 floats evaluated and downloaded by
+  // sdso_ba_get_post_state) and leaves them as they were.  Their only reader on the keyframe path is makeCoarseDepthL0, so switch it off
+  // exactly when the tracking reference comes from CoarseTracker::setCoarseTrackingRef(ba, ...) and no other code of the caller reads them.
+  bool writeBackProjections = true;
+  int win() const { return win_; }
+  // index of an EFPoint in the device window's point order, -1 when it is not part of it
+  int pointIndexOf(const void* efPoint) const { auto it = point_index_.find(efPoint); return it == point_index_.end() ? -1 : it->second; }
   // EnergyFunctional::marginalizePointsF() (EnergyFunctional.cpp:663-736): points with stateFlag == PS_MARGINALIZE; updates ef->HM / ef->bM /
   // ef->resInM.  The re-linearisation + fixLinearizationF that FullSystem::flagPointsForRemoval runs on those points beforehand
   // (FullSystem.cpp:1012-1021) is part of the call.  Call upload() first: optimize() dropped residuals and the reference drops points in between

@@ -470,6 +470,8 @@ def load():
     L.sdso_track_newest_coarse_batch.argtypes = [vp, C.c_int, c_int_p, c_int_p, C.POINTER(TrackParams), C.POINTER(SE3), C.POINTER(Aff), C.POINTER(TrackResult)]
     L.sdso_track_make_ref.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_float_p, c_float_p, c_int_p]
     L.sdso_track_get_ref.argtypes = [vp, C.c_int, C.c_int, c_int_p, c_float_p, c_float_p, c_float_p, c_float_p]
+    L.sdso_track_make_ref_from_window.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float, c_int_p, C.c_int, c_int_p, c_int_p, c_int_p]
+    L.sdso_track_get_ref_points.argtypes = [vp, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p, c_float_p, c_u8_p, c_u8_p, c_float_p, c_float_p]
     L.sdso_trace_on_batch.argtypes = [vp, C.c_int, C.c_int, C.POINTER(TraceGeom), c_int_p, C.POINTER(TracePoints), c_u8_p]
     L.sdso_pixel_select.argtypes = [vp, C.c_int, C.c_float, C.c_int, C.c_float, c_int_p, c_float_p, c_int_p]
     L.sdso_pixel_selector_pattern.argtypes = [C.c_int, c_u8_p]
@@ -527,6 +529,7 @@ EXPORTED_SYMBOLS = [
     "sdso_undistort_make_remap", "sdso_ingest_calib_create", "sdso_ingest_calib_release", "sdso_ingest_frame",
     "sdso_imm_add_frame", "sdso_imm_trace", "sdso_imm_count", "sdso_imm_get", "sdso_imm_remove_order", "sdso_imm_remove", "sdso_imm_release_host",
     "sdso_imm_put_host", "sdso_imm_activate", "sdso_imm_activate_fetch",
+    "sdso_track_make_ref_from_window", "sdso_track_get_ref_points",
 ]
 
 
