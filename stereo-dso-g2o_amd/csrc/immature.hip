@@ -1,6 +1,7 @@
 // The device-resident immature points of a ctx (sdso_imm_*): FullSystem::makeNewTraces, traceNewCoarseKey / traceNewCoarseNonKey and
-// STEP 5 of activatePointsMT on arrays that never leave the device.  Included at the end of stereo.hip: it reuses TraceDev,
-// k_immature_init, trace_on_point, k_trace_stereo_blk (launch_trace_stereo) and the TraceBatch helpers of the matching batches.
+// STEP 5 of activatePointsMT on arrays that never leave the device.  Included at the end of stereo.hip: the searches are stereo.hip's
+// trace_on_point and k_trace_stereo_blk (the pieces of trace_dev.h), the stereo chain of the non-key trace is launched with
+// trace_pair_bind / launch_fresh_trace around this file's own prepare / back / accept kernels, and new points are written by fresh_point.
 //
 // Reference (paths under /root/reference):
 //   src/FullSystem/FullSystem.cpp:1600-1629   makeNewTraces
@@ -202,14 +203,12 @@ __device__ __forceinline__ int imm_host_of(const Args& A, int j) {
 
 // ImmaturePoint::traceOn for every point of the named hosts, in place: one wave per point, the body of k_trace_on
 __global__ __launch_bounds__(256) void k_imm_trace_on(ImmTraceArgs A, TraceDev base) {
-  const int wv = threadIdx.x >> 6;
-  const int j = blockIdx.x * 4 + wv;
+  const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (j >= A.ntot) return;
-  __shared__ float s_err[4][128];
   const int g = imm_host_of(A, j);
   TraceDev T = base;
   imm_bind(T, A.H[g].f, A.H[g].st, A.H[g].cap, A.H[g].n);
-  trace_on_point(T, j - A.off[g], s_err[wv], [&] {
+  trace_on_point(T, j - A.off[g], [&] {
     sdso_trace_geom_t G;
     for (int k = 0; k < 9; k++) G.KRKi[k] = A.G[g].KRKi[k];
     for (int k = 0; k < 3; k++) G.Kt[k] = A.G[g].Kt[k];
@@ -218,14 +217,6 @@ __global__ __launch_bounds__(256) void k_imm_trace_on(ImmTraceArgs A, TraceDev b
   });
 }
 
-// a fresh point parked on a harmless pixel (the constructor kernel reads valid memory, the trace kernel skips it)
-__device__ __forceinline__ void imm_fresh_point(const TraceDev& T, int j, float u, float v, float idepth_min, float imin_stereo, float imax_stereo) {
-  T.u_stereo[j] = u; T.v_stereo[j] = v;
-  T.idepth_min[j] = idepth_min;
-  T.idepth_min_stereo[j] = imin_stereo; T.idepth_max_stereo[j] = imax_stereo;
-  T.idepth_stereo[j] = 0.f; T.quality[j] = 10000.f; T.lastTraceStatus[j] = IPS_UNINITIALIZED;
-  T.lastTraceUV[2 * j] = 0.f; T.lastTraceUV[2 * j + 1] = 0.f; T.lastTracePixelInterval[j] = 0.f;
-}
 // counts[k] += the lanes of the wave with `on` (one atomic per wave; every lane of the wave calls)
 __device__ __forceinline__ void imm_count(int* __restrict__ counts, int k, bool on) {
   const int c = __popcll(__ballot(on));
@@ -243,7 +234,7 @@ __global__ __launch_bounds__(256) void k_imm_stereo_prepare(ImmTraceArgs A, int 
   const float* f = A.H[g].f;
   const size_t N = (size_t)A.H[g].cap;
   bool run = false, unreadable = false;
-  float fu = 8.f, fv = 8.f, pm = 0.f, pM = NAN;
+  float fu = 8.f, fv = 8.f, pm = 0.f, pM = NAN;   // a point that takes no trace is parked on a harmless pixel: the constructor kernel reads valid memory
   if (in && A.H[g].st[i] == IPS_GOOD) {
     const float tu = f[IMM_UV * N + (size_t)i * 2], tv = f[IMM_UV * N + (size_t)i * 2 + 1];
     if (imm_readable(tu, tv, w, h)) {
@@ -259,7 +250,7 @@ __global__ __launch_bounds__(256) void k_imm_stereo_prepare(ImmTraceArgs A, int 
   if (!in) return;
   skip[j] = run ? 0 : 1;
   pmin[j] = pm; pmax[j] = pM;
-  imm_fresh_point(F, j, fu, fv, pm, pm, pM);   // :681-686: idepth_min and idepth_min_stereo are both the projection
+  fresh_point(F, j, fu, fv, pm, pm, pM);   // :681-686: idepth_min and idepth_min_stereo are both the projection
 }
 // :691-697: the back points at the forward trace's lastTraceUV, with the projected interval again
 __global__ __launch_bounds__(256) void k_imm_back_points(int n, int w, int h, TraceDev F, TraceDev Bk, const uint8_t* __restrict__ skipF, uint8_t* __restrict__ skipB,
@@ -274,7 +265,7 @@ __global__ __launch_bounds__(256) void k_imm_back_points(int n, int w, int h, Tr
       if (imm_readable(tu, tv, w, h)) { run = true; bu = tu; bv = tv; }
     }
     skipB[j] = run ? 0 : 1;
-    imm_fresh_point(Bk, j, bu, bv, 0.f, run ? pmin[j] : 0.f, run ? pmax[j] : NAN);
+    fresh_point(Bk, j, bu, bv, 0.f, run ? pmin[j] : 0.f, run ? pmax[j] : NAN);
   }
   imm_count(counts, IMM_C_FWD_GOOD, good);
   imm_count(counts, IMM_C_UNREADABLE, good && !run);
@@ -468,11 +459,7 @@ extern "C" int sdso_imm_trace(sdso_ctx* ctx, int frame_slot, int right_slot, int
   int rc = ensure_plane0(ctx, il->second);
   if (rc) return rc;
   if (nonkey) {
-    rc = ensure_plane0(ctx, ir->second);
-    if (rc) return rc;
-    rc = trace_reserve(ctx, S.fwd, n);
-    if (rc) return rc;
-    rc = trace_reserve(ctx, S.back, n);
+    rc = trace_pair_bind(ctx, S.fwd, S.back, n, il->second, ir->second, K, baseline, 1, 0);
     if (rc) return rc;
   }
   SDSO_HIP(ctx, hipMemsetAsync(S.d_counts, 0, sizeof(int) * SDSO_IMM_NCOUNTS, ctx->stream));
@@ -481,15 +468,8 @@ extern "C" int sdso_imm_trace(sdso_ctx* ctx, int frame_slot, int right_slot, int
   base.img = il->second.d[0]; base.plane = il->second.plane0;
   launch_timed(ctx, "k_imm_trace_on", 1, k_imm_trace_on, dim3((n + 3) / 4), dim3(256), A, base);
   if (nonkey) {
-    trace_bind(S.fwd, n); trace_bind(S.back, n);
-    TraceDev& F = S.fwd.T;
-    TraceDev& Bk = S.back.T;
-    auto cam = [&](TraceDev& T, const PyramidDev& P, int mode_right) {
-      T.w = w; T.h = h; T.mode_right = mode_right; T.img = P.d[0]; T.plane = P.plane0;
-      T.fx = K[0]; T.fy = K[1]; T.cx = K[2]; T.cy = K[3]; T.baseline = baseline;
-    };
-    cam(F, ir->second, 1);     // forward: points of the new left frame searched in the right one
-    cam(Bk, il->second, 0);    // back: points of the right frame searched in the left one
+    const TraceDev& F = S.fwd.T;     // forward: points of the new left frame searched in the right one
+    const TraceDev& Bk = S.back.T;   // back: points of the right frame searched in the left one
     uint8_t* skipF = S.fwd.bytes + 2 * (size_t)S.fwd.n;
     uint8_t* skipB = S.back.bytes + 2 * (size_t)S.back.n;
     float* pmin = S.fwd.blob + 32 * (size_t)S.fwd.n;
@@ -498,17 +478,9 @@ extern "C" int sdso_imm_trace(sdso_ctx* ctx, int frame_slot, int right_slot, int
     for (int k = 0; k < 9; k++) C.Ki[k] = Ki[k];
     const dim3 g1((n + 255) / 256), b1(256);
     launch_timed(ctx, "k_imm_stereo_prepare", 2, k_imm_stereo_prepare, g1, b1, A, w, h, F, skipF, pmin, pmax, S.d_counts);
-    launch_timed(ctx, "k_immature_init", 2, k_immature_init, g1, b1, (const float4*)il->second.d[0], w, n, (const float*)F.u_stereo, (const float*)F.v_stereo,
-                 (float*)F.color, (float*)F.weights, (float*)F.gradH, (float*)F.energyTH);
-    TraceDev Ff = F;
-    Ff.skip = skipF;
-    launch_trace_stereo(ctx, Ff, true);
+    launch_fresh_trace(ctx, F, il->second, skipF);
     launch_timed(ctx, "k_imm_back_points", 2, k_imm_back_points, g1, b1, n, w, h, F, Bk, (const uint8_t*)skipF, skipB, (const float*)pmin, (const float*)pmax, S.d_counts);
-    launch_timed(ctx, "k_immature_init", 2, k_immature_init, g1, b1, (const float4*)ir->second.d[0], w, n, (const float*)Bk.u_stereo, (const float*)Bk.v_stereo,
-                 (float*)Bk.color, (float*)Bk.weights, (float*)Bk.gradH, (float*)Bk.energyTH);
-    TraceDev Bb = Bk;
-    Bb.skip = skipB;
-    launch_trace_stereo(ctx, Bb, true);
+    launch_fresh_trace(ctx, Bk, ir->second, skipB);
     launch_timed(ctx, "k_imm_accept", 2, k_imm_accept, g1, b1, A, C, F, Bk, (const uint8_t*)skipB, S.d_counts);
   }
   SDSO_HIP(ctx, hipGetLastError());

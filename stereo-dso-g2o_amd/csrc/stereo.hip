@@ -1,60 +1,25 @@
-// Static stereo on gfx950: ImmaturePoint construction and ImmaturePoint::traceStereo for a batch
-// of points in one launch.
+// Static stereo on gfx950: ImmaturePoint construction, ImmaturePoint::traceStereo and ImmaturePoint::traceOn for a batch of points in one
+// launch, the left-right-left matching chain and point activation.
 //
 // Reference (paths under /root/reference):
 //   src/FullSystem/ImmaturePoint.cpp:33-62    ImmaturePoint::ImmaturePoint (colour patch, weights, gradH)
 //   src/FullSystem/ImmaturePoint.cpp:94-451   ImmaturePoint::traceStereo; the sub-pixel Gauss-Newton is
 //                                             the DSO-native one (twin in traceOn, :707-769)
+//   src/FullSystem/ImmaturePoint.cpp:459-828  ImmaturePoint::traceOn
 //
-// Kernel design: one 64-lane wave per point.  The search geometry (a few dozen scalar flops) is
-// evaluated redundantly by every lane; the discrete epipolar search puts ONE search step on each
-// lane (numSteps <= 99 -> at most two passes), so the 8-pixel x 4-tap gathers of neighbouring
-// steps hit the same image rows and are served from L1/L2; best / second-best are wave
-// reductions with the reference's first-minimum tie rule; the GN refinement evaluates the 8
-// pattern pixels on lanes 0..7 and sums them in pattern order.  Per-point arithmetic keeps the
-// reference's operation order (no FP contraction) => statuses, bestIdx and all outputs are
-// bit-identical to the CPU path.
+// Layout: trace_dev.h states the epipolar search once (search line, step energy, first minimum, Gauss-Newton terms and advance, interval)
+// together with TraceDev, the constants and the fresh-point writer.  This file has the two kernels that run it — k_trace_stereo_blk (a
+// workgroup per 16 points) and trace_on_point / k_trace_on (a wave per point), which differ only in lane layout and in where the geometry
+// comes from —, the TraceBatch helpers, the launch sequence of a trace of fresh points (trace_pair_bind, launch_fresh_trace) and the
+// C-ABI.  immature.hip, included at the end, runs the same kernels on the resident points.  Per-point arithmetic keeps the reference's
+// operation order (no FP contraction) => statuses, bestIdx and all outputs are bit-identical to the CPU path.
 #include "sdso_internal.h"
 #include "distmap_dev.h"
+#include "trace_dev.h"
 #include <algorithm>
 #include <cmath>
 
 using namespace sdso;
-
-namespace sdso {
-
-__constant__ int c_pat[8][2] = {{0, -2}, {-1, -1}, {1, -1}, {-2, 0}, {0, 0}, {2, 0}, {-1, 1}, {0, 2}};
-constexpr float kMaxPixSearch = 0.027f, kTraceStepsize = 1.0f, kTraceGNThreshold = 0.1f, kTraceExtraSlack = 1.2f,
-                kTraceSlackInterval = 1.5f, kTraceMinImprovement = 2.f, kOutlierTH = 144.f;
-constexpr int kTraceGNIterations = 3, kMinTraceTestRadius = 2;
-enum { IPS_GOOD = 0, IPS_OOB, IPS_OUTLIER, IPS_SKIPPED, IPS_BADCONDITION, IPS_UNINITIALIZED };
-
-struct TraceDev {
-  int n, w, h, mode_right;
-  float fx, fy, cx, cy, baseline;
-  const float4* img;
-  const float* plane;   // level-0 intensities only (discrete search)
-  float *u_stereo, *v_stereo, *idepth_min, *idepth_min_stereo, *idepth_max_stereo, *idepth_stereo;
-  const float *color, *weights, *gradH, *energyTH;
-  float* quality; uint8_t* lastTraceStatus; float* lastTraceUV; float* lastTracePixelInterval;
-  uint8_t* status;
-  const uint8_t* skip;   // optional: 1 = leave the point alone (status 255)
-};
-
-// getInterpolatedElement33BiLin (src/util/globalFuncs.h:160-184)
-__device__ __forceinline__ float3 interp33BiLin(const float4* __restrict__ img, float x, float y, int width) {
-  const int ix = (int)x, iy = (int)y;
-  const float4* bp = img + ix + iy * width;
-  const float tl = bp[0].x, tr = bp[1].x, bl = bp[width].x, br = bp[width + 1].x;
-  const float dx = x - ix, dy = y - iy;
-  const float topInt = dx * tr + (1 - dx) * tl;
-  const float botInt = dx * br + (1 - dx) * bl;
-  const float leftInt = dy * bl + (1 - dy) * tl;
-  const float rightInt = dy * br + (1 - dy) * tr;
-  return make_float3(dx * rightInt + (1 - dx) * leftInt, rightInt - leftInt, botInt - topInt);
-}
-
-}  // namespace sdso
 
 __global__ __launch_bounds__(256) void k_immature_init(const float4* __restrict__ img, int w, int n, const float* __restrict__ u,
                                                        const float* __restrict__ v, float* __restrict__ color, float* __restrict__ weights,
@@ -77,11 +42,12 @@ __global__ __launch_bounds__(256) void k_immature_init(const float4* __restrict_
 }
 
 // ImmaturePoint::traceStereo (ImmaturePoint.cpp:94-451), block organisation: a 256-thread workgroup owns PTS (16) points.
-//   phase 1  thread t < 64 : the search geometry of point t, one LANE per point (the reference's scalar code; every early exit of
-//                            ImmaturePoint.cpp:118-238 is a per-lane exit) -> numSteps, start, direction in LDS
+//   phase 1  thread t < PTS: the search line of point t, one LANE per point (the reference's scalar code; every early exit of
+//                            ImmaturePoint.cpp:118-238 is a per-lane exit) -> numSteps, the steps' positions, direction in LDS
 //   phase 2  wave w        : the discrete searches of its points, one after the other, lanes = steps
-//   phase 3  thread t < 64 : sub-pixel refinement of point t with the 8 pattern pixels in a serial loop (the reference's order by
-//                            construction), interval update, outputs
+//   phase 3a lane (pt, px) : sub-pixel refinement, the 8 pattern pixels of a point on 8 neighbouring lanes
+//   phase 3b thread t < PTS: quality, interval update, outputs
+// The pieces are those of trace_dev.h, shared with trace_on_point below.
 // (Rounds 1-3 ran one wave per point — every instruction of the geometry at 1 / 64 and of the refinement at 8 / 64 lanes, VALU-issue bound
 // at 1 350 VALU instructions per point — and kept that kernel, an LDS-band variant of it and an 8-waves-per-SIMD build for A/B until
 // round 5: 52-57 us against 33 us per 20 000 points, profiles/README.md.)  Same expressions, same operation order as the reference:
@@ -112,11 +78,12 @@ __global__ __launch_bounds__(256) void k_trace_stereo_blk(TraceDev T) {
   const int i = blockIdx.x * PTS + t;
   const float4* __restrict__ dI = T.img;
   const int wG0 = T.w, hG0 = T.h;
+  const TracePatStereo pat;
   bool live = false;                                            // the point goes on to the search and the refinement
   // per-lane state that survives the barriers (thread t of phase 1 is thread t of phase 3)
-  float u_stereo = 0, v_stereo = 0, idepth_min_stereo = 0, idepth_max_stereo = 0, energyTH = 0, quality = 0, errorInPixel = 0, dx = 0, dy = 0, bf = 0;
+  float u_stereo = 0, energyTH = 0, quality = 0, bf = 0;
   float Kt[3] = {0, 0, 0}, pr[3] = {0, 0, 0};
-  int numSteps = 0;
+  TraceLine L = {};
   uint8_t prevStatus = 0;
   auto finish = [&](int st, float uvx, float uvy, float interval, bool writeUV) {
     T.lastTraceStatus[i] = (uint8_t)st;
@@ -128,11 +95,9 @@ __global__ __launch_bounds__(256) void k_trace_stereo_blk(TraceDev T) {
     s_steps[t] = 0;
     if (i < T.n) {
       if (T.skip && T.skip[i]) { if (T.status) T.status[i] = 255; }
-      else do {
-        u_stereo = T.u_stereo[i]; v_stereo = T.v_stereo[i];
-        idepth_min_stereo = T.idepth_min_stereo[i]; idepth_max_stereo = T.idepth_max_stereo[i];
-        const float* gradH = T.gradH + (size_t)i * 4;
-        const float idepth_min = T.idepth_min[i];
+      else {
+        u_stereo = T.u_stereo[i];
+        const float v_stereo = T.v_stereo[i];
         energyTH = T.energyTH[i];
         quality = T.quality[i];
         prevStatus = T.lastTraceStatus[i];
@@ -144,71 +109,22 @@ __global__ __launch_bounds__(256) void k_trace_stereo_blk(TraceDev T) {
         pr[0] = (1.0f * u_stereo + 0.0f * v_stereo) + 0.0f * 1.0f;
         pr[1] = (0.0f * u_stereo + 1.0f * v_stereo) + 0.0f * 1.0f;
         pr[2] = (0.0f * u_stereo + 0.0f * v_stereo) + 1.0f * 1.0f;
-        float ptpMin[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++) ptpMin[k] = pr[k] + Kt[k] * idepth_min_stereo;
-        const float uMin = ptpMin[0] / ptpMin[2];
-        const float vMin = ptpMin[1] / ptpMin[2];
-        if (!(uMin > 4 && vMin > 4 && uMin < wG0 - 5 && vMin < hG0 - 5)) { finish(IPS_OOB, -1, -1, 0, true); break; }
-        float dist, uMax, vMax, ptpMax[3];
-        const float maxPixSearch = (wG0 + hG0) * kMaxPixSearch;
-        const bool finiteMax = isfinite(idepth_max_stereo);
-        if (finiteMax) {
-#pragma unroll
-          for (int k = 0; k < 3; k++) ptpMax[k] = pr[k] + Kt[k] * idepth_max_stereo;
-          uMax = ptpMax[0] / ptpMax[2];
-          vMax = ptpMax[1] / ptpMax[2];
-          if (!(uMax > 4 && vMax > 4 && uMax < wG0 - 5 && vMax < hG0 - 5)) { finish(IPS_OOB, -1, -1, 0, true); break; }
-          dist = (uMin - uMax) * (uMin - uMax) + (vMin - vMax) * (vMin - vMax);
-          dist = sqrtf(dist);
-          if (dist < kTraceSlackInterval) { finish(IPS_SKIPPED, 0, 0, 0, false); break; }
-        } else {
-          dist = maxPixSearch;
-#pragma unroll
-          for (int k = 0; k < 3; k++) ptpMax[k] = pr[k] + Kt[k] * 0.01f;
-          uMax = ptpMax[0] / ptpMax[2];
-          vMax = ptpMax[1] / ptpMax[2];
-          const float ddx = uMax - uMin;
-          const float ddy = vMax - vMin;
-          const float d = 1.0f / sqrtf(ddx * ddx + ddy * ddy);
-          uMax = uMin + dist * ddx * d;
-          vMax = vMin + dist * ddy * d;
-          if (!(uMax > 4 && vMax > 4 && uMax < wG0 - 5 && vMax < hG0 - 5)) { finish(IPS_OOB, -1, -1, 0, true); break; }
+        const int st = trace_line(pr, Kt, T.idepth_min[i], T.idepth_min_stereo[i], T.idepth_max_stereo[i], T.gradH + (size_t)i * 4, wG0, hG0, L);
+        if (st == IPS_OOB) finish(IPS_OOB, -1, -1, 0, true);
+        else if (st != kTraceSearch) finish(st, 0, 0, 0, false);   // SKIPPED, BADCONDITION: lastTraceUV stays
+        else {
+          s_steps[t] = L.numSteps > 0 ? L.numSteps : 0;
+          s_dx[t] = L.dx; s_dy[t] = L.dy;
+          float px = L.ptx0, py = L.pty0;
+          for (int k = 0; k < L.numSteps; k++) { s_px[t * kStepLd + k] = px; s_py[t * kStepLd + k] = py; px += L.dx; py += L.dy; }
+          live = true;
         }
-        if (!(idepth_min < 0 || (ptpMin[2] > 0.75 && ptpMin[2] < 1.5))) { finish(IPS_OOB, -1, -1, 0, true); break; }
-        dx = kTraceStepsize * (uMax - uMin);
-        dy = kTraceStepsize * (vMax - vMin);
-        const float a = (dx * gradH[0] + dy * gradH[2]) * dx + (dx * gradH[1] + dy * gradH[3]) * dy;
-        const float b = (dy * gradH[0] + (-dx) * gradH[2]) * dy + (dy * gradH[1] + (-dx) * gradH[3]) * (-dx);
-        errorInPixel = 0.2f + 0.2f * (a + b) / a;
-        if (errorInPixel * kTraceMinImprovement > dist && finiteMax) { finish(IPS_BADCONDITION, 0, 0, 0, false); break; }
-        if (errorInPixel > 10) errorInPixel = 10;
-        dx /= dist;
-        dy /= dist;
-        if (dist > maxPixSearch) {
-          uMax = uMin + maxPixSearch * dx;
-          vMax = vMin + maxPixSearch * dy;
-          dist = maxPixSearch;
-        }
-        numSteps = 1.9999f + dist / kTraceStepsize;
-        const float randShift = uMin * 1000 - floorf(uMin * 1000);
-        const float ptx0 = uMin - randShift * dx;
-        const float pty0 = vMin - randShift * dy;
-        if (!isfinite(dx) || !isfinite(dy)) { finish(IPS_OOB, -1, -1, 0, true); break; }
-        if (numSteps >= 100) numSteps = 99;
-        s_steps[t] = numSteps > 0 ? numSteps : 0;
-        s_dx[t] = dx; s_dy[t] = dy;
-        {
-          float px = ptx0, py = pty0;
-          for (int k = 0; k < numSteps; k++) { s_px[t * kStepLd + k] = px; s_py[t * kStepLd + k] = py; px += dx; py += dy; }
-        }
-        live = true;
-      } while (false);
+      }
     }
   }
   __syncthreads();
 
-  // ---- phase 2: discrete search, one wave per point, lane = step (ptx is the reference's running sum ptx += dx)
+  // ---- phase 2: discrete search, one wave per point, lane = step
   // (unrolled over the wave's points, no branch around a point that does not search — its lanes are simply inactive — so that the
   // taps of the next point are in flight while the minimum of the current one is reduced)
 #pragma unroll
@@ -222,42 +138,11 @@ __global__ __launch_bounds__(256) void k_trace_stereo_blk(TraceDev T) {
       const int s = pass * 64 + lane;
       if (s < nsteps) {
         const float ptx = s_px[pt * kStepLd + s], pty = s_py[pt * kStepLd + s];
-        float energy = 0;
-#pragma unroll
-        for (int idx = 0; idx < 8; idx++) {
-          const float hitColor = interp31_plane(T.plane, (float)(ptx + (float)c_pat[idx][0]), (float)(pty + (float)c_pat[idx][1]), wG0);
-          if (!isfinite(hitColor)) { energy += 1e5; continue; }
-          const float residual = hitColor - (float)(1.0f * color[idx] + 0.0f);
-          const float hw = fabsf(residual) < kHuberTH ? 1 : kHuberTH / fabsf(residual);
-          energy += hw * residual * residual * (2 - hw);
-        }
-        myE[pass] = energy; myX[pass] = ptx; myY[pass] = pty;
+        myE[pass] = trace_step_energy(pat, T.plane, wG0, color, ptx, pty); myX[pass] = ptx; myY[pass] = pty;
       }
     }
-    // first minimum (the reference takes strictly smaller energies only, in step order)
-    float bE = 1e10f; int bI = -1; float bX = 0, bY = 0;
-#pragma unroll
-    for (int pass = 0; pass < 2; pass++) {
-      const int s = pass * 64 + lane;
-      if (s < nsteps && myE[pass] < bE) { bE = myE[pass]; bI = s; bX = myX[pass]; bY = myY[pass]; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float oE = __shfl_xor(bE, o, 64); const int oI = __shfl_xor(bI, o, 64);
-      const float oX = __shfl_xor(bX, o, 64), oY = __shfl_xor(bY, o, 64);
-      const bool take = (oI >= 0) && (bI < 0 || oE < bE || (oE == bE && oI < bI));
-      if (take) { bE = oE; bI = oI; bX = oX; bY = oY; }
-    }
-    const int bestIdx = bI;
-    float secondBest = 1e10f;
-#pragma unroll
-    for (int pass = 0; pass < 2; pass++) {
-      const int s = pass * 64 + lane;
-      if (s < nsteps && (s < bestIdx - kMinTraceTestRadius || s > bestIdx + kMinTraceTestRadius) && myE[pass] < secondBest) secondBest = myE[pass];
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) secondBest = fminf(secondBest, __shfl_xor(secondBest, o, 64));
-    if (lane == 0 && nsteps > 0) { s_bE[pt] = bE; s_bI[pt] = bI; s_bX[pt] = bX; s_bY[pt] = bY; s_second[pt] = secondBest; }
+    const TraceMin m = trace_first_min(nsteps, lane, myE, myX, myY);
+    if (lane == 0 && nsteps > 0) { s_bE[pt] = m.bE; s_bI[pt] = m.bI; s_bX[pt] = m.bX; s_bY[pt] = m.bY; s_second[pt] = m.secondBest; }
   }
   __syncthreads();
 
@@ -273,7 +158,7 @@ __global__ __launch_bounds__(256) void k_trace_stereo_blk(TraceDev T) {
     const float dx = s_dx[pl], dy = s_dy[pl];
     float bestU = s_bX[pl], bestV = s_bY[pl], bestEnergy = s_bE[pl];
     if (s_bI[pl] < 0) { bestU = 0; bestV = 0; bestEnergy = 1e10f; }
-    const float patx = (float)c_pat[idx][0], paty = (float)c_pat[idx][1];
+    const float patx = pat.ox(idx), paty = pat.oy(idx);
     if constexpr (GN_MODE == 1) {
       // fork-live refinement (ImmaturePoint.cpp:309-412): VertexUVDSO in double, 8 EdgeTracePointUVDSO (dso_g2o_edge.cpp:571-619) with
       // Huber(9), one undamped g2o Gauss-Newton step per pass, update clamped by VertexUVDSO::oplusImpl (dso_g2o_vertex.cpp:73-88)
@@ -312,46 +197,17 @@ __global__ __launch_bounds__(256) void k_trace_stereo_blk(TraceDev T) {
       bestU = U;
       bestV = V;
     } else {
-      // DSO-native GN (ImmaturePoint.cpp:707-769)
-      float uBak = bestU, vBak = bestV, stepBack = 0;
-      const float gnstepsize = 1;
-      if (kTraceGNIterations > 0) bestEnergy = 1e5;
+      TraceGN S(bestU, bestV, bestEnergy);
       for (int it = 0; it < kTraceGNIterations; it++) {
-        float tH = 0, tb = 0, te = 0;
-        int nan = 0;
-        const float3 hit = interp33(dI, (float)(bestU + patx), (float)(bestV + paty), wG0);
-        if (!isfinite(hit.x)) nan = 1;
-        else {
-          const float residual = hit.x - (1.0f * col + 0.0f);
-          const float dResdDist = dx * hit.y + dy * hit.z;
-          const float hw = fabsf(residual) < kHuberTH ? 1 : kHuberTH / fabsf(residual);
-          tH = hw * dResdDist * dResdDist;
-          tb = hw * residual * dResdDist;
-          te = wgt * wgt * hw * residual * residual * (2 - hw);
-        }
+        const TraceGNTerms g = trace_gn_terms(pat, patx, paty, dI, wG0, S.bestU, S.bestV, dx, dy, col, wgt);
         float H = 1, bb = 0, energy = 0;
-#define TR_ADD(K) { const float h_ = tr_bcast8<K>(tH), b_ = tr_bcast8<K>(tb), e_ = tr_bcast8<K>(te); const int nn = tr_bcast8<K>(nan); \
+#define TR_ADD(K) { const float h_ = tr_bcast8<K>(g.tH), b_ = tr_bcast8<K>(g.tb), e_ = tr_bcast8<K>(g.te); const int nn = tr_bcast8<K>(g.nan); \
                     if (nn) energy += 1e5; else { H += h_; bb += b_; energy += e_; } }
         TR_ALL8(TR_ADD)
 #undef TR_ADD
-        if (energy > bestEnergy) {
-          stepBack *= 0.5;
-          bestU = uBak + stepBack * dx;
-          bestV = vBak + stepBack * dy;
-        } else {
-          float step = -gnstepsize * bb / H;
-          if (step < -0.5) step = -0.5;
-          else if (step > 0.5) step = 0.5;
-          if (!isfinite(step)) step = 0;
-          uBak = bestU;
-          vBak = bestV;
-          stepBack = step;
-          bestU += step * dx;
-          bestV += step * dy;
-          bestEnergy = energy;
-        }
-        if (fabsf(stepBack) < kTraceGNThreshold) break;
+        if (trace_gn_advance(S, H, bb, energy, dx, dy)) break;
       }
+      bestU = S.bestU; bestV = S.bestV; bestEnergy = S.bestEnergy;
     }
     if (idx == 0) { s_rU[pl] = bestU; s_rV[pl] = bestV; s_rE[pl] = bestEnergy; }
   }
@@ -364,7 +220,7 @@ __global__ __launch_bounds__(256) void k_trace_stereo_blk(TraceDev T) {
     float bestEnergy0 = s_bE[t];
     if (s_bI[t] < 0) bestEnergy0 = 1e10f;
     const float newQuality = s_second[t] / bestEnergy0;
-    if (newQuality < quality || numSteps > 10) quality = newQuality;
+    if (newQuality < quality || L.numSteps > 10) quality = newQuality;
   }
   const float bestU = s_rU[t], bestV = s_rV[t], bestEnergy = s_rE[t];
 
@@ -372,26 +228,21 @@ __global__ __launch_bounds__(256) void k_trace_stereo_blk(TraceDev T) {
     finish(prevStatus == IPS_OUTLIER ? IPS_OOB : IPS_OUTLIER, -1, -1, 0, true);
     return;
   }
-  if (dx * dx > dy * dy) {
-    idepth_min_stereo = (pr[2] * (bestU - errorInPixel * dx) - pr[0]) / (Kt[0] - Kt[2] * (bestU - errorInPixel * dx));
-    idepth_max_stereo = (pr[2] * (bestU + errorInPixel * dx) - pr[0]) / (Kt[0] - Kt[2] * (bestU + errorInPixel * dx));
-  } else {
-    idepth_min_stereo = (pr[2] * (bestV - errorInPixel * dy) - pr[1]) / (Kt[1] - Kt[2] * (bestV - errorInPixel * dy));
-    idepth_max_stereo = (pr[2] * (bestV + errorInPixel * dy) - pr[1]) / (Kt[1] - Kt[2] * (bestV + errorInPixel * dy));
-  }
-  if (idepth_min_stereo > idepth_max_stereo) { const float tmp = idepth_min_stereo; idepth_min_stereo = idepth_max_stereo; idepth_max_stereo = tmp; }
+  float idepth_min_stereo, idepth_max_stereo;
+  trace_interval(pr, Kt, bestU, bestV, L.dx, L.dy, L.errorInPixel, idepth_min_stereo, idepth_max_stereo);
   T.idepth_min_stereo[i] = idepth_min_stereo; T.idepth_max_stereo[i] = idepth_max_stereo;
   if (!isfinite(idepth_min_stereo) || !isfinite(idepth_max_stereo) || (idepth_max_stereo < 0)) { finish(IPS_OUTLIER, -1, -1, 0, true); return; }
   T.idepth_stereo[i] = (u_stereo - bestU) / bf;
-  finish(IPS_GOOD, bestU, bestV, 2 * errorInPixel, true);
+  finish(IPS_GOOD, bestU, bestV, 2 * L.errorInPixel, true);
 }
 
-// ImmaturePoint::traceOn (ImmaturePoint.cpp:459-828): the same search along a general epipolar line.  geom[pgeom[i]] is the
-// hostToFrame geometry of the point's host; T.idepth_min_stereo / idepth_max_stereo hold idepth_min / idepth_max.
+// ImmaturePoint::traceOn (ImmaturePoint.cpp:459-828): the same search along a general epipolar line, the same pieces on one wave per
+// point: the line redundantly on every lane, lane = step in the search, pattern pixel idx on lane idx in the refinement.
+// geom[pgeom[i]] is the hostToFrame geometry of the point's host; T.idepth_min_stereo / idepth_max_stereo hold idepth_min / idepth_max.
 // trace_on_point is the body for point i of T on the calling wave; getG() yields the point's geometry (read only once the point is
 // known to be traced).  k_trace_on runs it on uploaded arrays, k_imm_trace_on (immature.hip) on the resident set.
 template <class GetG>
-__device__ __forceinline__ void trace_on_point(const TraceDev& T, const int i, volatile float* errors, GetG getG) {
+__device__ __forceinline__ void trace_on_point(const TraceDev& T, const int i, GetG getG) {
   const int lane = threadIdx.x & 63;
   if (T.skip && T.skip[i]) { if (lane == 0 && T.status) T.status[i] = 255; return; }
   const float4* __restrict__ dI = T.img;
@@ -400,8 +251,7 @@ __device__ __forceinline__ void trace_on_point(const TraceDev& T, const int i, v
   float idepth_min_stereo = T.idepth_min_stereo[i], idepth_max_stereo = T.idepth_max_stereo[i];
   const float* color = T.color + (size_t)i * 8;
   const float* weights = T.weights + (size_t)i * 8;
-  const float* gradH = T.gradH + (size_t)i * 4;
-  const float idepth_min = idepth_min_stereo, energyTH = T.energyTH[i];
+  const float energyTH = T.energyTH[i];
   float quality = T.quality[i];
   const uint8_t prevStatus = T.lastTraceStatus[i];
   if (prevStatus == IPS_OOB) { if (lane == 0 && T.status) T.status[i] = IPS_OOB; return; }   // :466-468
@@ -416,189 +266,70 @@ __device__ __forceinline__ void trace_on_point(const TraceDev& T, const int i, v
     }
   };
 
-  float Kt[3] = {G.Kt[0], G.Kt[1], G.Kt[2]};
+  const float Kt[3] = {G.Kt[0], G.Kt[1], G.Kt[2]};
   float pr[3];
 #pragma unroll
   for (int r = 0; r < 3; r++) pr[r] = (G.KRKi[r * 3 + 0] * u_stereo + G.KRKi[r * 3 + 1] * v_stereo) + G.KRKi[r * 3 + 2] * 1.0f;
-  const float aff0 = G.aff[0], aff1 = G.aff[1];
   float rot[8][2];
 #pragma unroll
-  for (int idx = 0; idx < 8; idx++) {   // Rplane * patternP  (:628, :636-637)
+  for (int idx = 0; idx < 8; idx++) {
     rot[idx][0] = G.KRKi[0] * (float)c_pat[idx][0] + G.KRKi[1] * (float)c_pat[idx][1];
     rot[idx][1] = G.KRKi[3] * (float)c_pat[idx][0] + G.KRKi[4] * (float)c_pat[idx][1];
   }
-  float ptpMin[3];
-#pragma unroll
-  for (int k = 0; k < 3; k++) ptpMin[k] = pr[k] + Kt[k] * idepth_min_stereo;
-  const float uMin = ptpMin[0] / ptpMin[2];
-  const float vMin = ptpMin[1] / ptpMin[2];
-  if (!(uMin > 4 && vMin > 4 && uMin < wG0 - 5 && vMin < hG0 - 5)) { finish(IPS_OOB, -1, -1, 0, true); return; }
-
-  float dist, uMax, vMax, ptpMax[3];
-  const float maxPixSearch = (wG0 + hG0) * kMaxPixSearch;
-  const bool finiteMax = isfinite(idepth_max_stereo);
-  if (finiteMax) {
-#pragma unroll
-    for (int k = 0; k < 3; k++) ptpMax[k] = pr[k] + Kt[k] * idepth_max_stereo;
-    uMax = ptpMax[0] / ptpMax[2];
-    vMax = ptpMax[1] / ptpMax[2];
-    if (!(uMax > 4 && vMax > 4 && uMax < wG0 - 5 && vMax < hG0 - 5)) { finish(IPS_OOB, -1, -1, 0, true); return; }
-    dist = (uMin - uMax) * (uMin - uMax) + (vMin - vMax) * (vMin - vMax);
-    dist = sqrtf(dist);
-    if (dist < kTraceSlackInterval) { finish(IPS_SKIPPED, (uMax + uMin) * 0.5f, (vMax + vMin) * 0.5f, dist, true); return; }   // :525-531
-  } else {
-    dist = maxPixSearch;
-#pragma unroll
-    for (int k = 0; k < 3; k++) ptpMax[k] = pr[k] + Kt[k] * 0.01f;
-    uMax = ptpMax[0] / ptpMax[2];
-    vMax = ptpMax[1] / ptpMax[2];
-    const float ddx = uMax - uMin;
-    const float ddy = vMax - vMin;
-    const float d = 1.0f / sqrtf(ddx * ddx + ddy * ddy);
-    uMax = uMin + dist * ddx * d;
-    vMax = vMin + dist * ddy * d;
-    if (!(uMax > 4 && vMax > 4 && uMax < wG0 - 5 && vMax < hG0 - 5)) { finish(IPS_OOB, -1, -1, 0, true); return; }
-  }
-  if (!(idepth_min < 0 || (ptpMin[2] > 0.75 && ptpMin[2] < 1.5))) { finish(IPS_OOB, -1, -1, 0, true); return; }
-
-  float dx = kTraceStepsize * (uMax - uMin);
-  float dy = kTraceStepsize * (vMax - vMin);
-  const float a = (dx * gradH[0] + dy * gradH[2]) * dx + (dx * gradH[1] + dy * gradH[3]) * dy;
-  const float b = (dy * gradH[0] + (-dx) * gradH[2]) * dy + (dy * gradH[1] + (-dx) * gradH[3]) * (-dx);
-  float errorInPixel = 0.2f + 0.2f * (a + b) / a;
-  if (errorInPixel * kTraceMinImprovement > dist && finiteMax) { finish(IPS_BADCONDITION, (uMax + uMin) * 0.5f, (vMax + vMin) * 0.5f, dist, true); return; }   // :596-603
-  if (errorInPixel > 10) errorInPixel = 10;
-  dx /= dist;
-  dy /= dist;
-  if (dist > maxPixSearch) {
-    uMax = uMin + maxPixSearch * dx;
-    vMax = vMin + maxPixSearch * dy;
-    dist = maxPixSearch;
-  }
-  int numSteps = 1.9999f + dist / kTraceStepsize;
-  const float randShift = uMin * 1000 - floorf(uMin * 1000);
-  const float ptx0 = uMin - randShift * dx;
-  const float pty0 = vMin - randShift * dy;
-  if (!isfinite(dx) || !isfinite(dy)) { finish(IPS_OOB, -1, -1, 0, true); return; }
-  if (numSteps >= 100) numSteps = 99;
+  const TracePatOn pat{rot, G.aff[0], G.aff[1]};
+  TraceLine L;
+  const int st = trace_line(pr, Kt, idepth_min_stereo, idepth_min_stereo, idepth_max_stereo, T.gradH + (size_t)i * 4, wG0, hG0, L);
+  if (st == IPS_OOB) { finish(IPS_OOB, -1, -1, 0, true); return; }
+  if (st != kTraceSearch) { finish(st, (L.uMax + L.uMin) * 0.5f, (L.vMax + L.vMin) * 0.5f, L.dist, true); return; }   // SKIPPED :525-531, BADCONDITION :596-603
+  const float dx = L.dx, dy = L.dy;
 
   // ---- discrete search: lane = step (ptx is the reference's running sum ptx += dx)
   float myE[2] = {1e30f, 1e30f}, myX[2] = {0, 0}, myY[2] = {0, 0};
 #pragma unroll
   for (int pass = 0; pass < 2; pass++) {
     const int s = pass * 64 + lane;
-    if (s < numSteps) {
-      float ptx = ptx0, pty = pty0;
+    if (s < L.numSteps) {
+      float ptx = L.ptx0, pty = L.pty0;
       for (int k = 0; k < s; k++) { ptx += dx; pty += dy; }
-      float energy = 0;
-#pragma unroll
-      for (int idx = 0; idx < 8; idx++) {
-        const float hitColor = interp31_plane(T.plane, (float)(ptx + rot[idx][0]), (float)(pty + rot[idx][1]), wG0);
-        if (!isfinite(hitColor)) { energy += 1e5; continue; }
-        const float residual = hitColor - (float)(aff0 * color[idx] + aff1);
-        const float hw = fabsf(residual) < kHuberTH ? 1 : kHuberTH / fabsf(residual);
-        energy += hw * residual * residual * (2 - hw);
-      }
-      errors[s] = energy;
-      myE[pass] = energy; myX[pass] = ptx; myY[pass] = pty;
+      myE[pass] = trace_step_energy(pat, T.plane, wG0, color, ptx, pty); myX[pass] = ptx; myY[pass] = pty;
     }
   }
-  // first minimum (the reference takes strictly smaller energies only, in step order)
-  float bE = 1e10f; int bI = -1; float bX = 0, bY = 0;
-#pragma unroll
-  for (int pass = 0; pass < 2; pass++) {
-    const int s = pass * 64 + lane;
-    if (s < numSteps && myE[pass] < bE) { bE = myE[pass]; bI = s; bX = myX[pass]; bY = myY[pass]; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float oE = __shfl_xor(bE, o, 64); const int oI = __shfl_xor(bI, o, 64);
-    const float oX = __shfl_xor(bX, o, 64), oY = __shfl_xor(bY, o, 64);
-    const bool take = (oI >= 0) && (bI < 0 || oE < bE || (oE == bE && oI < bI));
-    if (take) { bE = oE; bI = oI; bX = oX; bY = oY; }
-  }
-  float bestU = bX, bestV = bY, bestEnergy = bE;
-  const int bestIdx = bI;
-  if (bestIdx < 0) { bestU = 0; bestV = 0; bestEnergy = 1e10f; }
-  float secondBest = 1e10f;
-#pragma unroll
-  for (int pass = 0; pass < 2; pass++) {
-    const int s = pass * 64 + lane;
-    if (s < numSteps && (s < bestIdx - kMinTraceTestRadius || s > bestIdx + kMinTraceTestRadius) && myE[pass] < secondBest) secondBest = myE[pass];
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) secondBest = fminf(secondBest, __shfl_xor(secondBest, o, 64));
-  const float newQuality = secondBest / bestEnergy;
-  if (newQuality < quality || numSteps > 10) quality = newQuality;
+  const TraceMin m = trace_first_min(L.numSteps, lane, myE, myX, myY);
+  float bestU = m.bX, bestV = m.bY, bestEnergy = m.bE;
+  if (m.bI < 0) { bestU = 0; bestV = 0; bestEnergy = 1e10f; }
+  const float newQuality = m.secondBest / bestEnergy;
+  if (newQuality < quality || L.numSteps > 10) quality = newQuality;
 
-  // ---- DSO-native GN (ImmaturePoint.cpp:707-769): pattern pixel idx on lane idx, summed in order
-  float uBak = bestU, vBak = bestV, stepBack = 0;
-  const float gnstepsize = 1;
-  if (kTraceGNIterations > 0) bestEnergy = 1e5;
+  // ---- sub-pixel refinement: pattern pixel idx on lane idx, summed in order
+  const float patx = pat.ox(lane & 7), paty = pat.oy(lane & 7);   // (once: the 16-way select of a lane's row of rot)
+  TraceGN S(bestU, bestV, bestEnergy);
   for (int it = 0; it < kTraceGNIterations; it++) {
-    float tH = 0, tb = 0, te = 0;
-    bool nan = false;
-    if (lane < 8) {
-      const float3 hit = interp33(dI, (float)(bestU + rot[lane][0]), (float)(bestV + rot[lane][1]), wG0);
-      if (!isfinite(hit.x)) nan = true;
-      else {
-        const float residual = hit.x - (aff0 * color[lane] + aff1);
-        const float dResdDist = dx * hit.y + dy * hit.z;
-        const float hw = fabsf(residual) < kHuberTH ? 1 : kHuberTH / fabsf(residual);
-        tH = hw * dResdDist * dResdDist;
-        tb = hw * residual * dResdDist;
-        te = weights[lane] * weights[lane] * hw * residual * residual * (2 - hw);
-      }
-    }
+    TraceGNTerms g = {0, 0, 0, 0};
+    if (lane < 8) g = trace_gn_terms(pat, patx, paty, dI, wG0, S.bestU, S.bestV, dx, dy, color[lane], weights[lane]);
     float H = 1, bb = 0, energy = 0;
 #pragma unroll
     for (int idx = 0; idx < 8; idx++) {
-      const float h_ = lane_bcast(tH, idx), b_ = lane_bcast(tb, idx), e_ = lane_bcast(te, idx);
-      const int nn = lane_bcast((int)nan, idx);
+      const float h_ = lane_bcast(g.tH, idx), b_ = lane_bcast(g.tb, idx), e_ = lane_bcast(g.te, idx);
+      const int nn = lane_bcast(g.nan, idx);
       if (nn) { energy += 1e5; continue; }
       H += h_; bb += b_; energy += e_;
     }
-    if (energy > bestEnergy) {
-      stepBack *= 0.5;
-      bestU = uBak + stepBack * dx;
-      bestV = vBak + stepBack * dy;
-    } else {
-      float step = -gnstepsize * bb / H;
-      if (step < -0.5) step = -0.5;
-      else if (step > 0.5) step = 0.5;
-      if (!isfinite(step)) step = 0;
-      uBak = bestU;
-      vBak = bestV;
-      stepBack = step;
-      bestU += step * dx;
-      bestV += step * dy;
-      bestEnergy = energy;
-    }
-    if (fabsf(stepBack) < kTraceGNThreshold) break;
+    if (trace_gn_advance(S, H, bb, energy, dx, dy)) break;
   }
 
-  if (!(bestEnergy < energyTH * kTraceExtraSlack)) {
+  if (!(S.bestEnergy < energyTH * kTraceExtraSlack)) {
     finish(prevStatus == IPS_OUTLIER ? IPS_OOB : IPS_OUTLIER, -1, -1, 0, true);
     return;
   }
-  if (dx * dx > dy * dy) {
-    idepth_min_stereo = (pr[2] * (bestU - errorInPixel * dx) - pr[0]) / (Kt[0] - Kt[2] * (bestU - errorInPixel * dx));
-    idepth_max_stereo = (pr[2] * (bestU + errorInPixel * dx) - pr[0]) / (Kt[0] - Kt[2] * (bestU + errorInPixel * dx));
-  } else {
-    idepth_min_stereo = (pr[2] * (bestV - errorInPixel * dy) - pr[1]) / (Kt[1] - Kt[2] * (bestV - errorInPixel * dy));
-    idepth_max_stereo = (pr[2] * (bestV + errorInPixel * dy) - pr[1]) / (Kt[1] - Kt[2] * (bestV + errorInPixel * dy));
-  }
-  if (idepth_min_stereo > idepth_max_stereo) { const float t = idepth_min_stereo; idepth_min_stereo = idepth_max_stereo; idepth_max_stereo = t; }
+  trace_interval(pr, Kt, S.bestU, S.bestV, dx, dy, L.errorInPixel, idepth_min_stereo, idepth_max_stereo);
   if (lane == 0) { T.idepth_min_stereo[i] = idepth_min_stereo; T.idepth_max_stereo[i] = idepth_max_stereo; }
   if (!isfinite(idepth_min_stereo) || !isfinite(idepth_max_stereo) || (idepth_max_stereo < 0)) { finish(IPS_OUTLIER, -1, -1, 0, true); return; }
-  finish(IPS_GOOD, bestU, bestV, 2 * errorInPixel, true);
+  finish(IPS_GOOD, S.bestU, S.bestV, 2 * L.errorInPixel, true);
 }
 __global__ __launch_bounds__(256) void k_trace_on(TraceDev T, const sdso_trace_geom_t* __restrict__ geom, const int* __restrict__ pgeom) {
-  const int wv = threadIdx.x >> 6;
-  const int i = blockIdx.x * 4 + wv;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= T.n) return;
-  __shared__ float s_err[4][128];
-  trace_on_point(T, i, s_err[wv], [&] { return geom[pgeom[i]]; });
+  trace_on_point(T, i, [&] { return geom[pgeom[i]]; });
 }
 
 // ------------------------------------------------------------------ API
@@ -807,12 +538,7 @@ __global__ __launch_bounds__(256) void k_match_prepare(int n, const float* __res
                                                        const float* __restrict__ imax, TraceDev T) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n) return;
-  T.u_stereo[p] = u[p]; T.v_stereo[p] = v[p];
-  T.idepth_min[p] = 0.f;
-  T.idepth_min_stereo[p] = imin ? imin[p] : 0.f;
-  T.idepth_max_stereo[p] = imax ? imax[p] : NAN;
-  T.idepth_stereo[p] = 0.f; T.quality[p] = 10000.f; T.lastTraceStatus[p] = IPS_UNINITIALIZED;   // ImmaturePoint.cpp:34-38
-  T.lastTraceUV[2 * p] = 0.f; T.lastTraceUV[2 * p + 1] = 0.f; T.lastTracePixelInterval[p] = 0.f;
+  fresh_point(T, p, u[p], v[p], 0.f, imin ? imin[p] : 0.f, imax ? imax[p] : NAN);
 }
 // back points at the forward trace's lastTraceUV; points whose forward trace was not GOOD are skipped (and parked on a
 // harmless pixel so that the constructor kernel reads valid memory)
@@ -822,57 +548,60 @@ __global__ __launch_bounds__(256) void k_match_back_points(int n, TraceDev F, Tr
   if (p >= n) return;
   const bool good = F.status[p] == IPS_GOOD;
   skip[p] = good ? 0 : 1;
-  Bk.u_stereo[p] = good ? F.lastTraceUV[2 * p] : 8.f;
-  Bk.v_stereo[p] = good ? F.lastTraceUV[2 * p + 1] : 8.f;
-  Bk.idepth_min[p] = 0.f;
-  Bk.idepth_min_stereo[p] = bmin ? bmin[p] : 0.f;
-  Bk.idepth_max_stereo[p] = bmax ? bmax[p] : NAN;
-  Bk.idepth_stereo[p] = 0.f; Bk.quality[p] = 10000.f; Bk.lastTraceStatus[p] = IPS_UNINITIALIZED;
-  Bk.lastTraceUV[2 * p] = 0.f; Bk.lastTraceUV[2 * p + 1] = 0.f; Bk.lastTracePixelInterval[p] = 0.f;
+  fresh_point(Bk, p, good ? F.lastTraceUV[2 * p] : 8.f, good ? F.lastTraceUV[2 * p + 1] : 8.f, 0.f, bmin ? bmin[p] : 0.f, bmax ? bmax[p] : NAN);
 }
 
-// The launch sequence of the chain on device-resident inputs: in[0..5] = u, v, idepth_min_stereo, idepth_max_stereo, and the back
-// trace's two bounds (each n floats in device memory; 2..5 may be null: 0 / NaN, a fresh ImmaturePoint), skip_fwd (optional, n bytes): 1 =
-// the point takes no trace at all (both statuses 255; its u, v must still address a readable pattern).  Enqueue only: the results stay
-// in the ctx's two match batches (*out points into them) until the next chain of this ctx.  The caller has validated the slots.
 namespace sdso {
+// The launch sequence of a trace of fresh points, for stereo_match_chain_dev below and sdso_imm_trace (immature.hip), each around its own
+// prepare / back / accept kernels and on its own two batches.
+// trace_pair_bind: F and Bk reserved and bound for n points, F's points lying on pyramid PA and searched in PB, Bk's on PB and searched in PA.
+static int trace_pair_bind(sdso_ctx* ctx, TraceBatch& F, TraceBatch& Bk, int n, PyramidDev& PA, PyramidDev& PB, const float K[4], float baseline,
+                           int mode_right_fwd, int mode_right_back) {
+  for (TraceBatch* B : {&F, &Bk}) {
+    const int rc = trace_reserve(ctx, *B, n);
+    if (rc) return rc;
+    trace_bind(*B, n);
+  }
+  for (PyramidDev* P : {&PA, &PB}) {
+    const int rc = ensure_plane0(ctx, *P);
+    if (rc) return rc;
+  }
+  auto cam = [&](TraceDev& T, const PyramidDev& P, int mode_right) {
+    T.w = P.w[0]; T.h = P.h[0]; T.mode_right = mode_right; T.img = P.d[0]; T.plane = P.plane0;
+    T.fx = K[0]; T.fy = K[1]; T.cx = K[2]; T.cy = K[3]; T.baseline = baseline;
+  };
+  cam(F.T, PB, mode_right_fwd);
+  cam(Bk.T, PA, mode_right_back);
+  return SDSO_OK;
+}
+// launch_fresh_trace: ImmaturePoint::ImmaturePoint on `host` for the points of T, then their traceStereo; skip[p] = 1 leaves point p alone.
+// (k_trace_stereo is timed at profiling level 1 — a chain's two traces —, k_immature_init at level 2.)
+static void launch_fresh_trace(sdso_ctx* ctx, TraceDev T, const PyramidDev& host, const uint8_t* skip) {
+  launch_timed(ctx, "k_immature_init", 2, k_immature_init, dim3((T.n + 255) / 256), dim3(256), (const float4*)host.d[0], T.w, T.n, (const float*)T.u_stereo,
+               (const float*)T.v_stereo, (float*)T.color, (float*)T.weights, (float*)T.gradH, (float*)T.energyTH);
+  T.skip = skip;
+  launch_trace_stereo(ctx, T, true);
+}
+
+// The chain on device-resident inputs: in[0..5] = u, v, idepth_min_stereo, idepth_max_stereo, and the back trace's two bounds (each n
+// floats in device memory; 2..5 may be null: 0 / NaN, a fresh ImmaturePoint), skip_fwd (optional, n bytes): 1 = the point takes no trace
+// at all (both statuses 255; its u, v must still address a readable pattern).  Enqueue only: the results stay in the ctx's two match
+// batches (*out points into them) until the next chain of this ctx.  The caller has validated the slots.
 int stereo_match_chain_dev(sdso_ctx* ctx, int slot_a, int slot_b, const float K[4], float baseline, int mode_right_first, int n,
                            const float* const in[6], const uint8_t* skip_fwd, MatchChainOut* out) {
   PyramidDev& PA = ctx->pyr.find(slot_a)->second;
   PyramidDev& PB = ctx->pyr.find(slot_b)->second;
-  const int w = PA.w[0], h = PA.h[0];
   StereoState& S = stereo_state(ctx);
-  TraceBatch& A = S.match[0];
-  TraceBatch& Bk = S.match[1];
-  int rc = trace_reserve(ctx, A, n);
+  TraceBatch& A = S.match[0];    // forward: points of frame A searched in frame B
+  TraceBatch& Bk = S.match[1];   // back: points of frame B searched in frame A
+  const int rc = trace_pair_bind(ctx, A, Bk, n, PA, PB, K, baseline, mode_right_first ? 1 : 0, mode_right_first ? 0 : 1);
   if (rc) return rc;
-  rc = trace_reserve(ctx, Bk, n);
-  if (rc) return rc;
-  trace_bind(A, n); trace_bind(Bk, n);
-  rc = ensure_plane0(ctx, PA);
-  if (rc) return rc;
-  rc = ensure_plane0(ctx, PB);
-  if (rc) return rc;
-  auto geom = [&](TraceDev& T, const float4* img, const float* plane, int mode_right) {
-    T.w = w; T.h = h; T.mode_right = mode_right; T.img = img; T.plane = plane;
-    T.fx = K[0]; T.fy = K[1]; T.cx = K[2]; T.cy = K[3]; T.baseline = baseline;
-  };
-  geom(A.T, PB.d[0], PB.plane0, mode_right_first ? 1 : 0);       // forward: points of frame A searched in frame B
-  geom(Bk.T, PA.d[0], PA.plane0, mode_right_first ? 0 : 1);      // back: points of frame B searched in frame A
   const dim3 g1((n + 255) / 256), b1(256);
   uint8_t* skip = Bk.bytes + 2 * (size_t)Bk.n;
   hipLaunchKernelGGL(k_match_prepare, g1, b1, 0, ctx->stream, n, in[0], in[1], in[2], in[3], A.T);
-  hipLaunchKernelGGL(k_immature_init, g1, b1, 0, ctx->stream, PA.d[0], w, n, (const float*)A.T.u_stereo, (const float*)A.T.v_stereo,
-                     (float*)A.T.color, (float*)A.T.weights, (float*)A.T.gradH, (float*)A.T.energyTH);
-  TraceDev Tf = A.T;
-  Tf.skip = skip_fwd;
-  launch_trace_stereo(ctx, Tf, true);       // (timed under k_trace_stereo when profiling is on: the match chain's two traces)
+  launch_fresh_trace(ctx, A.T, PA, skip_fwd);
   hipLaunchKernelGGL(k_match_back_points, g1, b1, 0, ctx->stream, n, A.T, Bk.T, skip, in[4], in[5]);
-  hipLaunchKernelGGL(k_immature_init, g1, b1, 0, ctx->stream, PB.d[0], w, n, (const float*)Bk.T.u_stereo, (const float*)Bk.T.v_stereo,
-                     (float*)Bk.T.color, (float*)Bk.T.weights, (float*)Bk.T.gradH, (float*)Bk.T.energyTH);
-  TraceDev Tb = Bk.T;
-  Tb.skip = skip;
-  launch_trace_stereo(ctx, Tb, true);
+  launch_fresh_trace(ctx, Bk.T, PB, skip);
   SDSO_HIP(ctx, hipGetLastError());
   out->idepth_stereo = A.T.idepth_stereo; out->idepth_min = A.T.idepth_min_stereo; out->idepth_max = A.T.idepth_max_stereo;
   out->fwd_uv = A.T.lastTraceUV; out->back_uv = Bk.T.lastTraceUV; out->status_fwd = A.T.status; out->status_back = Bk.T.status;
