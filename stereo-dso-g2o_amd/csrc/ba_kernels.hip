@@ -243,7 +243,7 @@ constexpr int CG_BATCH = 8;                                   // loads in flight
 // zeros.  The range is 2 GiB whatever the image's size (every offset a live lane forms lies inside the image), TAP_OFF_DEAD lies beyond it.
 typedef __amdgpu_buffer_rsrc_t tap_rsrc_t;
 typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
-constexpr unsigned TAP_RANGE = 0x80000000u, TAP_OFF_DEAD = 0xfffffff0u;   // (the window upload, ba.hip, refuses an image of TAP_RANGE bytes or more)
+constexpr unsigned TAP_RANGE = 0x80000000u, TAP_OFF_DEAD = 0xfffffff0u;   // (the window upload, ba_window.hip, refuses an image of TAP_RANGE bytes or more)
 constexpr int TAP_RSRC_FLAGS = 0x00020000;   // word 3 of a gfx9 (gfx950) raw buffer descriptor: DATA_FORMAT = 32; other families lay this word out differently
 __device__ __forceinline__ void cg_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

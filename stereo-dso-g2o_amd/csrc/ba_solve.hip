@@ -824,6 +824,19 @@ __global__ __launch_bounds__(256) void k_ba_marg_frame(const double* __restrict_
   if (tid < ndim) out[(size_t)ndim * ndim + tid] = S[tid] * b[tid];
 }
 
+}  // namespace sdso
+// EnergyFunctional::insertFrame's part on HM / bM (EnergyFunctional.cpp:468-476), for sdso_ba_adopt_prior (ba_marg.hip) and
+// sdso_ba_window_update (ba_update.hip): the prior of dimension m into a window of dimension n, the new rows / columns zero.
+// (Outside the namespace, as ever: its symbol is part of the device code.)
+__global__ __launch_bounds__(256) void k_ba_prior_adopt(double* __restrict__ HM, double* __restrict__ bM, int n, const double* __restrict__ srcH,
+                                                        const double* __restrict__ srcb, int m) {
+  for (int e = blockIdx.x * 256 + threadIdx.x; e < n * n + n; e += gridDim.x * 256) {
+    if (e < n * n) { const int i = e / n, j = e - i * n; HM[e] = (i < m && j < m) ? srcH[(size_t)i * m + j] : 0.0; }
+    else { const int i = e - n * n; bM[i] = i < m ? srcb[i] : 0.0; }
+  }
+}
+namespace sdso {
+
 // FullSystem::backupState / doStepFromBackup / loadSateBackup for the points.  op: 0 backup, 1 step, 2 restore
 // op 3 = backup + step in one pass (the resident loop never restores).  stepfacD < 0: the window's own stepsize (BaOptDev::stepsize,
 // SOLVER_STEPMOMENTUM).  SOLVER_MOMENTUM (FullSystemOptimize.cpp:238-250): step + 0.5f * step_backup, no step factor.

@@ -7,7 +7,7 @@
 //                                                                seven) dropped
 //   and the closing orthogonalize(&x, 0) of SOLVER_ORTHOGONALIZE_X[_LATER]  :980-984
 // Rounds 1-3 took the stitched blocks back to the host for these (one round trip per window and iteration, also behind the batch entry
-// points): solve_system_host in ba.hip, kept behind SDSO_BA_SOLVE_HOST=1 as the A/B and as the statement of the arithmetic this kernel
+// points): solve_system_host in ba_api.hip, kept behind SDSO_BA_SOLVE_HOST=1 as the A/B and as the statement of the arithmetic this kernel
 // follows line by line.  Here: ONE 512-thread workgroup per window behind k_ba_stitch, everything in LDS (f64).
 //   * the symmetric eigen-decomposition that stands in for JacobiSVD (singular values |w|, U = V sign(w)) is a cyclic Jacobi iteration
 //     like host_math.h::symEigen, in the PARALLEL ordering: a sweep is n - 1 rounds of n / 2 disjoint index pairs (round-robin

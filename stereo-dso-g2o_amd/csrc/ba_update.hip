@@ -2,171 +2,11 @@
 // removePoint (src/OptimizationBackend/EnergyFunctional.cpp:445-533, :739-772) and of the residual drops of FullSystem::marginalizeFrame
 // (src/FullSystem/FullSystemMarginalize.cpp:146-198) on an uploaded window.  Included at the end of ba.hip (one translation unit).
 //
-//   plan_window_edit   host: the integer list surgery on the window's mirrors, O(np + nr) — also sdso_ba_window_plan, without a ctx
-//   upload_window_impl host: the integer arrays, work lists and tables of the edited window, built by the code that builds an uploaded
+//   plan_window_edit   host: the integer list surgery on the window's mirrors, O(np + nr) — also sdso_ba_window_plan, without a ctx (ba_layout.h)
+//   upload_window_impl host (ba_window.hip): the integer arrays, work lists and tables of the edited window, built by the code that builds an uploaded
 //                      one (so the two cannot drift apart), staged in one copy together with the appended entries' payload
 //   k_ba_window_gather device: the surviving points' and residuals' rows, old slab -> new slab through the plan's maps
-//   k_ba_prior_adopt   device: HM / bM (or the chained prior of sdso_ba_marginalize_frame_dev) into the new dimension
-#include <string>
-
-struct WindowPlan {
-  int nf2 = 0, np2 = 0, nr2 = 0;
-  std::vector<int> frame_src, point_src, res_src;      // sdso_abi.h: index before the edit, or -1-k for the k-th appended entry
-  std::vector<int> host, res_point, res_target;        // the edited window's integer arrays in its own numbering
-  const char* why = nullptr;                           // the refusal
-};
-
-// The seven stages on plain index lists.  Returns false with P.why set for an edit the reference could not perform.
-static bool plan_window_edit(int nf, int np, int nr, const int* host, const int* res_point, const int* res_target, const sdso_ba_window_edit_t& E, WindowPlan& P) {
-#define BAD(cond, msg) do { if (!(cond)) { P.why = (msg); return false; } } while (0)
-  BAD(nf >= 1 && nf <= 8 && np >= 0 && nr >= 0, "window sizes out of range");
-  BAD((np == 0 || host) && (nr == 0 || (res_point && res_target)), "null window arrays");
-  BAD(E.n_drop_res >= 0 && E.n_remove_points >= 0 && E.n_remove_frames >= 0 && E.n_add_frames >= 0 && E.n_add_res >= 0 && E.n_add_points >= 0 && E.n_pt_res >= 0, "negative count in the edit");
-  BAD(E.n_add_frames <= 8 && E.n_drop_res <= nr && E.n_remove_points <= np && E.n_remove_frames <= nf, "a count of the edit exceeds what the window holds (at most 8 frames)");
-  BAD(E.n_add_points <= (1 << 24) && E.n_add_res <= SDSO_MAX_RES * np && E.n_pt_res <= SDSO_MAX_RES * (long)E.n_add_points, "a count of the edit exceeds what the window can hold");
-  BAD((!E.n_drop_res || E.drop_res) && (!E.n_remove_points || E.remove_points) && (!E.n_remove_frames || E.remove_frames), "null index list in the edit");
-  BAD(!E.n_add_res || (E.add_res_point && E.add_res_target), "null stage-6 arrays");
-  BAD(!E.n_add_points || E.pt_host, "null stage-7 hosts");
-  BAD(!E.n_pt_res || (E.pt_res_point && E.pt_res_target), "null stage-7 residual arrays");
-  const int nfa = nf + E.n_add_frames;                 // frames in the numbering before the call
-  // ---- the window's lists (EFFrame::points with EFPoint::idxInPoints, EFPoint::residualsAll)
-  std::vector<std::vector<int>> fpts(nfa);
-  std::vector<int> pidx(np), rcnt(np, 0), rl((size_t)np * SDSO_MAX_RES);
-  for (int f = 0; f < nfa; f++) fpts[f].reserve((size_t)np / nf + E.n_add_points + 16);
-  for (int p = 0; p < np; p++) {
-    BAD(host[p] >= 0 && host[p] < nf && (p == 0 || host[p] >= host[p - 1]), "point hosts out of range or not in allPoints order");
-    pidx[p] = (int)fpts[host[p]].size();
-    fpts[host[p]].push_back(p);
-  }
-  for (int r = 0; r < nr; r++) {
-    const int p = res_point[r];
-    BAD(p >= 0 && p < np && (r == 0 || p >= res_point[r - 1]) && res_target[r] >= 0 && res_target[r] < nf, "residuals out of range or not grouped by point");
-    BAD(rcnt[p] < SDSO_MAX_RES, "more than MAX_RES_PER_POINT residuals on a point");
-    rl[(size_t)p * SDSO_MAX_RES + rcnt[p]++] = r;
-  }
-  std::vector<uint8_t> ralive(nr, 1), palive(np, 1), falive(nfa, 1);
-  auto target_of = [&](int id) { return id >= 0 ? res_target[id] : E.add_res_target[-1 - id]; };
-  auto drop_at = [&](int p, int k) {                   // dropResidual (:529-533): the last entry takes the freed slot
-    int* l = &rl[(size_t)p * SDSO_MAX_RES];
-    l[k] = l[rcnt[p] - 1];
-    rcnt[p]--;
-  };
-  auto remove_point = [&](int p) {                     // removePoint (:755-771)
-    for (int k = 0; k < rcnt[p]; k++) ralive[rl[(size_t)p * SDSO_MAX_RES + k]] = 0;
-    rcnt[p] = 0;
-    std::vector<int>& L = fpts[host[p]];
-    const int i = pidx[p], last = L.back();
-    L[i] = last; pidx[last] = i;
-    L.pop_back();
-    palive[p] = 0;
-  };
-  // ---- stage 1
-  for (int i = 0; i < E.n_drop_res; i++) {
-    const int r = E.drop_res[i];
-    BAD(r >= 0 && r < nr, "stage 1: residual index out of range");
-    BAD(ralive[r], "stage 1: residual named twice");
-    const int p = res_point[r];
-    int k = 0;
-    while (rl[(size_t)p * SDSO_MAX_RES + k] != r) k++;
-    drop_at(p, k);
-    ralive[r] = 0;
-  }
-  // ---- stage 2
-  for (int i = 0; i < E.n_remove_points; i++) {
-    const int p = E.remove_points[i];
-    BAD(p >= 0 && p < np, "stage 2: point index out of range");
-    BAD(palive[p], "stage 2: point named twice");
-    remove_point(p);
-  }
-  // ---- stage 3
-  if (E.drop_point) {
-    for (int p = 0; p < np; p++) BAD(!E.drop_point[p] || palive[p], "stage 3: the point was already removed by stage 2");
-    for (int f = 0; f < nf; f++)
-      for (int i = 0; i < (int)fpts[f].size(); i++)    // dropPointsF (:741-747)
-        if (E.drop_point[fpts[f][i]]) { remove_point(fpts[f][i]); i--; }
-  }
-  // ---- stage 4
-  for (int i = 0; i < E.n_remove_frames; i++) {
-    const int f = E.remove_frames[i];
-    BAD(f >= 0 && f < nf, "stage 4: frame index out of range");
-    BAD(falive[f], "stage 4: frame named twice");
-    BAD(fpts[f].empty(), "stage 4: the frame still hosts a point (FullSystemMarginalize.cpp:148)");
-    falive[f] = 0;
-    for (int p = 0; p < np; p++) {
-      if (!palive[p]) continue;
-      for (int k = 0; k < rcnt[p]; k++) {
-        const int r = rl[(size_t)p * SDSO_MAX_RES + k];
-        if (res_target[r] == f) { drop_at(p, k); ralive[r] = 0; break; }
-      }
-    }
-  }
-  // ---- stage 5
-  int nf2 = E.n_add_frames;
-  for (int f = 0; f < nf; f++) nf2 += falive[f];
-  BAD(nf2 <= 8, "more than 8 frames after the edit (setting_maxFrames is 7, settings.cpp:65)");
-  BAD(nf2 >= 1, "no frame left after the edit");
-  // ---- stage 6
-  for (int i = 0; i < E.n_add_res; i++) {
-    const int p = E.add_res_point[i], t = E.add_res_target[i];
-    BAD(p >= 0 && p < np, "stage 6: point index out of range");
-    BAD(palive[p], "stage 6: residual added to a point that leaves");
-    BAD(t >= 0 && t < nfa, "stage 6: target frame out of range");
-    BAD(falive[t], "stage 6: residual into a frame that leaves");
-    BAD(t != host[p], "stage 6: a residual observes its own host frame");
-    for (int k = 0; k < rcnt[p]; k++) BAD(target_of(rl[(size_t)p * SDSO_MAX_RES + k]) != t, "stage 6: the point already observes that target frame");
-    BAD(rcnt[p] < SDSO_MAX_RES, "stage 6: more than MAX_RES_PER_POINT residuals on a point");
-    rl[(size_t)p * SDSO_MAX_RES + rcnt[p]++] = -1 - i;
-  }
-  // ---- stage 7
-  for (int i = 0; i < E.n_add_points; i++) {
-    const int h = E.pt_host[i];
-    BAD(h >= 0 && h < nfa, "stage 7: host frame out of range");
-    BAD(falive[h], "stage 7: point hosted by a frame that leaves");
-    fpts[h].push_back(-1 - i);
-  }
-  std::vector<int> prbeg(E.n_add_points + 1, 0);
-  {
-    unsigned seen = 0; int cur = -1;
-    for (int i = 0; i < E.n_pt_res; i++) {
-      const int q = E.pt_res_point[i], t = E.pt_res_target[i];
-      BAD(q >= 0 && q < E.n_add_points && q >= cur, "stage 7: residual point index out of range or decreasing");
-      if (q != cur) { cur = q; seen = 0; }
-      BAD(t >= 0 && t < nfa, "stage 7: target frame out of range");
-      BAD(falive[t], "stage 7: residual into a frame that leaves");
-      BAD(t != E.pt_host[q], "stage 7: a residual observes its own host frame");
-      BAD(!((seen >> t) & 1u), "stage 7: two residuals of one point observe the same target frame");
-      seen |= 1u << t;
-      BAD(++prbeg[q + 1] <= SDSO_MAX_RES, "stage 7: more than MAX_RES_PER_POINT residuals on a point");
-    }
-    for (int q = 0; q < E.n_add_points; q++) prbeg[q + 1] += prbeg[q];
-  }
-  // ---- makeIDX (:998-1018): frames, each frame's points, each point's residualsAll
-  std::vector<int> fnew(nfa, -1);
-  P.frame_src.clear();
-  for (int f = 0; f < nfa; f++)
-    if (falive[f]) { fnew[f] = (int)P.frame_src.size(); P.frame_src.push_back(f < nf ? f : -1 - (f - nf)); }
-  const size_t np_max = (size_t)np + E.n_add_points, nr_max = (size_t)nr + E.n_add_res + E.n_pt_res;
-  P.point_src.resize(np_max); P.host.resize(np_max); P.res_src.resize(nr_max); P.res_point.resize(nr_max); P.res_target.resize(nr_max);
-  int p2 = 0, r2 = 0;
-  for (int f = 0; f < nfa; f++) {
-    if (!falive[f]) continue;
-    for (int p : fpts[f]) {
-      P.point_src[p2] = p;
-      P.host[p2] = fnew[f];
-      if (p >= 0) {
-        const int* l = &rl[(size_t)p * SDSO_MAX_RES];
-        for (int k = 0; k < rcnt[p]; k++, r2++) { P.res_src[r2] = l[k]; P.res_point[r2] = p2; P.res_target[r2] = fnew[target_of(l[k])]; }
-      } else {
-        for (int j = prbeg[-1 - p]; j < prbeg[-p]; j++, r2++) { P.res_src[r2] = -1 - (E.n_add_res + j); P.res_point[r2] = p2; P.res_target[r2] = fnew[E.pt_res_target[j]]; }
-      }
-      p2++;
-    }
-  }
-  P.point_src.resize(p2); P.host.resize(p2); P.res_src.resize(r2); P.res_point.resize(r2); P.res_target.resize(r2);
-  P.nf2 = nf2; P.np2 = (int)P.point_src.size(); P.nr2 = (int)P.res_src.size();
-  return true;
-#undef BAD
-}
+//   k_ba_prior_adopt   device: HM / bM (or the chained prior of sdso_ba_marginalize_frame_dev) into the new dimension (ba_solve.hip)
 
 // Rows of the surviving points and residuals, old slab -> new slab.  One thread per 16-byte row: six rows per point (p_geo, p_track, two of
 // colour, two of weights), then one thread per residual for its two state bytes.  src < 0: the entry is new, its row came with the staged copy.

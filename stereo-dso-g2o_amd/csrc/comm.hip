@@ -21,10 +21,10 @@
 #include <cstdlib>
 
 namespace sdso {
-void* ba_batch_accum_block(sdso_ctx* ctx, size_t* nfloats);            // ba.hip
-void* ba_window_accum_block(sdso_ctx* ctx, int win, size_t* nfloats);  // ba.hip
-bool ba_batch_scatter_wanted(sdso_ctx* ctx);                           // ba.hip: the batch's exchange is the reduce-scatter by window (agreed on by all ranks at optimize_begin)
-void ba_batch_scatter_done(sdso_ctx* ctx);                             // ba.hip: ... and it has been enqueued: only this rank's windows hold summed accumulators
+void* ba_batch_accum_block(sdso_ctx* ctx, size_t* nfloats);            // ba_batch.hip
+void* ba_window_accum_block(sdso_ctx* ctx, int win, size_t* nfloats);  // ba_batch.hip
+bool ba_batch_scatter_wanted(sdso_ctx* ctx);                           // ba_loop.hip: the batch's exchange is the reduce-scatter by window (agreed on by all ranks at optimize_begin)
+void ba_batch_scatter_done(sdso_ctx* ctx);                             // ba_loop.hip: ... and it has been enqueued: only this rank's windows hold summed accumulators
 
 struct RcclApi {
   void* lib = nullptr;
@@ -90,7 +90,7 @@ void release_comm(sdso_ctx* ctx) { ctx->comm.reset(); }
 using namespace sdso;
 
 namespace sdso {
-// used by the resident GN loop (ba.hip): ranks of ctx's communicator (1 without one), the all-gather of the per-rank energy / break-test
+// used by the resident GN loop (ba_loop.hip): ranks of ctx's communicator (1 without one), the all-gather of the per-rank energy / break-test
 // records, and the max over ranks of a host int (collective, synchronises the ctx stream)
 int comm_nranks(sdso_ctx* ctx) { return ctx->comm ? ctx->comm->nranks : 1; }
 int comm_rank(sdso_ctx* ctx) { return ctx->comm ? ctx->comm->rank : 0; }
@@ -231,7 +231,7 @@ static int allreduce_block(sdso_ctx* ctx, void* ptr, size_t nfloats) {
 // The other shape of the same exchange (sdso_ba_batch_exchange_mode(ctx, 1)): the windows of the batch lie one after the other in the block,
 // so a reduce-scatter hands rank r the SUMMED accumulators of windows [r * nwin / N, (r + 1) * nwin / N) and nothing of the others — half
 // the bytes of the all-reduce on every xGMI link; the solve of a window then runs on one rank only and x comes back by all-gather
-// (ba.hip: opt_solve_step).  In place: rank r's slice of the block is both its send and its receive segment.
+// (ba_loop.hip: opt_solve_step).  In place: rank r's slice of the block is both its send and its receive segment.
 static int reduce_scatter_block(sdso_ctx* ctx, void* ptr, size_t nfloats) {
   Comm* c = ctx->comm.get();
   SDSO_REQUIRE(ctx, c, "no communicator: call sdso_comm_init (or sdso_comm_attach) first");

@@ -55,8 +55,8 @@ struct ProfEntry {
   long launches = 0;
 };
 
-struct BaWindowDev;  // ba.hip
-struct BaCtxState;   // ba.hip
+struct BaWindowDev;  // ba_window.hip
+struct BaCtxState;   // ba_window.hip
 struct TrackBatch;   // tracker.hip
 struct StereoState;  // stereo.hip
 struct SelState;     // selector.hip
@@ -235,7 +235,7 @@ int stereo_match_chain_dev(sdso_ctx* ctx, int slot_a, int slot_b, const float K[
                            const float* const in[6], const uint8_t* skip_fwd, MatchChainOut* out);                            // stereo.hip
 int track_make_ref_dev(sdso_ctx* ctx, int ref_slot, int frame_slot, int n, const int* d_u, const int* d_v, const float* d_idp, const float* d_wgt,
                        int* pc_n_out, bool sync_end);                                                                         // coarse_depth.hip
-// what a BA window offers a reader of its post-state (ba.hip): SDSO_ERR_ARG for an unknown window, SDSO_ERR_STATE unless an optimize
+// what a BA window offers a reader of its post-state (ba_api.hip): SDSO_ERR_ARG for an unknown window, SDSO_ERR_STATE unless an optimize
 // call has ended on it and nothing has edited it since, it is outside a batch and none of its residuals is linearised
 struct BaRefView { const BaDev* dev; int nf, np, nr, w, h, last_frame_slot; float K[4]; };
 int ba_ref_view(sdso_ctx* ctx, int win, BaRefView* out);

@@ -1,6 +1,6 @@
 // The tiled copy of a level-0 image that the BA linearisation samples (PyramidDev::tiled0): 12-byte pixels {I, dx, dy} in tiles of
 // 5 x 2 pixels, one 128-byte line per tile (two rows of 60 bytes, the last 8 bytes unused and zero).  One definition for the producer
-// (ctx.hip), the consumers (ba_kernels.hip), the upload's size check (ba.hip) and tests/test_tile_layout_cpu.py.
+// (ctx.hip), the consumers (ba_kernels.hip), the upload's size check (ba_window.hip) and tests/test_tile_layout_cpu.py.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
