@@ -95,9 +95,9 @@ def _trace3(ctx, case, named):
     ctx.check(ctx.L.sdso_imm_trace(ctx.h, SLOT_L3, SLOT_R3, len(named), _imm_geoms(named), abi.fp(case["K4"]), abi.fp(case["Ki"]), case["baseline"], None))
 
 
-def _composed(ctx, win, ids, min_obs, min_act_dist):
+def _composed(ctx, win, ids, min_obs, min_act_dist, slot=SLOT):
     """The path of the older entry points: sdso_imm_get of every host, sdso_activate_select, sdso_activate_points_batch, one sdso_imm_remove
-    per host.  -> (decision, records, counts of the groups afterwards)"""
+    per host; the window's frames are in the slots slot .. slot + nf - 1.  -> (decision, records)"""
     nf = len(ids)
     got = [ctx.imm_get(i) for i in ids[:nf - 1]]
     cat = lambda k: np.ascontiguousarray(np.concatenate([S[k] for S in got]))
@@ -120,7 +120,7 @@ def _composed(ctx, win, ids, min_obs, min_act_dist):
     A.u, A.v, A.idepth_min, A.idepth_max, A.color, A.weights, A.energyTH = [abi.fp(a) for a in keep[3:]]
     hosts = np.ascontiguousarray(rec["frame"], np.int32)
     A.host = abi.ip(hosts)
-    slots = np.arange(SLOT, SLOT + nf, dtype=np.int32)
+    slots = np.arange(slot, slot + nf, dtype=np.int32)
     A.frame_slot = abi.ip(slots)
     status, idepth, res_state = np.zeros(ns, np.int8), np.zeros(ns, np.float32), np.zeros((ns, nf), np.uint8)
     ctx.check(ctx.L.sdso_activate_points_batch(ctx.h, C.byref(A), status.ctypes.data_as(C.POINTER(C.c_int8)), abi.fp(idepth), abi.bp(res_state)))
