@@ -320,54 +320,36 @@ class WindowedBA {
   void upload(EnergyFunctionalT* ef, CalibHessianT* HCalib, int w, int h, int solverMode, double affineOptModeA, double affineOptModeB,
               bool forceAcceptStep, SlotOf slot_of) {
     const int nf = (int)ef->frames.size();
-    evalPT_.assign(nf * 12, 0); state_.assign(nf * 10, 0); state_zero_.assign(nf * 10, 0);
-    exposure_.assign(nf, 1.f); energyTH_.assign(nf, 0.f); frameID_.assign(nf, 0); slots_.assign(nf, 0);
-    for (int f = 0; f < nf; f++) {
-      auto* fh = ef->frames[f]->data;
-      const sdso_se3_t T = toAbi(fh->get_worldToCam_evalPT());
-      std::memcpy(&evalPT_[f * 12], T.R, 72); std::memcpy(&evalPT_[f * 12 + 9], T.t, 24);
-      for (int i = 0; i < 10; i++) { state_[f * 10 + i] = fh->get_state()[i]; state_zero_[f * 10 + i] = fh->get_state_zero()[i]; }
-      exposure_[f] = fh->ab_exposure; energyTH_[f] = fh->frameEnergyTH; frameID_[f] = fh->frameID; slots_[f] = slot_of(fh);
-    }
-    u_.clear(); v_.clear(); idepth_.clear(); idepth_zero_.clear(); color_.clear(); weights_.clear(); host_.clear(); prior_.clear();
-    res_point_.clear(); res_target_.clear(); res_state_.clear(); points_.clear(); residuals_.clear();
-    maxRelBaseline_.clear(); numGood_.clear(); isNew_.clear();
+    FrameCols& F = up_frames_; PointCols& P = up_points_; ResCols& R = up_res_;
+    F.clear(); P.clear(); R.clear(); points_.clear(); residuals_.clear();
+    for (int f = 0; f < nf; f++) F.push(ef->frames[f]->data, slot_of);
     for (int f = 0; f < nf; f++)
       for (auto* p : ef->frames[f]->points) {
-        auto* ph = p->data;
-        const int pi = (int)u_.size();
-        u_.push_back(ph->u); v_.push_back(ph->v); idepth_.push_back(ph->idepth); idepth_zero_.push_back(ph->idepth_zero);
-        for (int k = 0; k < 8; k++) { color_.push_back(ph->color[k]); weights_.push_back(ph->weights[k]); }
-        host_.push_back(f); prior_.push_back(ph->hasDepthPrior ? 1 : 0);
-        maxRelBaseline_.push_back(ph->maxRelBaseline); numGood_.push_back(ph->numGoodResiduals);
+        const int pi = (int)P.u.size();
+        P.push(p->data, f);
         points_.push_back(p);
         for (auto* r : p->residualsAll) {                  // residualsAll order: the order of the reference's per-point float sums
-          res_point_.push_back(pi); res_target_.push_back(r->target->idx); res_state_.push_back((uint8_t)r->data->state_state);
-          isNew_.push_back(r->data->isNew ? 1 : 0);
+          R.push(pi, r->target->idx, r->data);
           residuals_.push_back(r);
         }
       }
-    sdso_ba_window_t W;
-    std::memset(&W, 0, sizeof(W));
-    W.nf = nf; W.np = (int)u_.size(); W.nr = (int)res_point_.size(); W.w = w; W.h = h;
+    sdso_ba_window_t W; std::memset(&W, 0, sizeof(W));
+    W.nf = nf; W.np = (int)P.u.size(); W.nr = (int)R.point.size(); W.w = w; W.h = h;
     for (int i = 0; i < 4; i++) { W.calib_value_scaled[i] = HCalib->value_scaled[i]; W.calib_value_zero[i] = HCalib->value_zero[i]; }
-    W.evalPT = evalPT_.data(); W.state = state_.data(); W.state_zero = state_zero_.data();
-    W.ab_exposure = exposure_.data(); W.frameEnergyTH = energyTH_.data(); W.frameID = frameID_.data(); W.frame_slot = slots_.data();
-    W.u = u_.data(); W.v = v_.data(); W.idepth = idepth_.data(); W.idepth_zero = idepth_zero_.data();
-    W.color = color_.data(); W.weights = weights_.data(); W.host = host_.data(); W.hasDepthPrior = prior_.data();
-    W.res_point = res_point_.data(); W.res_target = res_target_.data(); W.res_state = res_state_.data();
-    W.maxRelBaseline = maxRelBaseline_.data(); W.numGoodResiduals = numGood_.data(); W.res_isNew = isNew_.data();
+    W.evalPT = F.evalPT.data(); W.state = F.state.data(); W.state_zero = F.state_zero.data();
+    W.ab_exposure = F.exposure.data(); W.frameEnergyTH = F.energyTH.data(); W.frameID = F.frameID.data(); W.frame_slot = F.slots.data();
+    W.u = P.u.data(); W.v = P.v.data(); W.idepth = P.idepth.data(); W.idepth_zero = P.idepth_zero.data();
+    W.color = P.color.data(); W.weights = P.weights.data(); W.host = P.host.data(); W.hasDepthPrior = P.prior.data();
+    W.res_point = R.point.data(); W.res_target = R.target.data(); W.res_state = R.state.data();
+    W.maxRelBaseline = P.maxRelBaseline.data(); W.numGoodResiduals = P.numGood.data(); W.res_isNew = R.isNew.data();
     const int n = 8 * nf + 4;
     HM_.assign((size_t)n * n, 0); bM_.assign(n, 0);
     for (int i = 0; i < n; i++) { bM_[i] = ef->bM[i]; for (int j = 0; j < n; j++) HM_[(size_t)i * n + j] = ef->HM(i, j); }
     W.HM = HM_.data(); W.bM = bM_.data();
     W.solverMode = solverMode; W.affineOptModeA = affineOptModeA; W.affineOptModeB = affineOptModeB; W.forceAcceptStep = forceAcceptStep ? 1 : 0;
     dev_.check(sdso_ba_upload_window(dev_.ctx(), win_, &W), "sdso_ba_upload_window");
-    nf_ = nf; resInM_seen_ = 0;
-    ef_ = ef;
-    res_index_.clear(); point_index_.clear();
-    for (size_t i = 0; i < residuals_.size(); i++) res_index_[residuals_[i]->data] = (int)i;
-    for (size_t i = 0; i < points_.size(); i++) point_index_[points_[i]] = (int)i;
+    nf_ = nf; resInM_seen_ = 0; ef_ = ef;
+    reindex_();
     lin_valid_ = app_valid_ = acc_valid_ = marg_valid_ = false;
     frames_.assign(ef->frames.begin(), ef->frames.end());
     clearPending_();
@@ -459,7 +441,7 @@ class WindowedBA {
     ensureAccumulated();
     dev_.check(sdso_ba_solve(dev_.ctx(), win_, iteration, lambda, x.data(), HS.data(), bS.data(), fstep.data(), cstep), "sdso_ba_solve");
     ef_->lastX.resize(n); ef_->lastbS.resize(n); ef_->lastHS.resize(n, n);
-    for (int i = 0; i < n; i++) { ef_->lastX[i] = x[i]; ef_->lastbS[i] = bS[i]; for (int j = 0; j < n; j++) ef_->lastHS(i, j) = HS[(size_t)i * n + j]; }
+    fill_(ef_->lastX, x.data(), n); fill_(ef_->lastbS, bS.data(), n); fill_(ef_->lastHS, HS.data(), n, n);
     for (int i = 0; i < 4; i++) HCalib->step[i] = cstep[i];
     for (int f = 0; f < nf_; f++) {
       auto* fh = ef_->frames[f]->data;
@@ -659,7 +641,7 @@ class WindowedBA {
     lastRemoved = nResRemoved;
     // ---- EnergyFunctional
     ef->lastX.resize(n); ef->lastbS.resize(n); ef->lastHS.resize(n, n);
-    for (int i = 0; i < n; i++) { ef->lastX[i] = lx[i]; ef->lastbS[i] = lbs[i]; for (int j = 0; j < n; j++) ef->lastHS(i, j) = lhs[(size_t)i * n + j]; }
+    fill_(ef->lastX, lx.data(), n); fill_(ef->lastbS, lbs.data(), n); fill_(ef->lastHS, lhs.data(), n, n);
     ef->resInA = P.resInA; ef->resInL = P.resInL;
     lastResult = out;
     return (float)out.rmse;
@@ -685,7 +667,7 @@ class WindowedBA {
     const int n = 8 * nf_ + 4;
     dev_.check(sdso_ba_marginalize_points(dev_.ctx(), win_, flag.data(), HM_.data(), bM_.data()), "sdso_ba_marginalize_points");
     marg_valid_ = true; acc_valid_ = lin_valid_ = app_valid_ = false;
-    for (int i = 0; i < n; i++) { ef->bM[i] = bM_[i]; for (int j = 0; j < n; j++) ef->HM(i, j) = HM_[(size_t)i * n + j]; }
+    fill_(ef->bM, bM_.data(), n); fill_(ef->HM, HM_.data(), n, n);
     int resInM = 0;                                        // resInM += accSSE_top_A->nres[0] (EnergyFunctional.cpp:704)
     dev_.check(sdso_ba_get_counts(dev_.ctx(), win_, nullptr, nullptr, &resInM), "sdso_ba_get_counts");
     ef->resInM += resInM - resInM_seen_; resInM_seen_ = resInM;
@@ -728,7 +710,7 @@ class WindowedBA {
     std::vector<double> H((size_t)m * m), b(m);
     dev_.check(sdso_ba_marginalize_frame_dev(dev_.ctx(), win_, idx, H.data(), b.data()), "sdso_ba_marginalize_frame_dev");
     ef->HM.resize(m, m); ef->bM.resize(m);
-    for (int i = 0; i < m; i++) { ef->bM[i] = b[i]; for (int j = 0; j < m; j++) ef->HM(i, j) = H[(size_t)i * m + j]; }
+    fill_(ef->bM, b.data(), m); fill_(ef->HM, H.data(), m, m);
     pending_rm_frames_.push_back(old_idx);
     for (size_t i = 0; i < residuals_.size(); i++)         // FullSystem::marginalizeFrame drops them next (FullSystemMarginalize.cpp:150-180)
       if (residuals_[i] && residuals_[i]->target == f) { res_index_.erase(residuals_[i]->data); residuals_[i] = nullptr; }
@@ -740,15 +722,10 @@ class WindowedBA {
     for (int k = 0; k < nf_old; k++)
       if (std::find(pending_rm_frames_.begin(), pending_rm_frames_.end(), k) == pending_rm_frames_.end()) frame_old[frames_[k]] = k;
     // ---- stage 5: frames the shim has not seen (insertFrame appends, EnergyFunctional.cpp:465-466)
-    std::vector<double> evalPT, state, state_zero; std::vector<float> exposure, energyTH; std::vector<int> frameID, slots;
-    int n_add_frames = 0;
+    FrameCols F; int n_add_frames = 0;
     for (auto* f : ef->frames) {
       if (frame_old.count(f)) { if (n_add_frames) throw Error("update: a known frame follows a new one"); continue; }
-      auto* fh = f->data;
-      const sdso_se3_t T = toAbi(fh->get_worldToCam_evalPT());
-      evalPT.insert(evalPT.end(), T.R, T.R + 9); evalPT.insert(evalPT.end(), T.t, T.t + 3);
-      for (int i = 0; i < 10; i++) { state.push_back(fh->get_state()[i]); state_zero.push_back(fh->get_state_zero()[i]); }
-      exposure.push_back(fh->ab_exposure); energyTH.push_back(fh->frameEnergyTH); frameID.push_back(fh->frameID); slots.push_back(slot_of(fh));
+      F.push(f->data, slot_of);
       frame_old[f] = nf_old + n_add_frames++;
     }
     auto frame_of = [&](const void* f) {
@@ -757,9 +734,7 @@ class WindowedBA {
       return it->second;
     };
     // ---- stages 6 and 7: the residuals and points the shim has not seen, in makeIDX order (EnergyFunctional.cpp:998-1018)
-    std::vector<int> ar_point, ar_target, pt_host, pt_ngood, pr_point, pr_target;
-    std::vector<uint8_t> ar_state, ar_new, pt_prior, pr_state, pr_new;
-    std::vector<float> pt_u, pt_v, pt_id, pt_idz, pt_col, pt_wgt, pt_mrb;
+    ResCols ar, pr; PointCols pt;                          // stage 6: residuals into known points; stage 7: the new points and theirs
     std::vector<int> want_point, want_res;                 // what sdso_ba_window_get_order must say
     decltype(points_) new_points; decltype(residuals_) new_residuals;
     for (auto* f : ef->frames)
@@ -772,23 +747,17 @@ class WindowedBA {
             new_residuals.push_back(r);
             auto ir = res_index_.find(r->data);
             if (ir != res_index_.end()) { want_res.push_back(ir->second); continue; }
-            want_res.push_back(-1 - (int)ar_point.size());
-            ar_point.push_back(it->second); ar_target.push_back(frame_of(r->target));
-            ar_state.push_back((uint8_t)r->data->state_state); ar_new.push_back(r->data->isNew ? 1 : 0);
+            want_res.push_back(-1 - (int)ar.point.size());
+            ar.push(it->second, frame_of(r->target), r->data);
           }
         } else {
-          auto* ph = p->data;
-          const int q = (int)pt_host.size();
+          const int q = (int)pt.host.size();
           want_point.push_back(-1 - q);
-          pt_host.push_back(frame_of(f));
-          pt_u.push_back(ph->u); pt_v.push_back(ph->v); pt_id.push_back(ph->idepth); pt_idz.push_back(ph->idepth_zero);
-          for (int k = 0; k < 8; k++) { pt_col.push_back(ph->color[k]); pt_wgt.push_back(ph->weights[k]); }
-          pt_prior.push_back(ph->hasDepthPrior ? 1 : 0); pt_mrb.push_back(ph->maxRelBaseline); pt_ngood.push_back(ph->numGoodResiduals);
+          pt.push(p->data, frame_of(f));
           for (auto* r : p->residualsAll) {
             new_residuals.push_back(r);
-            want_res.push_back(-(int)pr_point.size() - 1);   // (+ the stage-6 count, added below)
-            pr_point.push_back(q); pr_target.push_back(frame_of(r->target));
-            pr_state.push_back((uint8_t)r->data->state_state); pr_new.push_back(r->data->isNew ? 1 : 0);
+            want_res.push_back(-(int)pr.point.size() - 1);   // (+ the stage-6 count, added below)
+            pr.push(q, frame_of(r->target), r->data);
           }
         }
       }
@@ -796,7 +765,7 @@ class WindowedBA {
       size_t i = 0;
       for (size_t p = 0; p < new_points.size(); p++) {
         const size_t cnt = new_points[p]->residualsAll.size();
-        if (want_point[p] < 0) for (size_t k = 0; k < cnt; k++) want_res[i + k] -= (int)ar_point.size();
+        if (want_point[p] < 0) for (size_t k = 0; k < cnt; k++) want_res[i + k] -= (int)ar.point.size();
         i += cnt;
       }
     }
@@ -807,16 +776,16 @@ class WindowedBA {
     E.drop_point = pending_drop_flags_.empty() ? nullptr : pending_drop_flags_.data();
     E.n_remove_frames = (int)pending_rm_frames_.size(); E.remove_frames = pending_rm_frames_.data();
     E.n_add_frames = n_add_frames;
-    E.evalPT = evalPT.data(); E.state = state.data(); E.state_zero = state_zero.data();
-    E.ab_exposure = exposure.data(); E.frameEnergyTH = energyTH.data(); E.frameID = frameID.data(); E.frame_slot = slots.data();
-    E.n_add_res = (int)ar_point.size(); E.add_res_point = ar_point.data(); E.add_res_target = ar_target.data();
-    E.add_res_state = ar_state.data(); E.add_res_isNew = ar_new.data();
-    E.n_add_points = (int)pt_host.size(); E.pt_host = pt_host.data();
-    E.pt_u = pt_u.data(); E.pt_v = pt_v.data(); E.pt_idepth = pt_id.data(); E.pt_idepth_zero = pt_idz.data();
-    E.pt_color = pt_col.data(); E.pt_weights = pt_wgt.data();
-    E.pt_hasDepthPrior = pt_prior.data(); E.pt_maxRelBaseline = pt_mrb.data(); E.pt_numGoodResiduals = pt_ngood.data();
-    E.n_pt_res = (int)pr_point.size(); E.pt_res_point = pr_point.data(); E.pt_res_target = pr_target.data();
-    E.pt_res_state = pr_state.data(); E.pt_res_isNew = pr_new.data();
+    E.evalPT = F.evalPT.data(); E.state = F.state.data(); E.state_zero = F.state_zero.data();
+    E.ab_exposure = F.exposure.data(); E.frameEnergyTH = F.energyTH.data(); E.frameID = F.frameID.data(); E.frame_slot = F.slots.data();
+    E.n_add_res = (int)ar.point.size(); E.add_res_point = ar.point.data(); E.add_res_target = ar.target.data();
+    E.add_res_state = ar.state.data(); E.add_res_isNew = ar.isNew.data();
+    E.n_add_points = (int)pt.host.size(); E.pt_host = pt.host.data();
+    E.pt_u = pt.u.data(); E.pt_v = pt.v.data(); E.pt_idepth = pt.idepth.data(); E.pt_idepth_zero = pt.idepth_zero.data();
+    E.pt_color = pt.color.data(); E.pt_weights = pt.weights.data();
+    E.pt_hasDepthPrior = pt.prior.data(); E.pt_maxRelBaseline = pt.maxRelBaseline.data(); E.pt_numGoodResiduals = pt.numGood.data();
+    E.n_pt_res = (int)pr.point.size(); E.pt_res_point = pr.point.data(); E.pt_res_target = pr.target.data();
+    E.pt_res_state = pr.state.data(); E.pt_res_isNew = pr.isNew.data();
     dev_.check(sdso_ba_window_update(dev_.ctx(), win_, &E), "sdso_ba_window_update");
     // ---- the device's order is the EnergyFunctional's, or the two have drifted apart
     const int nf2 = (int)ef->frames.size();
@@ -828,9 +797,7 @@ class WindowedBA {
     }
     if (ps != want_point || rs != want_res) throw Error("update: the device window's order differs from the EnergyFunctional's (a removal the shim was not told about?)");
     points_.swap(new_points); residuals_.swap(new_residuals);
-    res_index_.clear(); point_index_.clear();
-    for (size_t i = 0; i < residuals_.size(); i++) res_index_[residuals_[i]->data] = (int)i;
-    for (size_t i = 0; i < points_.size(); i++) point_index_[points_[i]] = (int)i;
+    reindex_();
     frames_.assign(ef->frames.begin(), ef->frames.end());
     nf_ = nf2; ef_ = ef;
     HM_.assign((size_t)(8 * nf2 + 4) * (8 * nf2 + 4), 0.0); bM_.assign(8 * nf2 + 4, 0.0);   // (host copies of the prior: sized per window, filled by marginalizePointsF)
@@ -864,7 +831,7 @@ class WindowedBA {
     Hp[which] = Hs.data(); bp[which] = bs.data();
     dev_.check(sdso_ba_get_stitched(dev_.ctx(), win_, Hp[0], bp[0], Hp[1], bp[1], Hp[2], bp[2]), "sdso_ba_get_stitched");
     H.resize(n, n); b.resize(n);
-    for (int i = 0; i < n; i++) { b(i) = bs[i]; for (int j = 0; j < n; j++) H(i, j) = Hs[(size_t)i * n + j]; }
+    fill_(b, bs.data(), n); fill_(H, Hs.data(), n, n);
   }
   template <class PointFrameResidualT> int index_of_(PointFrameResidualT* r) const {
     auto it = res_index_.find(r);
@@ -879,11 +846,44 @@ class WindowedBA {
   std::unordered_map<const void*, int> res_index_, point_index_;
   std::vector<uint8_t> l_state_, a_state_, a_act_;
   std::vector<float> l_energy_, l_energyWO_;
-  std::vector<double> evalPT_, state_, state_zero_, HM_, bM_;
-  std::vector<float> exposure_, energyTH_, u_, v_, idepth_, idepth_zero_, color_, weights_;
-  std::vector<float> maxRelBaseline_;
-  std::vector<int> frameID_, slots_, host_, res_point_, res_target_, numGood_;
-  std::vector<uint8_t> prior_, res_state_, isNew_;
+  // ---- a frame's, a point's and a residual's record as columns of the ABI's arrays: upload() fills one set for the window, update() one for its gains
+  struct FrameCols {
+    std::vector<double> evalPT, state, state_zero; std::vector<float> exposure, energyTH; std::vector<int> frameID, slots;
+    void clear() { evalPT.clear(); state.clear(); state_zero.clear(); exposure.clear(); energyTH.clear(); frameID.clear(); slots.clear(); }
+    template <class FrameHessianT, class SlotOf> void push(FrameHessianT* fh, SlotOf& slot_of) {
+      const sdso_se3_t T = toAbi(fh->get_worldToCam_evalPT());
+      evalPT.insert(evalPT.end(), T.R, T.R + 9); evalPT.insert(evalPT.end(), T.t, T.t + 3);
+      for (int i = 0; i < 10; i++) { state.push_back(fh->get_state()[i]); state_zero.push_back(fh->get_state_zero()[i]); }
+      exposure.push_back(fh->ab_exposure); energyTH.push_back(fh->frameEnergyTH); frameID.push_back(fh->frameID); slots.push_back(slot_of(fh));
+    }
+  };
+  struct PointCols {
+    std::vector<float> u, v, idepth, idepth_zero, color, weights, maxRelBaseline; std::vector<int> host, numGood; std::vector<uint8_t> prior;
+    void clear() { u.clear(); v.clear(); idepth.clear(); idepth_zero.clear(); color.clear(); weights.clear(); maxRelBaseline.clear(); host.clear(); numGood.clear(); prior.clear(); }
+    template <class PointHessianT> void push(PointHessianT* ph, int host_idx) {
+      u.push_back(ph->u); v.push_back(ph->v); idepth.push_back(ph->idepth); idepth_zero.push_back(ph->idepth_zero);
+      for (int k = 0; k < 8; k++) { color.push_back(ph->color[k]); weights.push_back(ph->weights[k]); }
+      host.push_back(host_idx); prior.push_back(ph->hasDepthPrior ? 1 : 0);
+      maxRelBaseline.push_back(ph->maxRelBaseline); numGood.push_back(ph->numGoodResiduals);
+    }
+  };
+  struct ResCols {
+    std::vector<int> point, target; std::vector<uint8_t> state, isNew;
+    void clear() { point.clear(); target.clear(); state.clear(); isNew.clear(); }
+    template <class PointFrameResidualT> void push(int point_idx, int target_idx, PointFrameResidualT* pfr) {
+      point.push_back(point_idx); target.push_back(target_idx); state.push_back((uint8_t)pfr->state_state); isNew.push_back(pfr->isNew ? 1 : 0);
+    }
+  };
+  // a vector / an n x m matrix of the reference (Eigen: [i] / (i, j)) from a row-major buffer of the ABI
+  template <class V> static void fill_(V& v, const double* src, int n) { for (int i = 0; i < n; i++) v[i] = src[i]; }
+  template <class M> static void fill_(M& H, const double* src, int n, int m) { for (int i = 0; i < n; i++) for (int j = 0; j < m; j++) H(i, j) = src[(size_t)i * m + j]; }
+  void reindex_() {                                        // points_ / residuals_ -> their index maps
+    res_index_.clear(); point_index_.clear();
+    for (size_t i = 0; i < residuals_.size(); i++) res_index_[residuals_[i]->data] = (int)i;
+    for (size_t i = 0; i < points_.size(); i++) point_index_[points_[i]] = (int)i;
+  }
+  FrameCols up_frames_; PointCols up_points_; ResCols up_res_;   // upload()'s buffers, kept from call to call
+  std::vector<double> HM_, bM_;
   // an SE3 of the reference's type from R, t (Sophus::SE3d(Matrix3d, Vector3d); the prototype only lends its types)
   template <class SE3T>
   static SE3T like(const SE3T& proto, const sdso_se3_t& a) {

@@ -8,104 +8,9 @@
 // pointHessians.  upload for every host, makeDistanceMap, activatePointsMT, the caller's loop over the records (FullSystemOptPoint.cpp:
 // 196-237, FullSystem.cpp:923-933), download.  Dumped: the geometries, the records, the new pointHessians, the set afterwards, the map.
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
 #include "sdso_shim.h"
-
-template <class T>
-static std::vector<T> load(const std::string& dir, const std::string& name) {
-  std::ifstream f(dir + "/" + name + ".bin", std::ios::binary);
-  if (!f) { std::fprintf(stderr, "missing %s\n", name.c_str()); std::exit(2); }
-  f.seekg(0, std::ios::end);
-  const size_t bytes = (size_t)f.tellg();
-  f.seekg(0);
-  std::vector<T> v(bytes / sizeof(T));
-  f.read(reinterpret_cast<char*>(v.data()), (std::streamsize)(v.size() * sizeof(T)));
-  return v;
-}
-template <class T>
-static void dump(const std::string& dir, const std::string& name, const T* p, size_t n) {
-  std::ofstream f(dir + "/out_" + name + ".bin", std::ios::binary);
-  f.write(reinterpret_cast<const char*>(p), (std::streamsize)(n * sizeof(T)));
-}
-
-struct Mat33 { double m[9]; double& operator()(int i, int j) { return m[i * 3 + j]; } double operator()(int i, int j) const { return m[i * 3 + j]; } };
-struct Vec3 { double v[3]; double& operator[](int i) { return v[i]; } double operator[](int i) const { return v[i]; } };
-struct Vec2f { float v[2]; float& operator[](int i) { return v[i]; } float operator[](int i) const { return v[i]; } };
-struct Vec3f { float v[3]; float& operator[](int i) { return v[i]; } float operator[](int i) const { return v[i]; } };
-struct Mat22f { float m[4]; float& operator()(int i, int j) { return m[i * 2 + j]; } float operator()(int i, int j) const { return m[i * 2 + j]; } };
-struct Mat33f { float m[9]; float& operator()(int i, int j) { return m[i * 3 + j]; } float operator()(int i, int j) const { return m[i * 3 + j]; } };
-struct SE3 {
-  Mat33 R; Vec3 t;
-  const Mat33& rotationMatrix() const { return R; }
-  const Vec3& translation() const { return t; }
-  SE3 operator*(const SE3& o) const {
-    SE3 r;
-    for (int i = 0; i < 3; i++) {
-      for (int j = 0; j < 3; j++) r.R(i, j) = (R(i, 0) * o.R(0, j) + R(i, 1) * o.R(1, j)) + R(i, 2) * o.R(2, j);
-      r.t[i] = ((R(i, 0) * o.t[0] + R(i, 1) * o.t[1]) + R(i, 2) * o.t[2]) + t[i];
-    }
-    return r;
-  }
-};
-struct CalibHessian {
-  float f[4];
-  float fxl() const { return f[0]; } float fyl() const { return f[1]; } float cxl() const { return f[2]; } float cyl() const { return f[3]; }
-};
-enum ResState { IN = 0, OOB, OUTLIER };                                   // FullSystem/Residuals.h:43
-struct FrameHessian;
-struct ImmaturePoint {   // FullSystem/ImmaturePoint.h:60-102
-  float color[8], weights[8];
-  Mat22f gradH;
-  float u, v, my_type, idepth_min, idepth_max, quality, energyTH, lastTracePixelInterval;
-  Vec2f lastTraceUV;
-  int lastTraceStatus;
-  FrameHessian* host;
-  int idxInImmaturePoints;
-};
-struct PointFrameResidual { FrameHessian* host; FrameHessian* target; };
-struct PointHessian {    // FullSystem/HessianBlocks.h:382-459, the members the loop below and makeDistanceMap touch
-  float color[8], weights[8];
-  float u, v, my_type, idepth_scaled, idepth_zero, energyTH;
-  FrameHessian* host;
-  std::vector<PointFrameResidual*> residuals;
-  std::pair<PointFrameResidual*, ResState> lastResiduals[2];
-};
-struct FrameFramePrecalc { Mat33f PRE_RTll; Vec3f PRE_tTll; Vec2f PRE_aff_mode; };   // FullSystem/HessianBlocks.h:66-104
-struct FrameHessian {
-  SE3 PRE_worldToCam, PRE_camToWorld;
-  int idx = -1, slot = -1;
-  bool flaggedForMarginalization = false;
-  std::vector<FrameFramePrecalc> targetPrecalc;
-  std::vector<ImmaturePoint*> immaturePoints;
-  std::vector<PointHessian*> pointHessians;
-};
-
-static SE3 se3_of(const double* p) {
-  SE3 T;
-  for (int i = 0; i < 9; i++) T.R.m[i] = p[i];
-  for (int i = 0; i < 3; i++) T.t[i] = p[9 + i];
-  return T;
-}
-static void dump_points(const std::string& dir, const std::string& tag, const FrameHessian& fh) {
-  const size_t n = fh.immaturePoints.size();
-  std::vector<float> f(n * 30);
-  std::vector<uint8_t> st(n);
-  for (size_t i = 0; i < n; i++) {
-    const ImmaturePoint* p = fh.immaturePoints[i];
-    float* o = &f[i * 30];
-    o[0] = p->u; o[1] = p->v; o[2] = p->my_type; o[3] = p->idepth_min; o[4] = p->idepth_max; o[5] = p->quality;
-    for (int k = 0; k < 8; k++) { o[6 + k] = p->color[k]; o[14 + k] = p->weights[k]; }
-    o[22] = p->gradH(0, 0); o[23] = p->gradH(0, 1); o[24] = p->gradH(1, 0); o[25] = p->gradH(1, 1);
-    o[26] = p->energyTH; o[27] = p->lastTraceUV[0]; o[28] = p->lastTraceUV[1]; o[29] = p->lastTracePixelInterval;
-    st[i] = (uint8_t)p->lastTraceStatus;
-  }
-  dump(dir, tag + "_f", f.data(), f.size());
-  dump(dir, tag + "_st", st.data(), st.size());
-}
+#include "driver_io.h"
 
 static int run(const std::string& dir) {
   const auto meta = load<int>(dir, "meta");
@@ -139,12 +44,8 @@ static int run(const std::string& dir) {
     const auto gs = load<uint8_t>(dir, "group" + std::to_string(k) + "_st");
     for (size_t i = 0; i < gs.size(); i++) {
       ImmaturePoint* ip = new ImmaturePoint();
-      const float* o = &gf[i * 30];
-      ip->u = o[0]; ip->v = o[1]; ip->my_type = o[2]; ip->idepth_min = o[3]; ip->idepth_max = o[4]; ip->quality = o[5];
-      for (int c = 0; c < 8; c++) { ip->color[c] = o[6 + c]; ip->weights[c] = o[14 + c]; }
-      ip->gradH(0, 0) = o[22]; ip->gradH(0, 1) = o[23]; ip->gradH(1, 0) = o[24]; ip->gradH(1, 1) = o[25];
-      ip->energyTH = o[26]; ip->lastTraceUV[0] = o[27]; ip->lastTraceUV[1] = o[28]; ip->lastTracePixelInterval = o[29];
-      ip->lastTraceStatus = gs[i]; ip->host = &fh; ip->idxInImmaturePoints = (int)i;
+      point_from_record(ip, &gf[i * 30], gs[i]);
+      ip->host = &fh; ip->idxInImmaturePoints = (int)i;
       fh.immaturePoints.push_back(ip);
     }
     const auto sd = load<float>(dir, "seeds" + std::to_string(k));
@@ -155,7 +56,7 @@ static int run(const std::string& dir) {
     }
   }
 
-  CalibHessian Hcalib{{calib[0], calib[1], calib[2], calib[3]}};
+  CalibHessian Hcalib(calib[0], calib[1], calib[2], calib[3]);
   sdso_shim::PixelSelector pixelSelector(dev);
   using Imm = sdso_shim::ImmaturePoints<FrameHessian, CalibHessian, Mat33f>;
   Imm imm(dev, pixelSelector, Hcalib, frameHessians, [](const FrameHessian* f) { return f->slot; }, 0.f, 0.f);
@@ -200,7 +101,8 @@ static int run(const std::string& dir) {
     p->idepth_zero = p->idepth_scaled = a.idepth;                   // setIdepthZero / setIdepth (SCALE_IDEPTH = 1)
     for (int f = 0; f < nf; f++) {
       if (a.res_state[f] != ResState::IN) continue;
-      PointFrameResidual* r = new PointFrameResidual{p->host, frameHessians[f]};
+      PointFrameResidual* r = new PointFrameResidual;
+      r->host = p->host; r->target = frameHessians[f];
       p->residuals.push_back(r);
       if (r->target == frameHessians.back()) p->lastResiduals[0] = {r, ResState::IN};
       else if (r->target == (frameHessians.size() < 2 ? nullptr : frameHessians[frameHessians.size() - 2])) p->lastResiduals[1] = {r, ResState::IN};
@@ -224,7 +126,7 @@ static int run(const std::string& dir) {
     dump(dir, "ph" + std::to_string(k) + "_i", pi.data(), pi.size());
     if (!frames[k].immaturePoints.empty()) { std::fprintf(stderr, "host->immaturePoints was touched\n"); return 1; }
     imm.download(&frames[k]);
-    dump_points(dir, "h" + std::to_string(k), frames[k]);
+    dump_points(dir, "h" + std::to_string(k), frames[k], false);
   }
   dump(dir, "map", cdm.distFinal(), (size_t)(w / 2) * (h / 2));
   std::printf("activated %zu points", n);

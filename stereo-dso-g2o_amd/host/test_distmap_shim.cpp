@@ -6,70 +6,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
 #include "sdso_shim.h"
-
-template <class T>
-static std::vector<T> load(const std::string& dir, const char* name) {
-  std::ifstream f(dir + "/" + name + ".bin", std::ios::binary);
-  if (!f) { std::fprintf(stderr, "missing %s\n", name); std::exit(2); }
-  f.seekg(0, std::ios::end);
-  const size_t bytes = (size_t)f.tellg();
-  f.seekg(0);
-  std::vector<T> v(bytes / sizeof(T));
-  f.read(reinterpret_cast<char*>(v.data()), (std::streamsize)(v.size() * sizeof(T)));
-  return v;
-}
-template <class T>
-static void dump(const std::string& dir, const char* name, const T* p, size_t n) {
-  std::ofstream f(dir + "/out_" + name + ".bin", std::ios::binary);
-  f.write(reinterpret_cast<const char*>(p), (std::streamsize)(n * sizeof(T)));
-}
-
-struct Mat33 { double m[9]; double& operator()(int i, int j) { return m[i * 3 + j]; } double operator()(int i, int j) const { return m[i * 3 + j]; } };
-struct Vec3 { double v[3]; double& operator[](int i) { return v[i]; } double operator[](int i) const { return v[i]; } };
-struct Mat33f { float m[9]; float& operator()(int i, int j) { return m[i * 3 + j]; } float operator()(int i, int j) const { return m[i * 3 + j]; } };
-struct SE3 {
-  Mat33 R; Vec3 t;
-  const Mat33& rotationMatrix() const { return R; }
-  const Vec3& translation() const { return t; }
-  SE3 operator*(const SE3& o) const {
-    SE3 r;
-    for (int i = 0; i < 3; i++) {
-      for (int j = 0; j < 3; j++) r.R(i, j) = (R(i, 0) * o.R(0, j) + R(i, 1) * o.R(1, j)) + R(i, 2) * o.R(2, j);
-      r.t[i] = ((R(i, 0) * o.t[0] + R(i, 1) * o.t[1]) + R(i, 2) * o.t[2]) + t[i];
-    }
-    return r;
-  }
-};
-struct CalibHessian {
-  float f[4];
-  float fxl() const { return f[0]; } float fyl() const { return f[1]; } float cxl() const { return f[2]; } float cyl() const { return f[3]; }
-};
-struct FrameHessian;
-struct PointHessian { float u, v, idepth_scaled; };
-struct ImmaturePoint {
-  float u, v, idepth_min, idepth_max, quality, lastTracePixelInterval, my_type;
-  int lastTraceStatus;
-  FrameHessian* host;
-  int idxInImmaturePoints = -1;
-  int id;                       // position in the flattened input, to report the outcome
-};
-struct FrameHessian {
-  SE3 PRE_worldToCam, PRE_camToWorld;
-  bool flaggedForMarginalization = false;
-  std::vector<PointHessian*> pointHessians;
-  std::vector<ImmaturePoint*> immaturePoints;
-};
-
-static SE3 se3_of(const double* p) {
-  SE3 T;
-  for (int i = 0; i < 9; i++) T.R.m[i] = p[i];
-  for (int i = 0; i < 3; i++) T.t[i] = p[9 + i];
-  return T;
-}
+#include "driver_io.h"
 
 static int run(const std::string& dir) {
   const auto meta = load<int>(dir, "meta");   // w h levels nf
@@ -94,17 +32,19 @@ static int run(const std::string& dir) {
     frameHessians.push_back(&frames[f]);
   }
   std::vector<PointHessian> phs(a_u.size());
-  for (size_t i = 0; i < a_u.size(); i++) { phs[i] = PointHessian{a_u[i], a_v[i], a_id[i]}; frames[a_host[i]].pointHessians.push_back(&phs[i]); }
+  for (size_t i = 0; i < a_u.size(); i++) { phs[i].u = a_u[i]; phs[i].v = a_v[i]; phs[i].idepth_scaled = a_id[i]; frames[a_host[i]].pointHessians.push_back(&phs[i]); }
   const int nc = (int)c_u.size();
   std::vector<ImmaturePoint*> all(nc);
   for (int i = 0; i < nc; i++) {
-    all[i] = new ImmaturePoint{c_u[i], c_v[i], c_min[i], c_max[i], c_q[i], c_itv[i], c_ty[i], c_st[i], &frames[c_host[i]], -1, i};
+    ImmaturePoint* p = all[i] = new ImmaturePoint();
+    p->u = c_u[i]; p->v = c_v[i]; p->idepth_min = c_min[i]; p->idepth_max = c_max[i]; p->quality = c_q[i]; p->lastTracePixelInterval = c_itv[i];
+    p->my_type = c_ty[i]; p->lastTraceStatus = c_st[i]; p->host = &frames[c_host[i]]; p->idxInImmaturePoints = -1; p->id = i;
     frames[c_host[i]].immaturePoints.push_back(all[i]);
   }
 
   sdso_shim::Device dev(0);
   sdso_shim::CoarseDistanceMap<Mat33f> cdm(dev, w, h);
-  CalibHessian Hcalib{{calib[0], calib[1], calib[2], calib[3]}};
+  CalibHessian Hcalib(calib[0], calib[1], calib[2], calib[3]);
   cdm.makeK(&Hcalib, levels, w, h);
   const size_t npix = (size_t)cdm.w[1] * cdm.h[1];
   std::vector<sdso_distmap_geom_t> geoms;

@@ -6,103 +6,9 @@
 // flags = the removal mask of host 0 after the traces.  A first frame without makeNewTraces heads frameHessians; makeNewTraces for every host, traceNewCoarseNonKey for every frame but the last,
 // traceNewCoarseKey for the last, download, remove, download.  Dumped: K, Ki, the geometries of every frame, every member of every point.
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
 #include "sdso_shim.h"
-
-template <class T>
-static std::vector<T> load(const std::string& dir, const std::string& name) {
-  std::ifstream f(dir + "/" + name + ".bin", std::ios::binary);
-  if (!f) { std::fprintf(stderr, "missing %s\n", name.c_str()); std::exit(2); }
-  f.seekg(0, std::ios::end);
-  const size_t bytes = (size_t)f.tellg();
-  f.seekg(0);
-  std::vector<T> v(bytes / sizeof(T));
-  f.read(reinterpret_cast<char*>(v.data()), (std::streamsize)(v.size() * sizeof(T)));
-  return v;
-}
-template <class T>
-static void dump(const std::string& dir, const std::string& name, const T* p, size_t n) {
-  std::ofstream f(dir + "/out_" + name + ".bin", std::ios::binary);
-  f.write(reinterpret_cast<const char*>(p), (std::streamsize)(n * sizeof(T)));
-}
-
-struct Mat33 { double m[9]; double& operator()(int i, int j) { return m[i * 3 + j]; } double operator()(int i, int j) const { return m[i * 3 + j]; } };
-struct Vec3 { double v[3]; double& operator[](int i) { return v[i]; } double operator[](int i) const { return v[i]; } };
-struct Vec2 { double v[2]; double operator[](int i) const { return v[i]; } };
-struct Vec2f { float v[2]; float& operator[](int i) { return v[i]; } float operator[](int i) const { return v[i]; } };
-struct Mat22f { float m[4]; float& operator()(int i, int j) { return m[i * 2 + j]; } float operator()(int i, int j) const { return m[i * 2 + j]; } };
-struct Mat33f { float m[9]; float& operator()(int i, int j) { return m[i * 3 + j]; } float operator()(int i, int j) const { return m[i * 3 + j]; } };
-struct SE3 {
-  Mat33 R; Vec3 t;
-  const Mat33& rotationMatrix() const { return R; }
-  const Vec3& translation() const { return t; }
-  SE3 operator*(const SE3& o) const {
-    SE3 r;
-    for (int i = 0; i < 3; i++) {
-      for (int j = 0; j < 3; j++) r.R(i, j) = (R(i, 0) * o.R(0, j) + R(i, 1) * o.R(1, j)) + R(i, 2) * o.R(2, j);
-      r.t[i] = ((R(i, 0) * o.t[0] + R(i, 1) * o.t[1]) + R(i, 2) * o.t[2]) + t[i];
-    }
-    return r;
-  }
-};
-struct AffLight {   // util/NumType.h:110-146
-  double a, b;
-  static Vec2 fromToVecExposure(float exposureF, float exposureT, AffLight g2F, AffLight g2T) {
-    if (exposureF == 0 || exposureT == 0) exposureT = exposureF = 1;
-    const double a = std::exp(g2T.a - g2F.a) * exposureT / exposureF;
-    return Vec2{{a, g2T.b - a * g2F.b}};
-  }
-};
-struct CalibHessian {
-  float f[4];
-  float fxl() const { return f[0]; } float fyl() const { return f[1]; } float cxl() const { return f[2]; } float cyl() const { return f[3]; }
-};
-struct FrameHessian;
-struct ImmaturePoint {   // FullSystem/ImmaturePoint.h:60-102
-  float color[8], weights[8];
-  Mat22f gradH;
-  float u, v, my_type, idepth_min, idepth_max, quality, energyTH, lastTracePixelInterval;
-  Vec2f lastTraceUV;
-  int lastTraceStatus;
-  FrameHessian* host;
-  int idxInImmaturePoints;
-};
-struct FrameHessian {
-  SE3 PRE_worldToCam, PRE_camToWorld;
-  float ab_exposure = 1;
-  AffLight g2l{0, 0};
-  AffLight aff_g2l() const { return g2l; }
-  int slot = -1;
-  std::vector<ImmaturePoint*> immaturePoints;
-};
-
-static SE3 se3_of(const double* p) {
-  SE3 T;
-  for (int i = 0; i < 9; i++) T.R.m[i] = p[i];
-  for (int i = 0; i < 3; i++) T.t[i] = p[9 + i];
-  return T;
-}
-static void dump_points(const std::string& dir, const std::string& tag, const FrameHessian& fh) {
-  const size_t n = fh.immaturePoints.size();
-  std::vector<float> f(n * 30);
-  std::vector<uint8_t> st(n);
-  for (size_t i = 0; i < n; i++) {
-    const ImmaturePoint* p = fh.immaturePoints[i];
-    float* o = &f[i * 30];
-    o[0] = p->u; o[1] = p->v; o[2] = p->my_type; o[3] = p->idepth_min; o[4] = p->idepth_max; o[5] = p->quality;
-    for (int k = 0; k < 8; k++) { o[6 + k] = p->color[k]; o[14 + k] = p->weights[k]; }
-    o[22] = p->gradH(0, 0); o[23] = p->gradH(0, 1); o[24] = p->gradH(1, 0); o[25] = p->gradH(1, 1);
-    o[26] = p->energyTH; o[27] = p->lastTraceUV[0]; o[28] = p->lastTraceUV[1]; o[29] = p->lastTracePixelInterval;
-    st[i] = (uint8_t)p->lastTraceStatus;
-    if (p->host != &fh || p->idxInImmaturePoints != (int)i) { std::fprintf(stderr, "host / idxInImmaturePoints not set\n"); std::exit(1); }
-  }
-  dump(dir, tag + "_f", f.data(), f.size());
-  dump(dir, tag + "_st", st.data(), st.size());
-}
+#include "driver_io.h"
 
 static int run(const std::string& dir) {
   const auto meta = load<int>(dir, "meta");
@@ -116,7 +22,7 @@ static int run(const std::string& dir) {
   std::vector<FrameHessian> hosts(nh), lefts(nfr), rights(nfr);
   auto setup = [&](FrameHessian& fh, int k, int slot) {
     fh.PRE_worldToCam = se3_of(&poses[24 * k]); fh.PRE_camToWorld = se3_of(&poses[24 * k + 12]);
-    fh.g2l = AffLight{affs[3 * k], affs[3 * k + 1]}; fh.ab_exposure = (float)affs[3 * k + 2];
+    fh.aff = AffLight{affs[3 * k], affs[3 * k + 1]}; fh.ab_exposure = (float)affs[3 * k + 2];
     fh.slot = slot;
   };
   std::vector<int> ws(levels), hs(levels);
@@ -139,7 +45,7 @@ static int run(const std::string& dir) {
     dev.check(sdso_upload_pyramid(dev.ctx(), rights[k].slot, 1, &w, &h, &pr), "sdso_upload_pyramid");
   }
 
-  CalibHessian Hcalib{{calib[0], calib[1], calib[2], calib[3]}};
+  CalibHessian Hcalib(calib[0], calib[1], calib[2], calib[3]);
   sdso_shim::PixelSelector pixelSelector(dev);
   sdso_shim::ImmaturePoints<FrameHessian, CalibHessian, Mat33f> imm(dev, pixelSelector, Hcalib, frameHessians, [](const FrameHessian* f) { return f->slot; }, calib[4],
                                                                     calib[5]);
@@ -170,11 +76,11 @@ static int run(const std::string& dir) {
     if (k + 1 < nfr) imm.traceNewCoarseNonKey(&lefts[k], &rights[k]);
     else imm.traceNewCoarseKey(&lefts[k], &rights[k]);
   }
-  for (int k = 0; k < nh; k++) { imm.download(&hosts[k]); dump_points(dir, "h" + std::to_string(k), hosts[k]); }
+  for (int k = 0; k < nh; k++) { imm.download(&hosts[k]); dump_points(dir, "h" + std::to_string(k), hosts[k], true); }
   if ((int)flags.size() != imm.count(&hosts[0])) { std::fprintf(stderr, "flags do not fit host 0\n"); return 1; }
   imm.remove(&hosts[0], flags);
   imm.download(&hosts[0]);
-  dump_points(dir, "removed", hosts[0]);
+  dump_points(dir, "removed", hosts[0], true);
   imm.release(&hosts[1]);
   for (int k = 0; k < nfr; k++) imm.traceNewCoarseKey(&lefts[k], &rights[k]);   // a released host is in frameHessians until the caller erases it
   imm.download(&first);

@@ -4,34 +4,12 @@
 // meta = wOrg hOrg w h bits model out_mode photometricCalibration useExposure; pars (8 doubles), out_calib (4 floats), exposure (2),
 // G, vinv, raw0, raw1.  Object A is built from the model parameters, object B from A's remap tables as caller-owned arrays; A ingests the
 // stereo pair in one call, B the two images one by one.  Dumped: K, size, remap tables, exposures, and every level of the four slots.
+#include <algorithm>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
 #include "sdso_shim.h"
+#include "driver_io.h"
 
-template <class T>
-static std::vector<T> load(const std::string& dir, const char* name) {
-  std::ifstream f(dir + "/" + name + ".bin", std::ios::binary);
-  if (!f) { std::fprintf(stderr, "missing %s\n", name); std::exit(2); }
-  f.seekg(0, std::ios::end);
-  const size_t bytes = (size_t)f.tellg();
-  f.seekg(0);
-  std::vector<T> v(bytes / sizeof(T));
-  f.read(reinterpret_cast<char*>(v.data()), (std::streamsize)(v.size() * sizeof(T)));
-  return v;
-}
-template <class T>
-static void dump(const std::string& dir, const std::string& name, const T* p, size_t n) {
-  std::ofstream f(dir + "/out_" + name + ".bin", std::ios::binary);
-  f.write(reinterpret_cast<const char*>(p), (std::streamsize)(n * sizeof(T)));
-}
-
-struct Mat33 { double m[9]; double& operator()(int i, int j) { return m[i * 3 + j]; } double operator()(int i, int j) const { return m[i * 3 + j]; } };
-struct Vector2i { int v[2]; int& operator[](int i) { return v[i]; } int operator[](int i) const { return v[i]; } };
-template <class T> struct MinimalImage { int w, h; T* data; };
 using Undistort = sdso_shim::Undistort<Mat33, Vector2i>;
 
 static void dump_slot(sdso_shim::Device& dev, const std::string& dir, const std::string& tag, int slot, int w, int h) {

@@ -8,142 +8,15 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
-#include <fstream>
-#include <memory>
 #include "sdso_shim.h"
+#include "driver_io.h"
 
-template <class T>
-static std::vector<T> load(const std::string& dir, const char* name) {
-  std::ifstream f(dir + "/" + name + ".bin", std::ios::binary | std::ios::ate);
-  if (!f) { std::fprintf(stderr, "missing %s\n", name); std::exit(2); }
-  const size_t bytes = (size_t)f.tellg();
-  std::vector<T> v(bytes / sizeof(T));
-  f.seekg(0);
-  f.read(reinterpret_cast<char*>(v.data()), bytes);
-  return v;
-}
-
-// ---- stand-ins with the reference's member names ------------------------------------------------
-struct Mat33 { double m[9]; double& operator()(int i, int j) { return m[i * 3 + j]; } double operator()(int i, int j) const { return m[i * 3 + j]; } };
-struct Vec3 { double v[3]; double& operator[](int i) { return v[i]; } double operator[](int i) const { return v[i]; } };
-struct Mat33f { float m[9]; float operator()(int i, int j) const { return m[i * 3 + j]; } };
-struct Mat22f { float m[4]; float operator()(int i, int j) const { return m[i * 2 + j]; } };
-struct SE3 {
-  Mat33 R; Vec3 t;
-  SE3() { for (int i = 0; i < 9; i++) R.m[i] = (i % 4 == 0); t = {{0, 0, 0}}; }
-  SE3(const Mat33& R_, const Vec3& t_) : R(R_), t(t_) {}
-  const Mat33& rotationMatrix() const { return R; }
-  const Vec3& translation() const { return t; }
-};
-struct AffLight { double a = 0, b = 0; };
-struct Vec3f { float v[3]; };
-struct Vec10 { double v[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; double& operator[](int i) { return v[i]; } double operator[](int i) const { return v[i]; } };
-struct VecC { double v[4] = {0, 0, 0, 0}; double& operator[](int i) { return v[i]; } double operator[](int i) const { return v[i]; } };
-struct Vec2f { float v[2] = {0, 0}; float& operator[](int i) { return v[i]; } };
-struct Vec3fv { float v[3] = {0, 0, 0}; float& operator[](int i) { return v[i]; } };
-struct CalibHessian {
-  VecC value_scaled, value_zero, value, step;
-  void setValue(const VecC& val) {                               // HessianBlocks.h:318-333 (SCALE_F = SCALE_C = 50)
-    value = val;
-    for (int i = 0; i < 4; i++) value_scaled[i] = 50.0 * val[i];
-  }
-  float fxl() const { return (float)value_scaled[0]; } float fyl() const { return (float)value_scaled[1]; }
-  float cxl() const { return (float)value_scaled[2]; } float cyl() const { return (float)value_scaled[3]; }
-};
-struct PointHessian;
-struct FrameShell { int id = 0; };
-struct FrameHessian {
-  Vec3f* dIp[SDSO_PYR_LEVELS];
-  std::vector<std::vector<float>> store;
-  SE3 worldToCam_evalPT; Vec10 state, state_zero, step;
-  float ab_exposure = 1, frameEnergyTH = 0; int frameID = 0, idx = 0, slot = 0;
-  std::vector<PointHessian*> pointHessians;                      // HessianBlocks.h:125
-  FrameShell shellStore; FrameShell* shell = &shellStore;
-  AffLight aff; AffLight aff_g2l() const { return aff; }         // HessianBlocks.h:185
-  const SE3& get_worldToCam_evalPT() const { return worldToCam_evalPT; }
-  const Vec10& get_state() const { return state; }
-  const Vec10& get_state_zero() const { return state_zero; }
-  void setState(const Vec10& s) { state = s; }                   // (the reference also refreshes state_scaled / PRE_worldToCam here: host math)
-  void setEvalPT(const SE3& T, const Vec10& s) { worldToCam_evalPT = T; state = s; state_zero = s; }   // HessianBlocks.h:216-222
-};
-struct EFFrame; struct EFPoint; struct EFResidual; struct PointHessian;
-struct PointFrameResidual {
-  int state_state = 0, state_NewState = 0;
-  double state_energy = 0, state_NewEnergy = 0, state_NewEnergyWithOutlier = 0;
-  bool isNew = true;
-  Vec2f projectedTo[SDSO_MAX_RES];
-  Vec3fv centerProjectedTo;
-  PointHessian* point = nullptr; EFResidual* efResidual = nullptr;
-  int id = -1;                                                   // index in the uploaded window (the test's bookkeeping)
-};
-struct PointHessian {
-  float u, v, idepth, idepth_zero, color[8], weights[8], step = 0, idepth_hessian = 0, maxRelBaseline = 0;
-  int numGoodResiduals = 0;
-  bool hasDepthPrior = false;
-  std::vector<PointFrameResidual*> residuals;
-  std::pair<PointFrameResidual*, int> lastResiduals[2] = {{nullptr, 2}, {nullptr, 2}};
-  EFPoint* efPoint = nullptr;
-  void setIdepth(float x) { idepth = x; }
-  void setIdepthZero(float x) { idepth_zero = x; }
-  bool isInlierNew() const { return (int)residuals.size() >= 3 && numGoodResiduals >= 4; }   // HessianBlocks.h:465-469; setting_minGoodActiveResForMarg = 3, setting_minGoodResForMarg = 4 (settings.cpp:82-83)
-};
-struct EFResidual { PointFrameResidual* data; EFFrame* target; bool isActiveAndIsGoodNEW = false; int idxInAll = 0; EFPoint* point = nullptr; bool isLinearized = false; };
-struct EFPoint { PointHessian* data; std::vector<EFResidual*> residualsAll; int stateFlag = 0; float HdiF = 0, bdSumF = 0, deltaF = 0; };
-struct Vec8 { double v[8] = {0, 0, 0, 0, 0, 0, 0, 0}; double& operator[](int i) { return v[i]; } };
-struct EFFrame { FrameHessian* data; std::vector<EFPoint*> points; int idx; Vec8 delta, delta_prior; };
-struct Mat88 { double m[64]; double& operator()(int i, int j) { return m[i * 8 + j]; } };
-struct Mat88f { float m[64]; float& operator()(int i, int j) { return m[i * 8 + j]; } };
-struct Mat18f { float m[8]; float& operator()(int, int j) { return m[j]; } };
-struct DynMat {
-  int n = 0; std::vector<double> d;
-  void resize(int r, int c) { n = c; d.assign((size_t)r * c, 0.0); }
-  double& operator()(int i, int j) { return d[(size_t)i * n + j]; }
-};
-struct DynVec {
-  std::vector<double> d;
-  void resize(int r) { d.assign((size_t)r, 0.0); }
-  double& operator()(int i) { return d[(size_t)i]; }
-};
-struct EnergyFunctional {
-  std::vector<EFFrame*> frames; DynMat HM, lastHS; std::vector<double> bM, lastbS, lastX;
-  int resInA = 0, resInL = 0, resInM = 0, nResiduals = 0;
-  Mat88 *adHost = 0, *adTarget = 0; Mat88f *adHostF = 0, *adTargetF = 0; Mat18f* adHTdeltaF = 0;   // EnergyFunctional.h:115-135
-  float cDeltaF[4] = {0, 0, 0, 0};
-  std::vector<EFPoint*> allPoints;
-  ~EnergyFunctional() { delete[] adHost; delete[] adTarget; delete[] adHostF; delete[] adTargetF; delete[] adHTdeltaF; }
-  void dropResidual(EFResidual* r) {                             // EnergyFunctional.cpp:519-548
-    EFPoint* p = r->point;
-    p->residualsAll[r->idxInAll] = p->residualsAll.back();
-    p->residualsAll[r->idxInAll]->idxInAll = r->idxInAll;
-    p->residualsAll.pop_back();
-    nResiduals--;
-    r->data->efResidual = nullptr;
-    delete r;
-  }
-};
-struct ImmaturePoint {
-  float u, v, idepth_max;
-  float u_stereo, v_stereo, idepth_min, idepth_min_stereo, idepth_max_stereo, idepth_stereo, energyTH, quality, color[8], weights[8];
-  Mat22f gradH; int lastTraceStatus; float lastTraceUV[2]; float lastTracePixelInterval;
-};
-struct Vec5 { double v[5]; double operator[](int i) const { return v[i]; } };
 // compile the temporal-trace wrapper against the stand-in as well (it is exercised through the C-ABI in tests/test_stereo.py)
 template void sdso_shim::traceOnAll<ImmaturePoint>(sdso_shim::Device&, std::vector<ImmaturePoint*>&, const std::vector<int>&, const std::vector<sdso_trace_geom_t>&, int,
                                                    std::vector<uint8_t>&);
-
-struct Vec3fc { float v[3]; float operator[](int i) const { return v[i]; } };
-struct Vec2fc { float v[2]; float operator[](int i) const { return v[i]; } };
 // ... and ImmaturePoint::traceOn's one-point form (ImmaturePoint.h:90)
-template int sdso_shim::traceOn<ImmaturePoint, Mat33f, Vec3fc, Vec2fc>(sdso_shim::Device&, ImmaturePoint*, int, const Mat33f&, const Vec3fc&, const Vec2fc&);
+template int sdso_shim::traceOn<ImmaturePoint, Mat33f, Vec3f, Vec2f>(sdso_shim::Device&, ImmaturePoint*, int, const Mat33f&, const Vec3f&, const Vec2f&);
 
-static void load_pyramid(const std::string& dir, const char* prefix, FrameHessian& fh, int levels) {
-  fh.store.resize(levels);
-  for (int l = 0; l < levels; l++) {
-    char nm[64]; std::snprintf(nm, sizeof nm, "%s_l%d", prefix, l);
-    fh.store[l] = load<float>(dir, nm);
-    fh.dIp[l] = reinterpret_cast<Vec3f*>(fh.store[l].data());
-  }
-}
 
 static int run_tracker(const std::string& dir, bool fork_live) {
   auto meta = load<int>(dir, "meta");             // levels, w0, h0, coarsestLvl
@@ -184,9 +57,6 @@ static int run_tracker(const std::string& dir, bool fork_live) {
   return 0;
 }
 
-template <class T>
-static void dump(const std::string& dir, const char* name, const std::vector<T>& v);
-
 // CoarseTracker::setCoarseTrackingRef(frameHessians, fh_right, Hcalib) and setCTRefForFirstFrame(frameHessians) with the reference's
 // signatures on a small pointer graph: frames with pointHessians whose lastResiduals[0] / centerProjectedTo / efPoint->HdiF are what
 // FullSystem::optimize left.  The template levels come back through sdso_track_get_ref and are dumped for tests/test_host_shim.py, which
@@ -199,37 +69,34 @@ static int run_tracker_ref(const std::string& dir) {
   auto rstate = load<int>(dir, "rstate"), frame_of = load<int>(dir, "frame_of");
   auto has_last = load<uint8_t>(dir, "has_last");
   sdso_shim::Device dev(0);
-  std::vector<std::unique_ptr<FrameHessian>> fhs;
+  std::vector<FrameHessian> fhs(nfr);
   FrameHessian right;
   int w[SDSO_PYR_LEVELS], h[SDSO_PYR_LEVELS];
   for (int l = 0; l < levels; l++) { w[l] = w0 >> l; h[l] = h0 >> l; }
-  for (int f = 0; f < nfr; f++) { fhs.emplace_back(new FrameHessian); fhs.back()->slot = 20 + f; fhs.back()->shellStore.id = 100 + f; fhs.back()->ab_exposure = 1.f + 0.01f * f; }
-  FrameHessian& target = *fhs.back();
+  for (int f = 0; f < nfr; f++) { fhs[f].slot = 20 + f; fhs[f].shell->id = 100 + f; fhs[f].ab_exposure = 1.f + 0.01f * f; }
+  FrameHessian& target = fhs.back();
   target.aff.a = 0.02; target.aff.b = 1.5;
   load_pyramid(dir, "left", target, levels);
   dev.uploadFrame(target.slot, &target, levels, w, h);
   load_pyramid(dir, "right", right, 1);
   right.slot = 40;
   dev.uploadFrame(right.slot, &right, 1, w, h);
-  std::vector<std::unique_ptr<PointHessian>> phs;
-  std::vector<std::unique_ptr<EFPoint>> efps;
-  std::vector<std::unique_ptr<PointFrameResidual>> pfrs;
+  std::vector<PointHessian> phs(n);                 // nothing is added or removed here: the objects live in these three lists
+  std::vector<EFPoint> efps(n);
+  std::vector<PointFrameResidual> pfrs(n);
   for (int i = 0; i < n; i++) {
-    phs.emplace_back(new PointHessian);
-    PointHessian& ph = *phs.back();
+    PointHessian& ph = phs[i];
     ph.u = pu[i]; ph.v = pv[i]; ph.idepth = pid[i];
-    efps.emplace_back(new EFPoint{&ph, {}, 0});
-    ph.efPoint = efps.back().get();
-    ph.efPoint->HdiF = hdi[i];
-    pfrs.emplace_back(new PointFrameResidual);
-    for (int k = 0; k < 3; k++) pfrs.back()->centerProjectedTo[k] = cpt[(size_t)i * 3 + k];
-    ph.lastResiduals[0] = {has_last[i] ? pfrs.back().get() : nullptr, rstate[i]};
-    fhs[frame_of[i]]->pointHessians.push_back(&ph);
+    efps[i].data = &ph; efps[i].HdiF = hdi[i];
+    ph.efPoint = &efps[i];
+    for (int k = 0; k < 3; k++) pfrs[i].centerProjectedTo[k] = cpt[(size_t)i * 3 + k];
+    ph.lastResiduals[0] = {has_last[i] ? &pfrs[i] : nullptr, (ResState)rstate[i]};
+    fhs[frame_of[i]].pointHessians.push_back(&ph);
   }
   CalibHessian HC;
   for (int i = 0; i < 4; i++) HC.value_scaled[i] = HC.value_zero[i] = kf[i];
   std::vector<FrameHessian*> frameHessians;
-  for (auto& f : fhs) frameHessians.push_back(f.get());
+  for (auto& f : fhs) frameHessians.push_back(&f);
   std::vector<int> o_pcn;
   for (int variant = 0; variant < 2; variant++) {
     sdso_shim::CoarseTracker<SE3, AffLight, Mat33, Vec3> tracker(dev, 5 + variant);
@@ -286,7 +153,7 @@ static int run_stereo(const std::string& dir, bool fork_live) {
     const int st = sdso_shim::traceStereo(dev, &fresh[i], 3, K, kf[4], meta[3] != 0);
     const ImmaturePoint &a = fresh[i], &b = store[i];
     if (st != (int)status[i] || a.lastTraceStatus != b.lastTraceStatus || std::memcmp(&a.idepth_min_stereo, &b.idepth_min_stereo, 4) || std::memcmp(&a.idepth_max_stereo, &b.idepth_max_stereo, 4) ||
-        std::memcmp(&a.idepth_stereo, &b.idepth_stereo, 4) || std::memcmp(&a.quality, &b.quality, 4) || std::memcmp(a.lastTraceUV, b.lastTraceUV, 8) ||
+        std::memcmp(&a.idepth_stereo, &b.idepth_stereo, 4) || std::memcmp(&a.quality, &b.quality, 4) || std::memcmp(&a.lastTraceUV, &b.lastTraceUV, 8) ||
         std::memcmp(&a.lastTracePixelInterval, &b.lastTracePixelInterval, 4)) {
       std::fprintf(stderr, "traceStereo (one point) differs from traceStereoAll at point %zu\n", i);
       return 3;
@@ -298,95 +165,24 @@ static int run_stereo(const std::string& dir, bool fork_live) {
   return 0;
 }
 
-template <class T>
-static void dump(const std::string& dir, const char* name, const std::vector<T>& v) {
-  std::ofstream f(dir + "/out_" + name + ".bin", std::ios::binary);
-  f.write(reinterpret_cast<const char*>(v.data()), (std::streamsize)(v.size() * sizeof(T)));
-}
-
 // FullSystem::optimize through the shim on a pointer graph built like the reference's (FrameHessian / PointHessian / PointFrameResidual /
 // EFFrame / EFPoint / EFResidual with residuals, residualsAll, lastResiduals), then everything the reference's callers read afterwards,
 // dumped as raw arrays (out_*.bin) for tests/test_host_shim.py to compare with the ORACLE's post-state:
 //   makeCoarseDepthL0 STEP1 (CoarseTracker.cpp:295-350): which points enter, their pixel and weight sqrtf(1e-3 / (HdiF + 1e-12))
 //   flagPointsForRemoval (FullSystem.cpp:1004-1035): marginalise / drop / keep decision of a point whose host is being marginalised
-// the pointer graph of one window, built like the reference's (FrameHessian / PointHessian / PointFrameResidual / EFFrame / EFPoint /
-// EFResidual with residuals, residualsAll, lastResiduals) from the raw arrays tests/test_host_shim.py wrote
-struct BaGraph {
-  std::vector<int> meta;
-  int nf = 0, np = 0, nr = 0, w = 0, h = 0;
-  std::vector<std::unique_ptr<FrameHessian>> fhs;
-  std::vector<std::unique_ptr<EFFrame>> effs;
-  std::vector<std::unique_ptr<PointHessian>> phs;
-  std::vector<std::unique_ptr<EFPoint>> efps;
-  std::vector<PointFrameResidual*> pfrs;                        // window order
-  std::vector<int> host;
-  EnergyFunctional ef;
-  CalibHessian HC;
-  void build(const std::string& dir, sdso_shim::Device& dev) {
-    meta = load<int>(dir, "meta");             // nf np nr w h its solverMode
-    nf = meta[0]; np = meta[1]; nr = meta[2]; w = meta[3]; h = meta[4];
-    auto calib = load<double>(dir, "calib");        // value_scaled(4) value_zero(4)
-    auto evalPT = load<double>(dir, "evalPT"), state = load<double>(dir, "state"), state_zero = load<double>(dir, "state_zero"),
-         HM = load<double>(dir, "HM"), bM = load<double>(dir, "bM");
-    auto exposure = load<float>(dir, "ab_exposure"), eTH = load<float>(dir, "frameEnergyTH");
-    auto frameID = load<int>(dir, "frameID"), res_point = load<int>(dir, "res_point"), res_target = load<int>(dir, "res_target");
-    host = load<int>(dir, "host");
-    auto u = load<float>(dir, "u"), v = load<float>(dir, "v"), idepth = load<float>(dir, "idepth"), idz = load<float>(dir, "idepth_zero"),
-         color = load<float>(dir, "color"), weights = load<float>(dir, "weights"), mrb = load<float>(dir, "maxRelBaseline");
-    auto prior = load<uint8_t>(dir, "hasDepthPrior"), res_state = load<uint8_t>(dir, "res_state"), isnew = load<uint8_t>(dir, "res_isNew");
-    auto ngood = load<int>(dir, "numGoodResiduals");
-    int wv[1] = {w}, hv[1] = {h};
-    for (int f = 0; f < nf; f++) {
-      fhs.emplace_back(new FrameHessian);
-      FrameHessian& fh = *fhs.back();
-      char nm[32]; std::snprintf(nm, sizeof nm, "img%d", f);
-      load_pyramid(dir, nm, fh, 1);
-      for (int i = 0; i < 9; i++) fh.worldToCam_evalPT.R.m[i] = evalPT[f * 12 + i];
-      for (int i = 0; i < 3; i++) fh.worldToCam_evalPT.t.v[i] = evalPT[f * 12 + 9 + i];
-      for (int i = 0; i < 10; i++) { fh.state[i] = state[f * 10 + i]; fh.state_zero[i] = state_zero[f * 10 + i]; }
-      fh.ab_exposure = exposure[f]; fh.frameEnergyTH = eTH[f]; fh.frameID = frameID[f]; fh.idx = f; fh.slot = 10 + f;
-      dev.uploadFrame(fh.slot, &fh, 1, wv, hv);
-      effs.emplace_back(new EFFrame{&fh, {}, f});
-      ef.frames.push_back(effs.back().get());
-    }
-    int r = 0;
-    for (int p = 0; p < np; p++) {
-      phs.emplace_back(new PointHessian);
-      PointHessian& ph = *phs.back();
-      ph.u = u[p]; ph.v = v[p]; ph.idepth = idepth[p]; ph.idepth_zero = idz[p]; ph.hasDepthPrior = prior[p] != 0;
-      ph.maxRelBaseline = mrb[p]; ph.numGoodResiduals = ngood[p];
-      for (int k = 0; k < 8; k++) { ph.color[k] = color[p * 8 + k]; ph.weights[k] = weights[p * 8 + k]; }
-      efps.emplace_back(new EFPoint{&ph, {}, 0});
-      ph.efPoint = efps.back().get();
-      for (; r < nr && res_point[r] == p; r++) {
-        // raw new: the shim deletes dropped residuals like the reference does (deleteOut / dropResidual)
-        PointFrameResidual* pfr = new PointFrameResidual;
-        pfr->state_state = (int)res_state[r]; pfr->isNew = isnew[r] != 0; pfr->point = &ph; pfr->id = r;
-        EFResidual* efr = new EFResidual{pfr, ef.frames[res_target[r]]};
-        efr->point = ph.efPoint; efr->idxInAll = (int)ph.efPoint->residualsAll.size();
-        pfr->efResidual = efr;
-        ph.efPoint->residualsAll.push_back(efr);
-        ph.residuals.push_back(pfr);
-        pfrs.push_back(pfr);
-        ef.nResiduals++;
-        // lastResiduals: [0] the residual into the newest frame, [1] into the one before (FullSystem.cpp:1400-1410)
-        if (res_target[r] == nf - 1) ph.lastResiduals[0] = {pfr, 0};
-        if (res_target[r] == nf - 2) ph.lastResiduals[1] = {pfr, 0};
-      }
-      ef.frames[host[p]]->points.push_back(ph.efPoint);   // points arrive grouped by host (makeIDX order)
-      ef.allPoints.push_back(ph.efPoint);
-    }
-    const int n = 8 * nf + 4;
-    ef.HM.n = n; ef.HM.d = HM; ef.bM = bM;
-    for (int i = 0; i < 4; i++) { HC.value_scaled[i] = calib[i]; HC.value_zero[i] = calib[4 + i]; }
-  }
-  ~BaGraph() { for (auto& ph : phs) for (PointFrameResidual* rr : ph->residuals) { delete rr->efResidual; delete rr; } }
-};
+// the window of tests/test_host_shim.py as the reference's pointer graph, every frame's level 0 uploaded to its slot
+static void build_ba(WindowGraph& G, const std::string& dir, sdso_shim::Device& dev) {
+  WindowGraph::Options o;
+  o.extras = true;
+  G.build(dir, o);
+  int wv[1] = {G.w}, hv[1] = {G.h};
+  for (FrameHessian* fh : G.fhs) dev.uploadFrame(fh->slot, fh, 1, wv, hv);
+}
 
 static int run_ba(const std::string& dir) {
   sdso_shim::Device dev(0);
-  BaGraph G;
-  G.build(dir, dev);
+  WindowGraph G;
+  build_ba(G, dir, dev);
   const int nf = G.nf, np = G.np, nr = G.nr, w = G.w, h = G.h;
   auto& meta = G.meta; auto& fhs = G.fhs; auto& phs = G.phs; EnergyFunctional& ef = G.ef; CalibHessian& HC = G.HC;
   sdso_shim::WindowedBA<EnergyFunctional, CalibHessian> ba(dev, 0);
@@ -447,7 +243,7 @@ static int run_ba(const std::string& dir) {
   dump(dir, "lastX", o_lastX); dump(dir, "lastbS", o_lastbS); dump(dir, "lastHS", o_lastHS); dump(dir, "counts", o_counts);
   // EnergyFunctional::accumulate{AF,LF,SCF}_MT at the state optimize() left (EnergyFunctional.cpp:212-269): the three stitched systems
   ba.linearizeAll(); ba.applyRes(); ba.accumulateAll();
-  DynMat H3[3]; DynVec b3[3];
+  MatXX H3[3]; VecX b3[3];
   ba.accumulateAF_MT(H3[0], b3[0], false); ba.accumulateLF_MT(H3[1], b3[1], false); ba.accumulateSCF_MT(H3[2], b3[2], false);
   std::vector<double> o_st;
   for (int k = 0; k < 3; k++) { o_st.insert(o_st.end(), H3[k].d.begin(), H3[k].d.end()); o_st.insert(o_st.end(), b3[k].d.begin(), b3[k].d.end()); }
@@ -463,8 +259,8 @@ static int run_ba(const std::string& dir) {
 //   marginalizePointsF's accumulator calls (:663-736) for the points of the oldest keyframe
 static int run_ba_members(const std::string& dir) {
   sdso_shim::Device dev(0);
-  BaGraph G;
-  G.build(dir, dev);
+  WindowGraph G;
+  build_ba(G, dir, dev);
   const int nf = G.nf, np = G.np, nr = G.nr, n = 8 * nf + 4;
   EnergyFunctional& ef = G.ef; CalibHessian& HC = G.HC;
   using BA = sdso_shim::WindowedBA<EnergyFunctional, CalibHessian>;
@@ -486,14 +282,14 @@ static int run_ba_members(const std::string& dir) {
     PointFrameResidual probe = *G.pfrs[0];
     EFResidual ep = *G.pfrs[0]->efResidual;
     probe.efResidual = &ep;
-    probe.state_state = 1 /* OOB */; probe.state_NewState = 2; probe.state_NewEnergy = 42.0; probe.state_energy = 1.0; ep.isActiveAndIsGoodNEW = true;
+    probe.state_state = OOB; probe.state_NewState = OUTLIER; probe.state_NewEnergy = 42.0; probe.state_energy = 1.0; ep.isActiveAndIsGoodNEW = true;
     ba.applyRes(&probe, false);
-    if (probe.state_state != 2 || probe.state_energy != 42.0 || !ep.isActiveAndIsGoodNEW) { std::fprintf(stderr, "applyRes(r, false) semantics\n"); return 1; }
+    if (probe.state_state != OUTLIER || probe.state_energy != 42.0 || !ep.isActiveAndIsGoodNEW) { std::fprintf(stderr, "applyRes(r, false) semantics\n"); return 1; }
     ep.isLinearized = true;
-    probe.state_state = 0; probe.state_NewState = 2; probe.state_energy = 3.0; probe.state_NewEnergy = 5.0; probe.state_NewEnergyWithOutlier = 7.0;
+    probe.state_state = IN; probe.state_NewState = OUTLIER; probe.state_energy = 3.0; probe.state_NewEnergy = 5.0; probe.state_NewEnergyWithOutlier = 7.0;
     const double e0 = ba.linearize(&probe, &HC);
     ba.applyRes(&probe, true);
-    if (e0 != 0.0 || probe.state_state != 0 || probe.state_NewState != 2 || probe.state_energy != 3.0 || probe.state_NewEnergy != 5.0 || probe.state_NewEnergyWithOutlier != 7.0) {
+    if (e0 != 0.0 || probe.state_state != IN || probe.state_NewState != OUTLIER || probe.state_energy != 3.0 || probe.state_NewEnergy != 5.0 || probe.state_NewEnergyWithOutlier != 7.0) {
       std::fprintf(stderr, "a linearised residual was touched\n"); return 1; }
   }
   dump(dir, "m_newState", o_ns); dump(dir, "m_state", o_st); dump(dir, "m_act", o_act); dump(dir, "m_newEnergy", o_ne); dump(dir, "m_newEnergyWO", o_nw); dump(dir, "m_energy", o_en);
@@ -507,12 +303,12 @@ static int run_ba_members(const std::string& dir) {
     for (int j = 0; j < 8; j++) o_htd[(size_t)k * 8 + j] = ef.adHTdeltaF[k].m[j];
   }
   for (int f = 0; f < nf; f++) for (int i = 0; i < 8; i++) { o_fd[f * 16 + i] = ef.frames[f]->delta[i]; o_fd[f * 16 + 8 + i] = ef.frames[f]->delta_prior[i]; }
-  for (int p = 0; p < np; p++) o_pd[p] = G.efps[p]->deltaF;
+  for (int p = 0; p < np; p++) o_pd[p] = G.phs[p]->efPoint->deltaF;
   dump(dir, "m_adjoints", o_ad); dump(dir, "m_adjointsF", o_adf); dump(dir, "m_adHTdeltaF", o_htd); dump(dir, "m_frame_delta", o_fd); dump(dir, "m_point_delta", o_pd); dump(dir, "m_cDeltaF", o_cd);
   // ---- the three accumulations through the accumulator classes (bodies of accumulateAF_MT / LF_MT / SCF_MT)
   sdso_shim::AccumulatedTopHessianSSE<BA> accSSE_top_A(ba), accSSE_top_L(ba);
   sdso_shim::AccumulatedSCHessianSSE<BA> accSSE_bot(ba);
-  DynMat H3[3]; DynVec b3[3];
+  MatXX H3[3]; VecX b3[3];
   const int nAll = (int)ef.allPoints.size();
   accSSE_top_A.setZero(nf);
   for (EFFrame* f : ef.frames) for (EFPoint* p : f->points) accSSE_top_A.addPoint<0>(p, &ef);            // the MT == false branch (:225-230)
@@ -533,15 +329,15 @@ static int run_ba_members(const std::string& dir) {
   std::vector<double> o_x = ef.lastX, o_bS = ef.lastbS, o_HS = ef.lastHS.d, o_fs(nf * 10), o_cs(HC.step.v, HC.step.v + 4);
   std::vector<float> o_ps(np * 3);
   for (int f = 0; f < nf; f++) for (int i = 0; i < 10; i++) o_fs[f * 10 + i] = G.fhs[f]->step[i];
-  for (int p = 0; p < np; p++) { o_ps[p * 3] = G.phs[p]->step; o_ps[p * 3 + 1] = G.efps[p]->HdiF; o_ps[p * 3 + 2] = G.efps[p]->bdSumF; }
+  for (int p = 0; p < np; p++) { o_ps[p * 3] = G.phs[p]->step; o_ps[p * 3 + 1] = G.phs[p]->efPoint->HdiF; o_ps[p * 3 + 2] = G.phs[p]->efPoint->bdSumF; }
   dump(dir, "m_lastX", o_x); dump(dir, "m_lastbS", o_bS); dump(dir, "m_lastHS", o_HS); dump(dir, "m_frame_step", o_fs); dump(dir, "m_calib_step", o_cs); dump(dir, "m_point_step", o_ps);
   std::vector<double> o_e = {E, ba.calcLEnergyF_MT(), ba.calcMEnergyF(), (double)ef.resInA, (double)ef.resInL};
   // ---- marginalizePointsF's accumulator calls for the points hosted in the oldest keyframe (EnergyFunctional.cpp:680-717)
-  DynMat M, Msc; DynVec Mb, Mbsc;
+  MatXX M, Msc; VecX Mb, Mbsc;
   accSSE_bot.setZero(nf); accSSE_top_A.setZero(nf);
   int nflag = 0;
   for (int p = 0; p < np; p++)
-    if (G.host[p] == 0) { accSSE_top_A.addPoint<2>(G.efps[p].get(), &ef); accSSE_bot.addPoint(G.efps[p].get(), false); nflag++; }
+    if (G.host[p] == 0) { accSSE_top_A.addPoint<2>(G.phs[p]->efPoint, &ef); accSSE_bot.addPoint(G.phs[p]->efPoint, false); nflag++; }
   accSSE_top_A.stitchDouble(M, Mb, &ef, false, false);
   accSSE_bot.stitchDouble(Msc, Mbsc, &ef);
   ef.resInM += accSSE_top_A.nres[0];

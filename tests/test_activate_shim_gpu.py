@@ -1,8 +1,6 @@
 """sdso_shim::ImmaturePoints::upload / activatePointsMT (host/sdso_shim.h) driven by host/test_activate_shim.cpp on stand-in types: the
 records it returns and the set it leaves equal the C-ABI path from Python exactly, and the caller's loop over the records builds the
 pointHessians the CPU statement of activatePointsMT (tests/activate_ref.py) predicts."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,10 +11,9 @@ import distmap_cases as DC
 import distmap_ref as D
 import immature_cases as Cs
 import immature_ref as R
+import shim_driver
 import synth
 
-HOST = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "stereo-dso-g2o_amd", "host")
-EXE = os.path.join(HOST, "test_activate_shim")
 f32 = np.float32
 W, H = Cs.W, Cs.H
 MIN_OBS = 1                      # what the reference passes (FullSystem.cpp:790)
@@ -25,33 +22,12 @@ IN, OOB = 0, 1                   # ResState
 
 @pytest.fixture(scope="module")
 def driver():
-    r = subprocess.run(["make", "-s", "-C", HOST, "test_activate_shim"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return EXE
+    return shim_driver.build("test_activate_shim")
 
 
 def test_activate_shim_driver_compiles():
     """CPU: upload / activatePointsMT of the shim + the driver compile against the ABI header with the plain host compiler."""
-    r = subprocess.run(["make", "-C", HOST, "-B", "test_activate_shim"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert os.path.exists(EXE)
-
-
-def _pack(S):
-    """the members of immature_ref -> the driver's 30 floats per point + status bytes"""
-    n = len(S["u"])
-    f = np.zeros((n, 30), f32)
-    for k, c in (("u", 0), ("v", 1), ("my_type", 2), ("idepth_min", 3), ("idepth_max", 4), ("quality", 5), ("energyTH", 26), ("lastTracePixelInterval", 29)):
-        f[:, c] = S[k]
-    f[:, 6:14] = S["color"]; f[:, 14:22] = S["weights"]; f[:, 22:26] = S["gradH"]; f[:, 27:29] = S["lastTraceUV"]
-    return f, np.ascontiguousarray(S["lastTraceStatus"], np.uint8)
-
-
-def _unpack(f, st):
-    f = f.reshape(-1, 30)
-    return dict(u=f[:, 0].copy(), v=f[:, 1].copy(), my_type=f[:, 2].copy(), idepth_min=f[:, 3].copy(), idepth_max=f[:, 4].copy(), quality=f[:, 5].copy(),
-                color=f[:, 6:14].copy(), weights=f[:, 14:22].copy(), gradH=f[:, 22:26].copy(), energyTH=f[:, 26].copy(), lastTraceStatus=st,
-                lastTraceUV=f[:, 27:29].copy(), lastTracePixelInterval=f[:, 29].copy())
+    shim_driver.rebuild("test_activate_shim")
 
 
 @pytest.mark.gpu
@@ -71,15 +47,10 @@ def test_shim_activation_equals_the_abi_path_and_the_statement(gpu_ctx, oracle, 
     for k in range(nf):
         arrays["frame%d" % k] = win["imgs"][k]
     for k in range(nf - 1):
-        arrays["group%d_f" % k], arrays["group%d_st" % k] = _pack(win["groups"][k])
+        arrays["group%d_f" % k], arrays["group%d_st" % k] = shim_driver.pack_points(win["groups"][k])
         arrays["seeds%d" % k] = np.stack([su[pg == k], sv[pg == k], sid[pg == k]], axis=1).astype(f32)
-    for k, a in arrays.items():
-        np.ascontiguousarray(a).tofile(os.path.join(tmp_path, k + ".bin"))
-    r = subprocess.run([driver, "run", str(tmp_path)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-
-    def out(name, dt):
-        return np.fromfile(os.path.join(tmp_path, "out_" + name + ".bin"), dtype=dt)
+    r = shim_driver.run("test_activate_shim", tmp_path, arrays, mode="run")
+    out = r.out
 
     # the geometries the driver formed from the poses (CoarseDistanceMap::geomOf) are the ones both comparisons use: frame 1's differs from
     # the case's crafted sideways geometry, so the window below is the driver's, not the case's
@@ -107,7 +78,7 @@ def test_shim_activation_equals_the_abi_path_and_the_statement(gpu_ctx, oracle, 
         for k in ("idepth", "u", "v", "my_type", "idepth_min", "idepth_max", "energyTH", "color", "weights"):
             assert np.array_equal(drv[k], got[k], equal_nan=True), k
         for k in range(nf - 1):
-            a, b = _unpack(out("h%d_f" % k, f32), out("h%d_st" % k, np.uint8)), ctx.imm_get(ids[k])
+            a, b = shim_driver.unpack_points(out("h%d_f" % k, f32), out("h%d_st" % k, np.uint8)), ctx.imm_get(ids[k])
             assert R.same(a, b) is None, (k, R.same(a, b))
         assert np.array_equal(out("map", f32).reshape(H >> 1, W >> 1), DC.dm_get(ctx, W, H))
         assert r.stdout.split() == ["activated", str(counts[4]), "points"] + [str(counts[9 + k]) for k in range(nf - 1)]

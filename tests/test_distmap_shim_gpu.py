@@ -1,32 +1,25 @@
 """sdso_shim::CoarseDistanceMap / selectPointsToActivate (host/sdso_shim.h) driven by host/test_distmap_shim.cpp on stand-in types:
 what the program finds in its objects equals the C-ABI path from Python on the same inputs, exactly."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import distmap_cases as Cs
 import distmap_ref as R
+import shim_driver
 import synth
 
-HOST = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "stereo-dso-g2o_amd", "host")
-EXE = os.path.join(HOST, "test_distmap_shim")
 f32 = np.float32
 
 
 @pytest.fixture(scope="module")
 def driver():
-    r = subprocess.run(["make", "-s", "-C", HOST, "test_distmap_shim"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return EXE
+    return shim_driver.build("test_distmap_shim")
 
 
 def test_distmap_shim_driver_compiles():
     """CPU: the shim's new members + the driver compile against the ABI header with the plain host compiler."""
-    r = subprocess.run(["make", "-C", HOST, "-B", "test_distmap_shim"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert os.path.exists(EXE)
+    shim_driver.rebuild("test_distmap_shim")
 
 
 @pytest.mark.gpu
@@ -50,15 +43,8 @@ def test_shim_distance_map_and_selection(gpu_ctx, driver, tmp_path):
                   c_host=c["pg"], c_status=c["status"].astype(np.int32), c_u=c["u"], c_v=c["v"], c_idepth_min=c["idepth_min"], c_idepth_max=c["idepth_max"],
                   c_quality=c["quality"], c_interval=c["interval"], c_my_type=c["my_type"],
                   par=np.array([case["min_act_dist"], case["min_trace_quality"]], f32), add=add)
-    for k, arr in arrays.items():
-        np.ascontiguousarray(arr).tofile(os.path.join(tmp_path, k + ".bin"))
-    r = subprocess.run([driver, "run", str(tmp_path)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    head = r.stdout.split()
-
-    def out(name, dt):
-        return np.fromfile(os.path.join(tmp_path, "out_" + name + ".bin"), dtype=dt)
-
+    r = shim_driver.run("test_distmap_shim", tmp_path, arrays, mode="run")
+    head, out = r.stdout.split(), r.out
     # the geometries the shim formed (K[1] * R * Ki[0], K[1] * t in float) are the caller's side of the C-ABI: the same values go
     # through it from here; they are the float products of the double poses up to the rounding of the order of operations
     g = out("geoms", f32).reshape(nhost, 12)

@@ -5,36 +5,24 @@ stand-ins that carry the reference's member names, goes through the shim, and pr
 problems pushed through the C-ABI from Python must give the same numbers (identical code path on the
 device, so equality is exact up to the %.17g / %.9g round trip of the printout)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import helpers
 from sdso_amd import abi
+import shim_driver
 import synth
 
-HOST = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "stereo-dso-g2o_amd", "host")
-EXE = os.path.join(HOST, "test_shim")
 
-
-def _dump(d, **arrays):
-    for k, a in arrays.items():
-        np.ascontiguousarray(a).tofile(os.path.join(d, k + ".bin"))
-
-
-def _run(d, what):
-    r = subprocess.run([EXE, str(d), what], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    return r.stdout.strip().splitlines()
+def _run(d, what, arrays):
+    """(no build step here: tests/conftest.py names host/test_shim as part of the build)"""
+    return shim_driver.run("test_shim", d, arrays, what)
 
 
 def test_shim_header_compiles():
     """CPU: the shim + driver compile against the ABI header with the plain host compiler."""
-    r = subprocess.run(["make", "-C", HOST, "-B", "test_shim"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert os.path.exists(EXE)
+    shim_driver.rebuild("test_shim")
 
 
 @pytest.mark.gpu
@@ -51,8 +39,8 @@ def test_shim_tracker(gpu_ctx, tmp_path):
         arrays["ref_l%d" % l] = prob["pyr_ref"][l]; arrays["new_l%d" % l] = prob["pyr_new"][l]
         for k in ("u", "v", "idepth", "color"):
             arrays["pc_%s_l%d" % (k, l)] = prob["pc"][l][k]
-    _dump(tmp_path, **arrays)
-    lines = _run(tmp_path, "tracker")
+    r = _run(tmp_path, "tracker", arrays)
+    lines = r.lines
     assert lines[0] == "good 1" and out.good == 1
     Tc = np.array(lines[1].split()[1:], np.float64)
     R, t = T.Rt()
@@ -80,15 +68,15 @@ def test_shim_fork_live_modes(gpu_ctx, tmp_path):
         arrays["ref_l%d" % l] = prob["pyr_ref"][l]; arrays["new_l%d" % l] = prob["pyr_new"][l]
         for k in ("u", "v", "idepth", "color"):
             arrays["pc_%s_l%d" % (k, l)] = prob["pc"][l][k]
-    _dump(tmp_path, **arrays)
-    lines = _run(tmp_path, "tracker_g2o")
+    r = _run(tmp_path, "tracker_g2o", arrays)
+    lines = r.lines
     assert lines[0] == "good 1" and out.good == 1
     Tc = np.array(lines[1].split()[1:], np.float64)
     R, t = T.Rt()
     assert np.array_equal(Tc[:9].reshape(3, 3), R) and np.array_equal(Tc[9:], t)       # same library, same calls: identical
     resc = np.array(lines[3].split()[1:], np.float64)
     assert np.array_equal(resc, np.array(list(out.lastResiduals)), equal_nan=True)
-    native = _run(tmp_path, "tracker")
+    native = _run(tmp_path, "tracker", {}).lines
     assert native[0] == "good 1" and native[1] != lines[1]                               # and it is not the native LM
 
 
@@ -104,10 +92,10 @@ def test_shim_trace_stereo(gpu_ctx, tmp_path):
     P, d = abi.make_trace_points(n, pr["u"], pr["v"], col, wgt, gH, eth)
     st = np.zeros(n, np.uint8)
     gpu_ctx.check(gpu_ctx.L.sdso_trace_stereo_batch(gpu_ctx.h, 81, abi.fp(K), bl, 1, C.byref(P), abi.bp(st)))
-    _dump(tmp_path, meta=np.array([640, 480, n, 1], np.int32), K=np.array(list(K) + [bl], np.float32), right_l0=right,
-          u_stereo=pr["u"], v_stereo=pr["v"], idepth_min=np.zeros(n, np.float32), idepth_min_stereo=np.zeros(n, np.float32),
-          idepth_max_stereo=np.full(n, np.nan, np.float32), color=col, weights=wgt, gradH=gH, energyTH=eth)
-    lines = _run(tmp_path, "stereo")
+    arrays = dict(meta=np.array([640, 480, n, 1], np.int32), K=np.array(list(K) + [bl], np.float32), right_l0=right,
+                  u_stereo=pr["u"], v_stereo=pr["v"], idepth_min=np.zeros(n, np.float32), idepth_min_stereo=np.zeros(n, np.float32),
+                  idepth_max_stereo=np.full(n, np.nan, np.float32), color=col, weights=wgt, gradH=gH, energyTH=eth)
+    lines = _run(tmp_path, "stereo", arrays).lines
     assert len(lines) == n
     got = np.array([[float(x) for x in ln.split()] for ln in lines])
     assert np.array_equal(got[:, 0].astype(np.uint8), st) and np.array_equal(got[:, 1].astype(np.uint8), d["lastTraceStatus"])
@@ -115,10 +103,6 @@ def test_shim_trace_stereo(gpu_ctx, tmp_path):
         assert np.array_equal(got[:, 2 + j].astype(np.float32), d[k], equal_nan=True), k
     assert np.array_equal(got[:, 6:8].astype(np.float32), d["lastTraceUV"], equal_nan=True)
     assert np.array_equal(got[:, 8].astype(np.float32), d["lastTracePixelInterval"], equal_nan=True)
-
-
-def _load(d, name, dt):
-    return np.fromfile(os.path.join(d, "out_" + name + ".bin"), dtype=dt)
 
 
 @pytest.mark.gpu
@@ -155,41 +139,28 @@ def test_shim_windowed_ba(gpu_ctx, oracle, tmp_path, which):
     oracle.orc_ba_get_stitched(h, *[abi.dp(a) for pair in st_o for a in pair])
     oracle.orc_ba_destroy(h)
     # ---- the C++ program
-    arrays = dict(meta=np.array([nf, npts, nr, win["w"], win["h"], 6, win["solverMode"]], np.int32),
-                  calib=np.concatenate([win["calib_value_scaled"], win["calib_value_zero"]]).astype(np.float64))
-    for k in ("evalPT", "state", "state_zero", "HM", "bM"):
-        arrays[k] = np.asarray(win[k], np.float64)
-    for k in ("ab_exposure", "frameEnergyTH", "u", "v", "idepth", "idepth_zero", "color", "weights", "maxRelBaseline"):
-        arrays[k] = np.asarray(win[k], np.float32)
-    for k in ("frameID", "host", "res_point", "res_target", "numGoodResiduals"):
-        arrays[k] = np.asarray(win[k], np.int32)
-    for k in ("hasDepthPrior", "res_state", "res_isNew"):
-        arrays[k] = np.asarray(win[k], np.uint8)
-    for f in range(nf):
-        arrays["img%d_l0" % f] = win["pyrs"][f][0]
-    _dump(tmp_path, **arrays)
-    lines = _run(tmp_path, "ba")
+    r = _run(tmp_path, "ba", _ba_arrays(win))
+    lines = r.lines
     head = lines[0].split()
-    d = str(tmp_path)
-    counts = _load(d, "counts", np.int32)          # resInA resInL resInM nResiduals removed iterations
-    pt = _load(d, "pt", np.float32).reshape(npts, 8); pi = _load(d, "pi", np.int32).reshape(npts, 8)
-    alive = _load(d, "alive", np.int32).astype(bool)
+    counts = r.out("counts", np.int32)          # resInA resInL resInM nResiduals removed iterations
+    pt = r.out("pt", np.float32).reshape(npts, 8); pi = r.out("pi", np.int32).reshape(npts, 8)
+    alive = r.out("alive", np.int32).astype(bool)
     # ---- pack what the program holds into the post-state layout and run the common field-by-field check
-    cal = _load(d, "calib", np.float64)
+    cal = r.out("calib", np.float64)
     dg = dict(idepth=pt[:, 0].copy(), step=pt[:, 2].copy(), idepth_hessian=pt[:, 3].copy(), maxRelBaseline=pt[:, 4].copy(), HdiF=pt[:, 5].copy(), bdSumF=pt[:, 6].copy(),
               numGoodResiduals=pi[:, 0].copy(),
-              state=_load(d, "state", np.float64).reshape(nf, 10), state_zero=_load(d, "state_zero", np.float64).reshape(nf, 10),
-              evalPT=_load(d, "evalPT", np.float64).reshape(nf, 12), frame_step=_load(d, "frame_step", np.float64).reshape(nf, 10),
-              frameEnergyTH=_load(d, "frameEnergyTH", np.float32), lastX=_load(d, "lastX", np.float64), lastbS=_load(d, "lastbS", np.float64),
-              lastHS=_load(d, "lastHS", np.float64).reshape(n, n))
+              state=r.out("state", np.float64).reshape(nf, 10), state_zero=r.out("state_zero", np.float64).reshape(nf, 10),
+              evalPT=r.out("evalPT", np.float64).reshape(nf, 12), frame_step=r.out("frame_step", np.float64).reshape(nf, 10),
+              frameEnergyTH=r.out("frameEnergyTH", np.float32), lastX=r.out("lastX", np.float64), lastbS=r.out("lastbS", np.float64),
+              lastHS=r.out("lastHS", np.float64).reshape(n, n))
     assert np.array_equal(pt[:, 0], pt[:, 1])                                       # setIdepth + setIdepthZero (:268-272)
     # the program dropped what linearizeAll(true) would: the survivors carry their state; dropped residuals are gone from both lists
-    rstate, ract = _load(d, "rstate", np.int32), _load(d, "ract", np.int32)
+    rstate, ract = r.out("rstate", np.int32), r.out("ract", np.int32)
     dg["toRemove"] = (~alive).astype(np.uint8)
     dg["isActiveAndIsGoodNEW"] = np.where(alive, ract, 0).astype(np.uint8)
     dg["state_state"] = np.where(alive, rstate, do["state_state"]).astype(np.uint8)   # (a dropped residual's state left with it)
-    dg["state_energy"] = np.where(alive, _load(d, "renergy", np.float32), do["state_energy"]).astype(np.float32)
-    dg["centerProjectedTo"] = _load(d, "cpt", np.float32).reshape(nr, 3); dg["projectedTo"] = _load(d, "prj", np.float32).reshape(nr, 16)
+    dg["state_energy"] = np.where(alive, r.out("renergy", np.float32), do["state_energy"]).astype(np.float32)
+    dg["centerProjectedTo"] = r.out("cpt", np.float32).reshape(nr, 3); dg["projectedTo"] = r.out("prj", np.float32).reshape(nr, 16)
     dg["PRE_worldToCam"] = do["PRE_worldToCam"].copy(); dg["PRE_worldToCam"][nf - 1] = dg["evalPT"][nf - 1]   # (host math of the reference's setState; the newest frame's is its evalPT)
 
     class G:                                                                          # the scalar members of the post-state
@@ -201,7 +172,7 @@ def test_shim_windowed_ba(gpu_ctx, oracle, tmp_path, which):
     flips = check_post_state(win, Po, do, Pg, dg)
     # accumulateAF_MT / accumulateLF_MT / accumulateSCF_MT through the shim: H, b of the top-A, top-L (priors) and Schur systems, each at its
     # own side's final state (they differ by the loop bars)
-    st = _load(d, "stitched", np.float64).reshape(3, n * n + n)
+    st = r.out("stitched", np.float64).reshape(3, n * n + n)
     dd = np.sqrt(np.abs(np.diag(do["lastHS"]))) + 1e-30
     for k, name in enumerate(("A", "L", "SC")):
         Hs, bs = st[k, :n * n].reshape(n, n), st[k, n * n:]
@@ -218,7 +189,7 @@ def test_shim_windowed_ba(gpu_ctx, oracle, tmp_path, which):
     # ---- the lists dropResidual / deleteOut left behind: the swap-with-last of the reference on the oracle's toRemove flags
     starts = np.searchsorted(win["res_point"], np.arange(npts), side="left"); ends = np.searchsorted(win["res_point"], np.arange(npts), side="right")
     expect = helpers.apply_drops([list(range(int(starts[p]), int(ends[p]))) for p in range(npts)], [int(i) for i in np.nonzero(dg["toRemove"])[0]])
-    lists = _load(d, "lists", np.int32)
+    lists = r.out("lists", np.int32)
     pos = 0
     for p in range(npts):
         e1 = pos + int(np.nonzero(lists[pos:] == -1)[0][0]); e2 = e1 + 1 + int(np.nonzero(lists[e1 + 1:] == -2)[0][0])
@@ -269,8 +240,8 @@ def test_shim_selector_and_marginalize_frame(gpu_ctx, tmp_path):
     arrays = dict(meta=np.array([640, 480, prob["levels"], 3, 1], np.int32), par=np.array([1500.0, 1.0], np.float32))
     for l in range(prob["levels"]):
         arrays["img_l%d" % l] = pyr[l]
-    _dump(tmp_path, **arrays)
-    lines = _run(tmp_path, "selector")
+    r = _run(tmp_path, "selector", arrays)
+    lines = r.lines
     f = lines[0].split()
     assert int(f[1]) == n.value and int(f[3]) == p.value
     assert [int(f[5]), int(f[7]), int(f[9])] == [int((m == 1).sum()), int((m == 2).sum()), int((m == 4).sum())]
@@ -357,11 +328,10 @@ def test_shim_energy_functional_members(oracle, tmp_path):
     oracle.orc_ba_get_post_state(h, C.byref(Po))
     oracle.orc_ba_destroy(h)
     # ---- the C++ program
-    _dump(tmp_path, **_ba_arrays(win))
-    lines = _run(tmp_path, "ba_members")
+    r = _run(tmp_path, "ba_members", _ba_arrays(win))
+    lines = r.lines
     assert lines[-1].startswith("members ok")
-    d = str(tmp_path)
-    m = lambda name, dt: _load(d, "m_" + name, dt)      # noqa: E731
+    m = lambda name, dt: r.out("m_" + name, dt)      # noqa: E731
     # per-object linearize / applyRes: decisions and energies of every residual, bit for bit
     assert np.array_equal(m("newState", np.int32), ns) and np.array_equal(m("state", np.int32), st) and np.array_equal(m("act", np.int32), act)
     lin = ns != 1
@@ -471,14 +441,14 @@ def test_shim_set_coarse_tracking_ref(oracle, tmp_path):
                   rstate=rstate, frame_of=frame_of, has_last=has_last, right_l0=right0)
     for l in range(L):
         arrays["left_l%d" % l] = left[l]
-    _dump(tmp_path, **arrays)
-    lines = _run(tmp_path, "tracker_ref")
+    r = _run(tmp_path, "tracker_ref", arrays)
+    lines = r.lines
     assert lines[-1] == "tracker_ref ok"
-    pcn = _load(str(tmp_path), "pcn", np.int32).reshape(2, L)
+    pcn = r.out("pcn", np.int32).reshape(2, L)
     for variant, exp in enumerate((exp0, exp1)):
         for l in range(L):
             npc = len(exp[l]["u"])
             assert pcn[variant, l] == npc and npc > 0, (variant, l)
-            got = _load(str(tmp_path), "pc_%d_l%d" % (variant, l), np.float32).reshape(4, npc)
+            got = r.out("pc_%d_l%d" % (variant, l), np.float32).reshape(4, npc)
             for a, k in zip(got, ("u", "v", "idepth", "color")):
                 assert np.array_equal(a, exp[l][k]), (variant, l, k)

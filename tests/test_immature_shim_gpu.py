@@ -3,8 +3,6 @@ traceNewCoarseNonKey and traceNewCoarseKey on the program's objects leave the sa
 driver's window is headed by a frame that never had makeNewTraces (the first keyframe of the reference's own call sequence) and is
 traced before any host has points: both are empty loops in the reference and must not fail here."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,34 +10,21 @@ import pytest
 from sdso_amd import abi
 import immature_cases as Cs
 import immature_ref as R
+import shim_driver
 import synth
 
-HOST = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "stereo-dso-g2o_amd", "host")
-EXE = os.path.join(HOST, "test_immature_shim")
 f32 = np.float32
 DENSITY = 600.0
 
 
 @pytest.fixture(scope="module")
 def driver():
-    r = subprocess.run(["make", "-s", "-C", HOST, "test_immature_shim"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return EXE
+    return shim_driver.build("test_immature_shim")
 
 
 def test_immature_shim_driver_compiles():
     """CPU: the shim's ImmaturePoints class + the driver compile against the ABI header with the plain host compiler."""
-    r = subprocess.run(["make", "-C", HOST, "-B", "test_immature_shim"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert os.path.exists(EXE)
-
-
-def _unpack(f, st):
-    """the driver's 30 floats per point -> the members of immature_ref"""
-    f = f.reshape(-1, 30)
-    return dict(u=f[:, 0].copy(), v=f[:, 1].copy(), my_type=f[:, 2].copy(), idepth_min=f[:, 3].copy(), idepth_max=f[:, 4].copy(), quality=f[:, 5].copy(),
-                color=f[:, 6:14].copy(), weights=f[:, 14:22].copy(), gradH=f[:, 22:26].copy(), energyTH=f[:, 26].copy(), lastTraceStatus=st,
-                lastTraceUV=f[:, 27:29].copy(), lastTracePixelInterval=f[:, 29].copy())
+    shim_driver.rebuild("test_immature_shim")
 
 
 @pytest.mark.gpu
@@ -79,13 +64,8 @@ def test_shim_members_leave_the_set_of_the_abi_path(gpu_ctx, driver, tmp_path):
                 arrays["host%d_dI%d" % (k, l)] = pyrs[k][l]
         for k, F in enumerate(frames):
             arrays["frame%d_left" % k] = F["left"]; arrays["frame%d_right" % k] = F["right"]
-        for k, a in arrays.items():
-            np.ascontiguousarray(a).tofile(os.path.join(tmp_path, k + ".bin"))
-        r = subprocess.run([driver, "run", str(tmp_path)], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr
-
-        def out(name, dt):
-            return np.fromfile(os.path.join(tmp_path, "out_" + name + ".bin"), dtype=dt)
+        r = shim_driver.run("test_immature_shim", tmp_path, arrays, mode="run")
+        out = r.out
 
         assert list(out("made", np.int32)) == made
         kk = out("K4Ki", f32)
@@ -104,12 +84,12 @@ def test_shim_members_leave_the_set_of_the_abi_path(gpu_ctx, driver, tmp_path):
             ctx.check(L.sdso_imm_trace(ctx.h, slots_f[k][0], slots_f[k][1] if k + 1 < nfr else -1, nh, G, abi.fp(kk[:4].copy()), abi.fp(kk[4:].copy()),
                                        float(cal["baseline"]), None))
         for k in range(nh):
-            got = _unpack(out("h%d_f" % k, f32), out("h%d_st" % k, np.uint8))
+            got = shim_driver.unpack_points(out("h%d_f" % k, f32), out("h%d_st" % k, np.uint8))
             want = ctx.imm_get(ids[k])
             assert len(want["u"]) > 100 and R.same(got, want) is None, (k, R.same(got, want))
             assert (want["lastTraceStatus"] == R.GOOD).sum() > 10
         ctx.check(L.sdso_imm_remove(ctx.h, ids[0], len(flags), abi.bp(flags)))
-        got = _unpack(out("removed_f", f32), out("removed_st", np.uint8))
+        got = shim_driver.unpack_points(out("removed_f", f32), out("removed_st", np.uint8))
         want = ctx.imm_get(ids[0])
         assert len(want["u"]) == n0.value - int(flags.sum()) and R.same(got, want) is None
         assert r.stdout.split() == ["points", str(len(want["u"])), "0"]

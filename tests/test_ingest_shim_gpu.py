@@ -1,32 +1,25 @@
 """sdso_shim::Undistort (host/sdso_shim.h) driven by host/test_ingest_shim.cpp on stand-in types: what the program's objects ingest
 equals the C-ABI path from Python and the CPU statement on the same inputs, exactly."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import ingest_cases as Cs
+import shim_driver
 import synth
 import undistort_ref as R
 
-HOST = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "stereo-dso-g2o_amd", "host")
-EXE = os.path.join(HOST, "test_ingest_shim")
 f32 = np.float32
 
 
 @pytest.fixture(scope="module")
 def driver():
-    r = subprocess.run(["make", "-s", "-C", HOST, "test_ingest_shim"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return EXE
+    return shim_driver.build("test_ingest_shim")
 
 
 def test_ingest_shim_driver_compiles():
     """CPU: the shim's Undistort class + the driver compile against the ABI header with the plain host compiler."""
-    r = subprocess.run(["make", "-C", HOST, "-B", "test_ingest_shim"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert os.path.exists(EXE)
+    shim_driver.rebuild("test_ingest_shim")
 
 
 @pytest.mark.gpu
@@ -39,16 +32,9 @@ def test_shim_undistort_ingests_like_the_abi(gpu_ctx, driver, tmp_path, bits, si
     p = Cs.pars(model, size)
     arrays = dict(meta=np.array([wOrg, hOrg, w, h, bits, model, R.CROP, 2, 1], np.int32), pars=np.concatenate([p, np.zeros(8 - len(p))]),
                   out_calib=np.zeros(4, f32), exposure=exposure, G=G, vinv=vinv, raw0=raws[0], raw1=raws[1])
-    for k, arr in arrays.items():
-        np.ascontiguousarray(arr).tofile(os.path.join(tmp_path, k + ".bin"))
-    r = subprocess.run([driver, "run", str(tmp_path)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    levels = int(r.stdout.split()[1])
+    r = shim_driver.run("test_ingest_shim", tmp_path, arrays, mode="run")
+    levels, out = int(r.stdout.split()[1]), r.out
     assert levels == synth.pyramid_levels(w, h)
-
-    def out(name, dt):
-        return np.fromfile(os.path.join(tmp_path, "out_" + name + ".bin"), dtype=dt)
-
     # geometry: Pinhole and RadTan have no transcendental call, the tables equal the statement's bit for bit
     K, rx, ry, _ = R.make_remap(model, p, wOrg, hOrg, w, h, R.CROP)
     Ks = out("K", np.float64).reshape(3, 3)

@@ -3,36 +3,29 @@
 writeBackProjections = false and the overload that reads the device-resident window, once with the full write-back and the overload
 that walks the pointer graph.  FrameHessian::pointHessians of one host is not in the window's point order (two members of a
 three-points-on-one-pixel group are swapped), so the templates only agree if the shim hands the pointHessians order down."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import helpers
+import shim_driver
 import synth
 import tracking_ref_window_cases as TC
 
-HOST = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "stereo-dso-g2o_amd", "host")
-EXE = os.path.join(HOST, "test_tracking_ref_shim")
 ITS = 3
 
 
 @pytest.fixture(scope="module")
 def driver():
-    r = subprocess.run(["make", "-s", "-C", HOST, "test_tracking_ref_shim"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return EXE
+    return shim_driver.build("test_tracking_ref_shim")
 
 
 def test_tracking_ref_shim_driver_compiles():
     """CPU: the new overload, writeBackProjections and the driver compile against the ABI header with the plain host compiler."""
-    r = subprocess.run(["make", "-C", HOST, "-B", "test_tracking_ref_shim"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert os.path.exists(EXE)
+    shim_driver.rebuild("test_tracking_ref_shim")
 
 
-def _write(case, swap, path):
+def _arrays(case, swap):
     arrays = dict(meta=np.array([case["nf"], case["np"], case["nr"], case["w"], case["h"], ITS, case["solverMode"], case["levels"], swap[0], swap[1]], np.int32),
                   calib=np.concatenate([case["calib_value_scaled"], case["calib_value_zero"], [case["baseline"]]]).astype(np.float64))
     for k, dt in (("evalPT", np.float64), ("state", np.float64), ("state_zero", np.float64), ("ab_exposure", np.float32), ("frameEnergyTH", np.float32),
@@ -43,17 +36,12 @@ def _write(case, swap, path):
     for f, pyr in enumerate(list(case["pyrs"]) + [case["pyr_right"]]):
         for l, img in enumerate(pyr):
             arrays["img%d_l%d" % (f, l)] = np.ascontiguousarray(img, np.float32)
-    for k, a in arrays.items():
-        a.tofile(os.path.join(path, k + ".bin"))
+    return arrays
 
 
-def _read(path, mode, levels):
-    pcn = np.fromfile(os.path.join(path, "out_%s_pcn.bin" % mode), np.int32)
-    lv = []
-    for l in range(levels):
-        a = np.fromfile(os.path.join(path, "out_%s_l%d.bin" % (mode, l)), np.float32).reshape(4, -1)
-        lv.append(dict(zip(TC.KEYS, a)))
-    return pcn, lv, np.fromfile(os.path.join(path, "out_%s_info.bin" % mode), np.float64)
+def _read(r, mode, levels):
+    lv = [dict(zip(TC.KEYS, r.out("%s_l%d" % (mode, l), np.float32).reshape(4, -1))) for l in range(levels)]
+    return r.out(mode + "_pcn", np.int32), lv, r.out(mode + "_info", np.float64)
 
 
 @pytest.mark.gpu
@@ -88,12 +76,9 @@ def test_window_overload_equals_the_graph_overload(gpu_ctx, driver, tmp_path):
         for s in range(780, 785):
             ctx.L.sdso_release_pyramid(ctx.h, s)
     # ---- the driver, both overloads
-    _write(case, swap, str(tmp_path))
-    out = {}
+    arrays, out = _arrays(case, swap), {}
     for mode in ("window", "graph"):
-        r = subprocess.run([driver, str(tmp_path), mode], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr
-        out[mode] = _read(str(tmp_path), mode, case["levels"])
+        out[mode] = _read(shim_driver.run("test_tracking_ref_shim", tmp_path, arrays, mode), mode, case["levels"])
     (pcn_w, lv_w, info_w), (pcn_g, lv_g, info_g) = out["window"], out["graph"]
     assert np.array_equal(pcn_w, pcn_g) and pcn_w[0] > 100
     for l in range(case["levels"]):

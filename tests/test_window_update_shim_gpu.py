@@ -3,38 +3,27 @@ the toRemove drops, removeOutliers, update instead of a second upload) leaves th
 (tests/test_ba_window_update_gpu.py::test_update_after_optimize_equals_fresh_upload's edit), bit for bit, and the EnergyFunctional's
 own lists in the order of the Python model."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from sdso_amd import abi
+import shim_driver
 import synth
 import window_edit_ref as ref
 import window_update_helpers as wu
 
-HOST = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "stereo-dso-g2o_amd", "host")
-EXE = os.path.join(HOST, "test_window_update")
 ITS = 6
 
 
 @pytest.fixture(scope="module")
 def driver():
-    r = subprocess.run(["make", "-s", "-C", HOST, "test_window_update"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return EXE
+    return shim_driver.build("test_window_update")
 
 
 def test_window_update_driver_compiles():
     """CPU: WindowedBA::update and its driver compile against the ABI header with the plain host compiler."""
-    r = subprocess.run(["make", "-C", HOST, "-B", "test_window_update"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert os.path.exists(EXE)
-
-
-def _out(d, name, dt):
-    return np.fromfile(os.path.join(str(d), "out_" + name + ".bin"), dtype=dt)
+    shim_driver.rebuild("test_window_update")
 
 
 def _first_frames(big, nfw):
@@ -121,10 +110,7 @@ def test_shim_update_equals_the_abi_path(gpu_ctx, driver, tmp_path):
     # ---- step 3: every point of the oldest frame and a seeded part of the others is marginalised, the frame leaves
     flags = ((w2["host"] == 0) | (np.random.RandomState(8).rand(w2["np"]) < 0.06)).astype(np.uint8)
     arrays["s3_marg"] = np.array([ids_p2[p] for p in np.nonzero(flags)[0]], np.int32)
-    for k, a in arrays.items():
-        np.ascontiguousarray(a).tofile(os.path.join(str(tmp_path), k + ".bin"))
-    r = subprocess.run([driver, str(tmp_path)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
+    r = shim_driver.run("test_window_update", tmp_path, arrays)
     print(r.stdout.strip())
     mp = wu.marginalize_points(ctx, 3, w2, flags)
     mf = wu.marginalize_frame_dev(ctx, 3, 0, w2["nf"] - 1)
@@ -134,24 +120,24 @@ def test_shim_update_equals_the_abi_path(gpu_ctx, driver, tmp_path):
     ids_p3 = [ids_p2[p] for p in maps3[1]]; ids_r3 = [ids_r2[r] for r in maps3[2]]
     s3 = wu.snapshot(ctx, 3, dict(nf=len(maps3[0]), np=len(maps3[1]), nr=len(maps3[2])))
     # ---- step 1: the EnergyFunctional after dropResidual / dropPointsF, the device's maps and the model agree; the window computes the same
-    assert list(_out(tmp_path, "ef_points", np.int32)) == ids_p == list(_out(tmp_path, "order_points", np.int32))
-    assert list(_out(tmp_path, "ef_res", np.int32)) == ids_r == list(_out(tmp_path, "order_res", np.int32))
+    assert list(r.out("ef_points", np.int32)) == ids_p == list(r.out("order_points", np.int32))
+    assert list(r.out("ef_res", np.int32)) == ids_r == list(r.out("order_res", np.int32))
 
     def same(prefix, s):
-        assert np.array_equal(_out(tmp_path, prefix + "idepth", np.float32), s["idepth"])
-        assert np.array_equal(_out(tmp_path, prefix + "rstate", np.uint8), s["res_state"])
-        assert np.array_equal(_out(tmp_path, prefix + "energy", np.float64), s["energy"])
+        assert np.array_equal(r.out(prefix + "idepth", np.float32), s["idepth"])
+        assert np.array_equal(r.out(prefix + "rstate", np.uint8), s["res_state"])
+        assert np.array_equal(r.out(prefix + "energy", np.float64), s["energy"])
         st = np.concatenate([s[k].ravel() for k in ("HA", "bA", "HL", "bL", "Hsc", "bsc")])
-        assert np.array_equal(_out(tmp_path, prefix + "stitched", np.float64), st) and np.abs(st).max() > 0
-    assert np.array_equal(_out(tmp_path, "state", np.float64), s1["state"].ravel())
+        assert np.array_equal(r.out(prefix + "stitched", np.float64), st) and np.abs(st).max() > 0
+    assert np.array_equal(r.out("state", np.float64), s1["state"].ravel())
     same("", s1)
     # ---- step 2: the grown window's order
-    assert list(_out(tmp_path, "s2_ef_points", np.int32)) == ids_p2 and list(_out(tmp_path, "s2_ef_res", np.int32)) == ids_r2
+    assert list(r.out("s2_ef_points", np.int32)) == ids_p2 and list(r.out("s2_ef_res", np.int32)) == ids_r2
     assert len(maps2[0]) == nf + 1 and n_ar > 0 and len(hosts) > 0
     # ---- step 3: the prior after marginalizePointsF (6 frames: 52 x 52) and after marginalizeFrame (44 x 44), the window that is left
-    assert np.array_equal(_out(tmp_path, "s3_HM", np.float64), mp[0].ravel()) and np.array_equal(_out(tmp_path, "s3_bM", np.float64), mp[1])
+    assert np.array_equal(r.out("s3_HM", np.float64), mp[0].ravel()) and np.array_equal(r.out("s3_bM", np.float64), mp[1])
     assert mp[0].shape == (52, 52) and np.abs(mp[0]).max() > 0
-    assert np.array_equal(_out(tmp_path, "s3_HMf", np.float64), mf[0].ravel()) and np.array_equal(_out(tmp_path, "s3_bMf", np.float64), mf[1])
-    assert list(_out(tmp_path, "s3_ef_points", np.int32)) == ids_p3 and list(_out(tmp_path, "s3_ef_res", np.int32)) == ids_r3
+    assert np.array_equal(r.out("s3_HMf", np.float64), mf[0].ravel()) and np.array_equal(r.out("s3_bMf", np.float64), mf[1])
+    assert list(r.out("s3_ef_points", np.int32)) == ids_p3 and list(r.out("s3_ef_res", np.int32)) == ids_r3
     same("s3_", s3)
     ctx.check(ctx.L.sdso_ba_release_window(ctx.h, 3))
