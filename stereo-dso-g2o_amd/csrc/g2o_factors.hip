@@ -342,16 +342,11 @@ extern "C" int sdso_g2o_track_add_edges(sdso_ctx* ctx, int ref_slot, int frame_s
   if (!ctx) return SDSO_ERR_STATE;
   SDSO_HIP(ctx, hipSetDevice(ctx->device));
   SDSO_REQUIRE(ctx, ev && res6, "null argument");
-  auto ir = ctx->refs.find(ref_slot);
-  SDSO_REQUIRE(ctx, ir != ctx->refs.end(), "unknown reference slot");
-  auto ip = ctx->pyr.find(frame_slot);
-  SDSO_REQUIRE(ctx, ip != ctx->pyr.end(), "unknown frame slot");
   const int lvl = ev->lvl;
-  SDSO_REQUIRE(ctx, lvl >= 0 && lvl < ip->second.levels, "level out of range");
-  SDSO_REQUIRE(ctx, ev->w == ip->second.w[lvl] && ev->h == ip->second.h[lvl], "level size does not match the uploaded pyramid");
-  int rc0 = ref_counts(ctx, ir->second);
-  if (rc0) return rc0;
-  const int n = ir->second.n[lvl];
+  TrackLevel TL;
+  int rc = track_level(ctx, ref_slot, frame_slot, lvl, ev->w, ev->h, &TL);
+  if (rc) return rc;
+  const int n = TL.n;
   if (!ctx->g2o) ctx->g2o = new G2oState();
   G2oState& st = *ctx->g2o;
   G2oEdgeSet& S = st.sets[{ref_slot, lvl}];
@@ -379,8 +374,7 @@ extern "C" int sdso_g2o_track_add_edges(sdso_ctx* ctx, int ref_slot, int frame_s
     SDSO_HIP(ctx, hipMemsetAsync(st.d_cnt, 0, sizeof(int) * 2, ctx->stream));
     {
       ProfScope ps(ctx, "k_g2o_track_edges");
-      hipLaunchKernelGGL(k_g2o_track_edges, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, (const float4*)ir->second.pc[lvl],
-                         (const float4*)ip->second.d[lvl], *ev, S.mask, S.xref, st.d_cnt, st.d_flow);
+      hipLaunchKernelGGL(k_g2o_track_edges, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, TL.pc, TL.img, *ev, S.mask, S.xref, st.d_cnt, st.d_flow);
     }
     SDSO_HIP(ctx, hipGetLastError());
     SDSO_HIP(ctx, hipMemcpyAsync(cnt, st.d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
@@ -410,11 +404,10 @@ extern "C" int sdso_g2o_track_linearize(sdso_ctx* ctx, int ref_slot, int frame_s
   if (!ctx) return SDSO_ERR_STATE;
   SDSO_HIP(ctx, hipSetDevice(ctx->device));
   SDSO_REQUIRE(ctx, ev && H && b && chi2, "null argument");
-  auto ip = ctx->pyr.find(frame_slot);
-  SDSO_REQUIRE(ctx, ip != ctx->pyr.end(), "unknown frame slot");
   const int lvl = ev->lvl;
-  SDSO_REQUIRE(ctx, lvl >= 0 && lvl < ip->second.levels, "level out of range");
-  SDSO_REQUIRE(ctx, ev->w == ip->second.w[lvl] && ev->h == ip->second.h[lvl], "level size does not match the uploaded pyramid");
+  const float4* img = nullptr;
+  int rc = track_image_level(ctx, frame_slot, lvl, ev->w, ev->h, &img);
+  if (rc) return rc;
   G2oEdgeSet* S = find_set(ctx, ref_slot, lvl);
   SDSO_REQUIRE(ctx, S != nullptr, "no edge set for (reference, level): call sdso_g2o_track_add_edges first");
   for (int i = 0; i < 64; i++) H[i] = 0;
@@ -427,15 +420,14 @@ extern "C" int sdso_g2o_track_linearize(sdso_ctx* ctx, int ref_slot, int frame_s
   const int blocks = std::min(kMaxLinBlocks, (n + 255) / 256);
   double *d_err = nullptr, *d_J = nullptr;
   if (err || J) {
-    int rc = ensure_scratch(ctx, sizeof(double) * 9 * (size_t)n);
+    rc = ensure_scratch(ctx, sizeof(double) * 9 * (size_t)n);
     if (rc) return rc;
     if (err) d_err = (double*)ctx->scratch;
     if (J) d_J = (double*)ctx->scratch + n;
   }
   {
     ProfScope ps(ctx, "k_g2o_track_lin");
-    hipLaunchKernelGGL(k_g2o_track_lin, dim3(blocks), dim3(256), 0, ctx->stream, n, (const uint8_t*)S->mask, (const float4*)S->xref,
-                       (const float4*)ip->second.d[lvl], *ev, st.d_part, d_err, d_J);
+    hipLaunchKernelGGL(k_g2o_track_lin, dim3(blocks), dim3(256), 0, ctx->stream, n, (const uint8_t*)S->mask, (const float4*)S->xref, img, *ev, st.d_part, d_err, d_J);
   }
   SDSO_HIP(ctx, hipGetLastError());
   std::vector<double> part((size_t)blocks * kSysDoubles);
@@ -461,17 +453,14 @@ extern "C" int sdso_g2o_track_newest_coarse(sdso_ctx* ctx, int ref_slot, int fra
                                             sdso_aff_t* aff_g2l, sdso_track_result_t* out) {
   if (!ctx) return SDSO_ERR_STATE;
   SDSO_REQUIRE(ctx, prm && lastToNew && aff_g2l && out, "null argument");
-  SDSO_REQUIRE(ctx, prm->coarsestLvl >= 0 && prm->coarsestLvl < 5 && prm->coarsestLvl < prm->levels, "coarsestLvl out of range");
-  for (int i = 0; i < 5; i++) { out->lastResiduals[i] = NAN; out->iterations[i] = 0; }
-  for (int i = 0; i < 3; i++) out->lastFlowIndicators[i] = 1000;
-  out->good = 0; out->evaluations = 0; out->point_evals = 0;
+  int rc = track_coarsest_level_ok(ctx, *prm);
+  if (rc) return rc;
+  track_result_reset(*out);
   auto ir = ctx->refs.find(ref_slot);
   SDSO_REQUIRE(ctx, ir != ctx->refs.end(), "unknown reference slot");
   int rc0 = ref_counts(ctx, ir->second);
   if (rc0) return rc0;
-  Se3 pose;
-  std::memcpy(pose.R.data(), lastToNew->R, 72);
-  std::memcpy(pose.t.data(), lastToNew->t, 24);
+  Se3 pose = se3_from_abi(*lastToNew);
   double aff[2] = {aff_g2l->a, aff_g2l->b};
   const sdso_se3_t refToNew_current = *lastToNew;
   const int maxIterations[5] = {2, 2, 2, 2, 2};   // :861
@@ -563,8 +552,7 @@ extern "C" int sdso_g2o_track_newest_coarse(sdso_ctx* ctx, int ref_slot, int fra
     for (int k = 0; k < 3; k++) out->lastFlowIndicators[k] = resOld[2 + k];
     if (out->lastResiduals[lvl] > 1.5 * prm->minResForAbort[lvl]) return SDSO_OK;   // :1032-1033
   }
-  std::memcpy(lastToNew->R, pose.R.data(), 72);
-  std::memcpy(lastToNew->t, pose.t.data(), 24);
+  se3_to_abi(pose, *lastToNew);
   aff_g2l->a = aff[0]; aff_g2l->b = aff[1];
   if ((prm->affineOptModeA != 0 && (fabsf((float)aff_g2l->a) > 1.2)) || (prm->affineOptModeB != 0 && (fabsf((float)aff_g2l->b) > 200))) return SDSO_OK;
   double relAff[2];

@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstring>
 #include <vector>
+#include "../../include/sdso_abi.h"
 
 #define SDSO_HD __host__ __device__
 
@@ -21,6 +22,18 @@ struct Se3 {
   M3 R{{1, 0, 0, 0, 1, 0, 0, 0, 1}};
   V3 t{{0, 0, 0}};
 };
+
+// the C-ABI's pose (row-major R, then t) <-> Se3
+SDSO_HD inline Se3 se3_from_abi(const sdso_se3_t& a) {
+  Se3 T;
+  for (int i = 0; i < 9; ++i) T.R[i] = a.R[i];
+  for (int i = 0; i < 3; ++i) T.t[i] = a.t[i];
+  return T;
+}
+SDSO_HD inline void se3_to_abi(const Se3& T, sdso_se3_t& a) {
+  for (int i = 0; i < 9; ++i) a.R[i] = T.R[i];
+  for (int i = 0; i < 3; ++i) a.t[i] = T.t[i];
+}
 
 SDSO_HD inline M3 mul(const M3& a, const M3& b) {
   M3 c;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <cstdint>
+#include <cmath>
 #include <cstdio>
 #include <map>
 #include <memory>
@@ -57,7 +58,7 @@ struct ProfEntry {
 
 struct BaWindowDev;  // ba_window.hip
 struct BaCtxState;   // ba_window.hip
-struct TrackBatch;   // tracker.hip
+struct TrackBatch;   // tracker_eval.hip
 struct StereoState;  // stereo.hip
 struct SelState;     // selector.hip
 struct G2oState;     // g2o_factors.hip
@@ -147,6 +148,43 @@ inline void ref_free(RefDev& R) {
   if (R.counts_host) hipHostFree(R.counts_host);
   if (R.counts_ev) hipEventDestroy(R.counts_ev);
   R.counts_host = nullptr; R.counts_ev = nullptr; R.counts_pending = false;
+}
+// ---- what the tracker's entry points (tracker_*.hip, g2o_factors.hip) evaluate: one template level on one image level.  Every refusal
+// is SDSO_ERR_ARG, or what ref_counts returns; nothing is launched before them.
+// The image half: level `lvl` of the pyramid in `frame_slot`.  The kernels index the image with the caller's (w, h): they must be the
+// uploaded level's size.
+inline int track_image_level(sdso_ctx* ctx, int frame_slot, int lvl, int w, int h, const float4** img) {
+  auto ip = ctx->pyr.find(frame_slot);
+  SDSO_REQUIRE(ctx, ip != ctx->pyr.end(), "unknown frame slot");
+  SDSO_REQUIRE(ctx, lvl >= 0 && lvl < ip->second.levels, "level not in the uploaded pyramid");
+  SDSO_REQUIRE(ctx, w == ip->second.w[lvl] && h == ip->second.h[lvl], "w / h do not match the uploaded pyramid level");
+  *img = ip->second.d[lvl];
+  return SDSO_OK;
+}
+// Both halves.  The argument checks come before ref_counts (the four copies this replaces did not agree on the order): a call that is
+// wrong in its arguments AND whose template's counts fail to arrive (SDSO_ERR_HIP) is refused with SDSO_ERR_ARG.
+struct TrackLevel { const float4* pc; const float4* img; int n; };
+inline int track_level(sdso_ctx* ctx, int ref_slot, int frame_slot, int lvl, int w, int h, TrackLevel* out) {
+  auto ir = ctx->refs.find(ref_slot);
+  SDSO_REQUIRE(ctx, ir != ctx->refs.end(), "unknown reference slot");
+  int rc = track_image_level(ctx, frame_slot, lvl, w, h, &out->img);
+  if (rc) return rc;
+  rc = ref_counts(ctx, ir->second);
+  if (rc) return rc;
+  out->pc = ir->second.pc[lvl];
+  out->n = ir->second.n[lvl];
+  return SDSO_OK;
+}
+// what a trackNewestCoarse call reports before its first evaluation (CoarseTracker.cpp:846-850)
+__host__ __device__ inline void track_result_reset(sdso_track_result_t& out) {
+  for (int i = 0; i < 5; i++) { out.lastResiduals[i] = NAN; out.iterations[i] = 0; }
+  for (int i = 0; i < 3; i++) out.lastFlowIndicators[i] = 1000;
+  out.evaluations = 0; out.point_evals = 0; out.good = 0;
+}
+// the levels a trackNewestCoarse call may start from (the assert of CoarseTracker.cpp:853)
+inline int track_coarsest_level_ok(sdso_ctx* ctx, const sdso_track_params_t& p) {
+  SDSO_REQUIRE(ctx, p.coarsestLvl >= 0 && p.coarsestLvl < 5 && p.coarsestLvl < p.levels, "coarsestLvl out of range");
+  return SDSO_OK;
 }
 // Bracket the launches of one named kernel with HIP events when profiling is enabled.
 // The A/B and diagnostic switches of the library (SDSO_BA_*, SDSO_TRK_*, SDSO_OPT_*, SDSO_PROF_BRACKET) exist only under SDSO_DEBUG_ENV=1,

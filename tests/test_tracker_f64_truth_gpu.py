@@ -1,4 +1,4 @@
-"""The coarse tracker's evaluation (k_track_eval + k_track_finalize, csrc/tracker.hip) against an f64 truth of calcRes + calcGSSSE, at
+"""The coarse tracker's evaluation (k_track_eval + k_track_finalize, csrc/tracker_eval.hip) against an f64 truth of calcRes + calcGSSSE, at
 the shapes the batched kernel takes in production.
 
 The truth: the oracle's per-point terms (calcRes' buf_warped: idepth, u, v, dx, dy, residual, weight, refColor of every warped
@@ -33,8 +33,8 @@ import synth
 pytestmark = pytest.mark.gpu
 
 W0, H0 = 1232, 368
-TRK_BLOCK, TRK_UNROLL = 256, 4          # tracker.hip:32-33
-LM_BLOCK, LM_UNROLL, LM_MAXG = 512, 4, 8  # tracker.hip:703-709, 1069
+TRK_BLOCK, TRK_UNROLL = 256, 4          # the constants of those names in tracker_eval.hip
+LM_BLOCK, LM_UNROLL, LM_MAXG = 512, 4, 8  # LM_BLOCK_THREADS / LM_UNROLL in tracker_lm_core.h, LM_MAXG in tracker_lm.hip
 SC = np.array([synth.SCALE_XI_ROT] * 3 + [synth.SCALE_XI_TRANS] * 3 + [synth.SCALE_A, synth.SCALE_B], np.float64)
 NFRAMES = 128                           # bench.py TrackerWorkload: 128 frames x 5 levels
 SIZES = (0, 1, 255, 256, 257, 1024, 1025, 4097, 12000, 20000)   # level-0 templates
@@ -46,7 +46,7 @@ NOISE_FACTOR = 4.0                      # device error <= this x the CPU float o
 
 
 def choose_gx(n_cu, nprob, maxn):
-    """tracker.hip:416 choose_gx — workgroups per problem of a batched k_track_eval launch"""
+    """choose_gx (tracker_eval_api.hip) — workgroups per problem of a batched k_track_eval launch"""
     if maxn <= 0:
         return 1
     by_points = (maxn + TRK_BLOCK - 1) // TRK_BLOCK
@@ -55,7 +55,7 @@ def choose_gx(n_cu, nprob, maxn):
 
 
 def lane_trips(n, gx):
-    """trips of track_accumulate's lane loop (tracker.hip:122): TRK_UNROLL points per lane and trip, gx * TRK_BLOCK lanes"""
+    """trips of track_accumulate's lane loop (tracker_eval.hip): TRK_UNROLL points per lane and trip, gx * TRK_BLOCK lanes"""
     return -(-n // (TRK_UNROLL * TRK_BLOCK * gx)) if n > 0 else 0
 
 
@@ -532,7 +532,7 @@ def test_resident_lm_on_multi_trip_template(gpu_ctx, oracle, scene, n_cu, monkey
     gpu_ctx.upload_pyramid(slot_new, big["pyr_new"])
     gpu_ctx.set_ref(slot_ref, pcs)
     slots8 = 8
-    g_eff = min(LM_MAXG, (n_cu * 7 // 8) // slots8, G)       # tracker.hip:1324-1327 for one hypothesis
+    g_eff = min(LM_MAXG, (n_cu * 7 // 8) // slots8, G)       # the choice of G in sdso_track_newest_coarse_batch (tracker_lm_api.hip), for one hypothesis
     g_eff = 1 if g_eff < 2 else g_eff
     assert g_eff == G
     assert -(-n0 // (LM_UNROLL * LM_BLOCK * G)) >= 2 and -(-len(pcs[1]["u"]) // (LM_UNROLL * LM_BLOCK * G)) >= 2

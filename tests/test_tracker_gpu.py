@@ -167,6 +167,94 @@ def test_track_abort_and_error(gpu_ctx, oracle, prob_small):
     assert gpu_ctx.L.sdso_track_newest_coarse(gpu_ctx.h, 1, 2, C.byref(prm), C.byref(T), C.byref(aff), C.byref(out)) == -1
 
 
+def test_tracker_refusals(gpu_ctx, prob_small):
+    """The four entry points that evaluate a template level on an image level — sdso_track_calc_res_gs, sdso_track_newest_coarse,
+    sdso_g2o_track_add_edges, sdso_g2o_track_linearize — refuse an unknown reference slot, an unknown frame slot, a level outside the
+    uploaded pyramid and a w or h one off the uploaded level's with SDSO_ERR_ARG, before anything is launched; the same correct calls
+    before and after the refusals give the same bits (every reduction on these paths runs in a fixed order)."""
+    from test_g2o_factors import _g2o_eval
+    prob, L, h = prob_small, gpu_ctx.L, gpu_ctx.h
+    ERR_ARG = -1
+    _setup(gpu_ctx, prob, 1, 2)
+    prm = helpers.track_params(prob)
+    top = prm.coarsestLvl                                          # the level a trackNewestCoarse call starts on
+    assert top == prob["levels"] - 1 >= 3
+    gpu_ctx.upload_pyramid(5, prob["pyr_new"][:top])               # the same image without its coarsest level
+    T0 = synth.se3_exp(np.array([0.015, -0.008, 0.3, 0.003, -0.005, 0.0015]))
+    lvl = 1
+    n = len(prob["pc"][lvl]["u"])
+
+    def make_ev(**over):
+        ev = abi.TrackEval()
+        L.sdso_track_make_eval(C.byref(prm), lvl, C.byref(abi.SE3.from_Rt(*T0)), C.byref(abi.Aff(0.01, 1.0)), 1.0, C.byref(ev))
+        for k, v in over.items():
+            setattr(ev, k, v)
+        return ev
+
+    def make_evg(**over):
+        ev = _g2o_eval(L, "sdso_", prm, lvl, T0, T0, (0.01, 1.0))
+        for k, v in over.items():
+            setattr(ev, k, v)
+        return ev
+
+    def calc(ref, frame, ev):
+        H = np.zeros(64); b = np.zeros(8); res = np.zeros(6); nw = C.c_int(0); mask = np.zeros(n, np.uint8)
+        rc = L.sdso_track_calc_res_gs(h, ref, frame, C.byref(ev), abi.dp(H), abi.dp(b), abi.dp(res), C.byref(nw), abi.bp(mask))
+        return rc, (H, b, res, nw.value, mask)
+
+    def track(ref, frame, p):
+        T = abi.SE3.from_Rt(np.eye(3), np.zeros(3)); aff = abi.Aff(0, 0); out = abi.TrackResult()
+        rc = L.sdso_track_newest_coarse(h, ref, frame, C.byref(p), C.byref(T), C.byref(aff), C.byref(out))
+        return rc, (bytes(T), bytes(aff), out.good, list(out.iterations), out.evaluations, out.point_evals,
+                    np.array(out.lastResiduals), np.array(out.lastFlowIndicators))
+
+    def add_edges(ref, frame, ev):
+        res = np.zeros(6); ne = C.c_int(0); mask = np.zeros(n, np.uint8); X = np.zeros((n, 3), np.float32)
+        rc = L.sdso_g2o_track_add_edges(h, ref, frame, C.byref(ev), abi.dp(res), C.byref(ne), abi.bp(mask), abi.fp(X))
+        return rc, (res, ne.value, mask, X)
+
+    def linearize(ref, frame, ev):
+        H = np.zeros(64); b = np.zeros(8); chi = np.zeros(2)
+        rc = L.sdso_g2o_track_linearize(h, ref, frame, C.byref(ev), abi.dp(H), abi.dp(b), abi.dp(chi), None, None)
+        return rc, (H, b, chi)
+
+    def good_calls():
+        got = []
+        for rc, val in (calc(1, 2, make_ev()), track(1, 2, prm), add_edges(1, 2, make_evg()), linearize(1, 2, make_evg())):
+            assert rc == 0
+            got.append(val)
+        return got
+
+    def same(a, b):
+        if isinstance(a, (tuple, list)):
+            return len(a) == len(b) and all(same(x, y) for x, y in zip(a, b))
+        return np.array_equal(a, b, equal_nan=True) if isinstance(a, np.ndarray) else a == b
+
+    before = good_calls()
+    assert before[0][3] > 0 and before[2][1] > 0                    # the correct calls evaluate something
+
+    w1, h1 = prob["pyr_new"][lvl].shape[1], prob["pyr_new"][lvl].shape[0]
+    # (reference slot, frame slot, overrides of the evaluation's lvl / w / h)
+    ev_cases = [(999, 2, {}), (1, 998, {}), (1, 2, dict(lvl=prob["levels"])), (1, 2, dict(lvl=-1)), (1, 5, dict(lvl=top)),
+                (1, 2, dict(w=w1 + 1)), (1, 2, dict(w=w1 - 1)), (1, 2, dict(h=h1 + 1)), (1, 2, dict(h=h1 - 1))]
+    for ref, frame, over in ev_cases:
+        assert calc(ref, frame, make_ev(**over))[0] == ERR_ARG, ("calc_res_gs", ref, frame, over)
+        assert add_edges(ref, frame, make_evg(**over))[0] == ERR_ARG, ("add_edges", ref, frame, over)
+        assert linearize(ref, frame, make_evg(**over))[0] == ERR_ARG, ("linearize", ref, frame, over)   # (999: no edge set of that reference)
+
+    def params(level=None, dw=0, dh=0):
+        p = helpers.track_params(prob)
+        if level is not None:
+            p.w[level] += dw; p.h[level] += dh
+        return p
+    trk_cases = [(999, 2, params()), (1, 998, params()), (1, 5, params()),      # (slot 5 lacks the level the call starts on)
+                 (1, 2, params(0, dw=1)), (1, 2, params(2, dw=-1)), (1, 2, params(top, dh=1)), (1, 2, params(1, dh=-1))]
+    for k, (ref, frame, p) in enumerate(trk_cases):
+        assert track(ref, frame, p)[0] == ERR_ARG, ("newest_coarse", k)
+
+    assert same(before, good_calls())
+
+
 def test_make_pyramid_bit_exact(gpu_ctx, oracle, prob_kitti):
     img = np.ascontiguousarray(prob_kitti["pyr_new"][0][..., 0])
     h, w = img.shape
