@@ -440,6 +440,43 @@ int sdso_ba_get_post_state(sdso_ctx* ctx, int win, sdso_ba_post_state_t* out);
  * through this window by sdso_ba_marginalize_points so far (:704).  Any pointer may be NULL. */
 int sdso_ba_get_counts(sdso_ctx* ctx, int win, int* resInA, int* resInL, int* resInM);
 
+/* FullSystem::removeOutliers (FullSystemOptimize.cpp:1063-1084) and FullSystem::flagPointsForRemoval (FullSystem.cpp:965-1056, with
+ * PointHessian::isOOB / isInlierNew, HessianBlocks.h:439-469) decided on the device-resident window after an optimize call: one byte
+ * per point, nothing per point crosses the bus on the way in.  Per point (csrc/ba_flag.h states the rule once):
+ *   n          : its residuals that linearizeAll(true) did not put on toRemove — ph->residuals.size() after FullSystemOptimize.cpp:176-195
+ *   n == 0     -> SDSO_PT_DROP_NO_RESIDUAL (removeOutliers);  idepth < 0 -> SDSO_PT_DROP_NEGATIVE (FullSystem.cpp:997)
+ *   last[k]    : lastResiduals[k].second, k = 0, 1 = state_state of the point's residual into frame nf-1-k, whether that residual is on
+ *                toRemove or not (:167-173 update .second before :184-187 clear .first).  last_gone[2p+k] other than 255 replaces it: the
+ *                history of a residual an earlier keyframe dropped.  Neither: ResState::OOB (FullSystemOptPoint.cpp:204-207)
+ *   isOOB() || frame_marg[host] -> isInlierNew() ? (idepth_hessian > minIdepthH_marg ? SDSO_PT_MARGINALIZE : SDSO_PT_DROP_WEAK)
+ *                                                : SDSO_PT_DROP_NOT_INLIER;  otherwise SDSO_PT_KEEP
+ * The re-linearisation and fixLinearizationF of FullSystem.cpp:1012-1021 stay in sdso_ba_marginalize_points.
+ *   counts      : points per code.  The reference's statistics follow: flag_nores = [1] + [2], flag_oob = [3] + [4] + [5],
+ *                 flag_in = [3] + [4], flag_inin = [3]
+ *   host_counts : the same per host frame, [host * 6 + code]: pointHessiansMarginalized grows by code 3, pointHessiansOut by the
+ *                 codes 1, 2, 4 and 5 — what the next flagFramesForMarginalization reads
+ *   refusals    : decided before any device work.  SDSO_ERR_STATE as for sdso_track_make_ref_from_window: no valid post-state (no
+ *                 optimize call has ended on the window, or sdso_ba_window_update has edited it since), a member of a batch, a window
+ *                 holding a linearised residual.  SDSO_ERR_ARG: an unknown window, a NULL struct, frame_marg or decision, a last_gone
+ *                 byte outside {0, 1, 2, 255}, a negative setting
+ * The call changes nothing in the window: a second call returns the same bytes (integer counting only), every getter returns what it
+ * returned before.  One upload (last_gone, when given), one kernel, one copy back, one synchronisation. */
+#define SDSO_PT_KEEP 0
+#define SDSO_PT_DROP_NO_RESIDUAL 1
+#define SDSO_PT_DROP_NEGATIVE 2
+#define SDSO_PT_MARGINALIZE 3
+#define SDSO_PT_DROP_WEAK 4
+#define SDSO_PT_DROP_NOT_INLIER 5
+typedef struct {
+  const uint8_t* frame_marg;      /* nf  FrameHessian::flaggedForMarginalization (flagFramesForMarginalization ran before optimize) */
+  const uint8_t* last_gone;       /* np*2 or NULL; 0/1/2 = ResState to use, 255 = derive from the window */
+  int   minGoodActiveResForMarg;  /* settings.cpp:82  3  */
+  int   minGoodResForMarg;        /* settings.cpp:83  4  */
+  float minIdepthH_marg;          /* settings.cpp:57  50 */
+} sdso_ba_flag_points_t;
+int sdso_ba_flag_points(sdso_ctx* ctx, int win, const sdso_ba_flag_points_t* prm, uint8_t* decision /* np */,
+                        int* counts /* 6, per code; may be NULL */, int* host_counts /* nf*6; may be NULL */);
+
 /* EnergyFunctional::marginalizePointsF (EnergyFunctional.cpp:663-736) for the points flagged in
  * marg_flag[np] (after flagPointsForRemoval's linearize + fixLinearizationF, FullSystem.cpp:1012-1021):
  * returns the updated HM / bM. */

@@ -57,6 +57,7 @@ struct BaWindowDev {
   sdso_ba_opt_result_t last_result{0, 0, 0, 0};
   float* d_post = nullptr;      // nr x 19: projectedTo, centerProjectedTo of the closing linearisation
   int resInL = 0, resInM = 0;
+  uint8_t* d_flag = nullptr;    // sdso_ba_flag_points: counters, decisions and the staged last_gone (ba_flag.hip), allocated by its first call
   // sdso_ba_window_update: where every frame / point / residual of this window came from (sdso_ba_window_get_order)
   bool has_order = false;
   std::vector<int> ord_frame, ord_point, ord_res;

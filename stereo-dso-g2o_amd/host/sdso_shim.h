@@ -353,6 +353,7 @@ class WindowedBA {
     lin_valid_ = app_valid_ = acc_valid_ = marg_valid_ = false;
     frames_.assign(ef->frames.begin(), ef->frames.end());
     clearPending_();
+    window_serial_++;
   }
 
   // Vec3 FullSystem::linearizeAll(false): returns lastEnergyP
@@ -598,7 +599,7 @@ class WindowedBA {
       auto* ph = efp->data;
       ph->setIdepth(idp[p]); ph->setIdepthZero(idp[p]);
       ph->step = pstep[p];
-      ph->idepth_hessian = idh[p]; ph->maxRelBaseline = mrb[p]; ph->numGoodResiduals = ngood[p];
+      if (writeBackPointStats) { ph->idepth_hessian = idh[p]; ph->maxRelBaseline = mrb[p]; ph->numGoodResiduals = ngood[p]; }
       efp->HdiF = hdi[p]; efp->bdSumF = bds[p];
     }
     // ---- residuals
@@ -651,6 +652,113 @@ class WindowedBA {
   // sdso_ba_get_post_state) and leaves them as they were.  Their only reader on the keyframe path is makeCoarseDepthL0, so switch it off
   // exactly when the tracking reference comes from CoarseTracker::setCoarseTrackingRef(ba, ...) and no other code of the caller reads them.
   bool writeBackProjections = true;
+  // false: optimize() leaves PointHessian::idepth_hessian / maxRelBaseline / numGoodResiduals as they were (their one reader on the keyframe
+  // path is flagPointsForRemoval, which the two members below decide on the device; the window carries all three from keyframe to keyframe
+  // through update()).  idepth, step, HdiF and bdSumF are written back either way: other host code reads them.  The download is the same
+  // (sdso_ba_get_post_state copies the per-point arrays together); what goes is the host loop's three stores per point.  Needs update(),
+  // not upload(), for the next keyframe: an upload would read the stale members.
+  bool writeBackPointStats = true;
+  // ---- FullSystem::removeOutliers (FullSystemOptimize.cpp:1063-1084) and FullSystem::flagPointsForRemoval (FullSystem.cpp:965-1056) with the
+  // reference's effects on the pointer graph, decided on the device (sdso_ba_flag_points): nothing per point is read from the PointHessians
+  // but lastResiduals.  frameHessians: std::vector<FrameHessian*>-like, in window order; of a frame the members flaggedForMarginalization,
+  // pointHessians, pointHessiansOut, pointHessiansMarginalized are touched.
+  //   removeOutliers(frameHessians)        after optimize(), before anything edits the device window: makes the one device call and keeps the
+  //                                        decisions; points without a residual get PS_DROP, go to pointHessiansOut and leave pointHessians by
+  //                                        swap-with-back (:1073-1079).  Its ef->dropPointsF() (:1083) waits for the one that follows
+  //                                        flagPointsForRemoval: the dropped points have left pointHessians, nothing in between meets them,
+  //                                        and one window edit holds one dropPointsF sweep (two sweeps order EFFrame::points differently)
+  //   flagPointsForRemoval(frameHessians)  consumes the kept decisions: stateFlag, pointHessiansOut / pointHessiansMarginalized, the
+  //                                        null-then-compact of :1042-1053, the four counters.  The caller goes on with willDropPoints +
+  //                                        ef->dropPointsF(), update() and marginalizePointsF (which holds :1012-1021)
+  // frame_marg = flaggedForMarginalization; last_gone[2p+k] = lastResiduals[k].second where .first == 0 (a residual that has left: optimize()
+  // cleared it, or an earlier keyframe did), 255 where it is live — then the window holds that residual and knows its state.
+  int setting_minGoodActiveResForMarg = 3, setting_minGoodResForMarg = 4;   // settings.cpp:82-83
+  float setting_minIdepthH_marg = 50;                                       // settings.cpp:57
+  int numPointsDropped = 0;                                                 // removeOutliers' (:1064)
+  int flag_oob = 0, flag_in = 0, flag_inin = 0, flag_nores = 0;             // flagPointsForRemoval's (FullSystem.cpp:981)
+  template <class FrameHessians>
+  void removeOutliers(FrameHessians& frameHessians) {
+    flags_pending_ = false;
+    const int nf = nf_, np = (int)points_.size();
+    if ((int)frameHessians.size() != nf) throw Error("removeOutliers: frameHessians is not the device window's frame list");
+    if (!pending_rm_points_.empty() || !pending_drop_flags_.empty() || !pending_rm_frames_.empty())
+      throw Error("removeOutliers: points or frames left the EnergyFunctional since optimize(): call it right after optimize()");
+    std::vector<uint8_t> frame_marg(nf), last_gone((size_t)np * 2, 255);
+    for (int f = 0; f < nf; f++) frame_marg[f] = frameHessians[f]->flaggedForMarginalization ? 1 : 0;
+    for (int p = 0; p < np; p++) {
+      auto* ph = points_[p]->data;
+      for (int k = 0; k < 2; k++) {
+        auto* first = ph->lastResiduals[k].first;
+        if (!first) { last_gone[(size_t)p * 2 + k] = (uint8_t)ph->lastResiduals[k].second; continue; }
+        auto it = res_index_.find(first);
+        if (it == res_index_.end() || nf - 1 - k < 0 || residuals_[it->second]->target != frames_[nf - 1 - k])
+          throw Error("removeOutliers: a live lastResiduals[k].first does not observe frame nf-1-k of the device window");
+      }
+    }
+    sdso_ba_flag_points_t F;
+    F.frame_marg = frame_marg.data(); F.last_gone = last_gone.data();
+    F.minGoodActiveResForMarg = setting_minGoodActiveResForMarg; F.minGoodResForMarg = setting_minGoodResForMarg; F.minIdepthH_marg = setting_minIdepthH_marg;
+    flag_decisions_.assign((size_t)np, 0);
+    dev_.check(sdso_ba_flag_points(dev_.ctx(), win_, &F, flag_decisions_.data(), nullptr, nullptr), "sdso_ba_flag_points");
+    flags_pending_ = true; flags_serial_ = window_serial_;
+    numPointsDropped = 0;
+    for (auto* fh : frameHessians)
+      for (unsigned int i = 0; i < fh->pointHessians.size(); i++) {
+        auto* ph = fh->pointHessians[i];
+        if (ph == 0) continue;
+        if (decisionOf_(ph->efPoint, "removeOutliers") == SDSO_PT_DROP_NO_RESIDUAL) {      // ph->residuals.size() == 0 (:1073)
+          fh->pointHessiansOut.push_back(ph);
+          setStateFlag_(ph->efPoint, 2);
+          fh->pointHessians[i] = fh->pointHessians.back();
+          fh->pointHessians.pop_back();
+          i--;
+          numPointsDropped++;
+        }
+      }
+  }
+  template <class FrameHessians>
+  void flagPointsForRemoval(FrameHessians& frameHessians) {
+    if (!flags_pending_) throw Error("flagPointsForRemoval: no decisions are pending: removeOutliers() makes them, once per optimize()");
+    if (flags_serial_ != window_serial_) throw Error("flagPointsForRemoval: the device window was edited since removeOutliers() (update() / upload() come after it)");
+    flag_oob = flag_in = flag_inin = flag_nores = 0;
+    for (auto* host : frameHessians) {
+      for (unsigned int i = 0; i < host->pointHessians.size(); i++) {
+        auto* ph = host->pointHessians[i];
+        if (ph == 0) continue;
+        const int d = decisionOf_(ph->efPoint, "flagPointsForRemoval");
+        if (d == SDSO_PT_DROP_NEGATIVE || d == SDSO_PT_DROP_NO_RESIDUAL) {                 // FullSystem.cpp:997-1002
+          host->pointHessiansOut.push_back(ph);
+          setStateFlag_(ph->efPoint, 2);
+          host->pointHessians[i] = 0;
+          flag_nores++;
+        } else if (d != SDSO_PT_KEEP) {                                                    // :1004-1041
+          flag_oob++;
+          if (d == SDSO_PT_MARGINALIZE || d == SDSO_PT_DROP_WEAK) {
+            flag_in++;
+            if (d == SDSO_PT_MARGINALIZE) {
+              flag_inin++;
+              setStateFlag_(ph->efPoint, 1);
+              host->pointHessiansMarginalized.push_back(ph);
+            } else {
+              setStateFlag_(ph->efPoint, 2);
+              host->pointHessiansOut.push_back(ph);
+            }
+          } else {
+            host->pointHessiansOut.push_back(ph);
+            setStateFlag_(ph->efPoint, 2);
+          }
+          host->pointHessians[i] = 0;
+        }
+      }
+      for (int i = 0; i < (int)host->pointHessians.size(); i++)                            // :1044-1051
+        if (host->pointHessians[i] == 0) {
+          host->pointHessians[i] = host->pointHessians.back();
+          host->pointHessians.pop_back();
+          i--;
+        }
+    }
+    flags_pending_ = false;
+  }
   int win() const { return win_; }
   // index of an EFPoint in the device window's point order, -1 when it is not part of it
   int pointIndexOf(const void* efPoint) const { auto it = point_index_.find(efPoint); return it == point_index_.end() ? -1 : it->second; }
@@ -802,6 +910,7 @@ class WindowedBA {
     nf_ = nf2; ef_ = ef;
     HM_.assign((size_t)(8 * nf2 + 4) * (8 * nf2 + 4), 0.0); bM_.assign(8 * nf2 + 4, 0.0);   // (host copies of the prior: sized per window, filled by marginalizePointsF)
     clearPending_();
+    window_serial_++;
     lin_valid_ = app_valid_ = acc_valid_ = marg_valid_ = false;
   }
 
@@ -820,6 +929,17 @@ class WindowedBA {
     }
     point_index_.erase(points_[i]); points_[i] = nullptr;
   }
+  // the kept decision of a point that is still part of the device window's numbering
+  int decisionOf_(const void* efPoint, const char* who) const {
+    auto it = point_index_.find(efPoint);
+    if (!efPoint || it == point_index_.end()) throw Error(std::string(who) + ": a point of pointHessians is not part of the device window");
+    return flag_decisions_[(size_t)it->second];
+  }
+  // EFPointStatus (EnergyFunctionalStructs.h:97): PS_GOOD = 0, PS_MARGINALIZE = 1, PS_DROP = 2
+  template <class EFPointT> static void setStateFlag_(EFPointT* p, int v) { p->stateFlag = static_cast<std::decay_t<decltype(p->stateFlag)>>(v); }
+  std::vector<uint8_t> flag_decisions_;                    // sdso_ba_flag_points of the latest removeOutliers(), device point order
+  bool flags_pending_ = false;
+  int window_serial_ = 0, flags_serial_ = 0;               // upload() / update() count; the count the decisions were made at
   std::vector<int> pending_drop_res_, pending_rm_points_, pending_rm_frames_;
   std::vector<uint8_t> pending_drop_flags_;
   std::vector<const void*> frames_;                        // EFFrame* of the uploaded window, in order

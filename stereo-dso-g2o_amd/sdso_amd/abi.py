@@ -126,6 +126,27 @@ def make_post_state(nf, npts, nr, with_system=True):
     return P, d
 
 
+PT_KEEP, PT_DROP_NO_RESIDUAL, PT_DROP_NEGATIVE, PT_MARGINALIZE, PT_DROP_WEAK, PT_DROP_NOT_INLIER = range(6)   # SDSO_PT_*
+
+
+class BAFlagPoints(C.Structure):
+    """sdso_ba_flag_points_t: removeOutliers + flagPointsForRemoval on the resident window (FullSystem.cpp:965-1056)."""
+    _fields_ = [("frame_marg", c_u8_p), ("last_gone", c_u8_p), ("minGoodActiveResForMarg", C.c_int), ("minGoodResForMarg", C.c_int),
+                ("minIdepthH_marg", C.c_float)]
+
+
+def make_flag_points(frame_marg, last_gone=None, minGoodActiveResForMarg=3, minGoodResForMarg=4, minIdepthH_marg=50.0):
+    """Fill a BAFlagPoints.  frame_marg: nf flags; last_gone: np*2 bytes (0/1/2 or 255) or None.  Returns (struct, keep-alive list)."""
+    F = BAFlagPoints()
+    keep = [np.ascontiguousarray(frame_marg, np.uint8)]
+    F.frame_marg = bp(keep[0])
+    if last_gone is not None:
+        keep.append(np.ascontiguousarray(last_gone, np.uint8).reshape(-1))
+        F.last_gone = bp(keep[1])
+    F.minGoodActiveResForMarg, F.minGoodResForMarg, F.minIdepthH_marg = int(minGoodActiveResForMarg), int(minGoodResForMarg), float(minIdepthH_marg)
+    return F, keep
+
+
 class TracePoints(C.Structure):
     _fields_ = [("n", C.c_int), ("u_stereo", c_float_p), ("v_stereo", c_float_p), ("idepth_min", c_float_p),
                 ("idepth_min_stereo", c_float_p), ("idepth_max_stereo", c_float_p), ("idepth_stereo", c_float_p),
@@ -453,6 +474,7 @@ def load():
     L.sdso_ba_window_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, C.POINTER(BAWindowEdit), c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p]
     L.sdso_ba_window_update.argtypes = [vp, C.c_int, C.POINTER(BAWindowEdit)]
     L.sdso_ba_window_get_order.argtypes = [vp, C.c_int, c_int_p, c_int_p, c_int_p]
+    L.sdso_ba_flag_points.argtypes = [vp, C.c_int, C.POINTER(BAFlagPoints), c_u8_p, c_int_p, c_int_p]
     L.sdso_ba_get_deltas.argtypes = [vp, C.c_int, c_float_p, c_double_p, c_double_p, c_float_p]
     L.sdso_comm_unique_id.argtypes = [vp]
     L.sdso_comm_init.argtypes = [vp, C.c_int, C.c_int, vp]
@@ -530,6 +552,7 @@ EXPORTED_SYMBOLS = [
     "sdso_imm_add_frame", "sdso_imm_trace", "sdso_imm_count", "sdso_imm_get", "sdso_imm_remove_order", "sdso_imm_remove", "sdso_imm_release_host",
     "sdso_imm_put_host", "sdso_imm_activate", "sdso_imm_activate_fetch",
     "sdso_track_make_ref_from_window", "sdso_track_get_ref_points",
+    "sdso_ba_flag_points",
 ]
 
 
@@ -641,6 +664,13 @@ class Context:
         rc, counts = self.imm_activate_raw(host_id, *args, **kw)
         self.check(rc)
         return counts, self.imm_activate_fetch(int(counts[0]), int(counts[4]), len(host_id))
+
+    def flag_points(self, wid, nf, npts, frame_marg, last_gone=None, **settings):
+        """sdso_ba_flag_points -> (decision [np], counts [6], host_counts [nf, 6])."""
+        F, keep = make_flag_points(frame_marg, last_gone, **settings)
+        dec, cnt, hc = np.full(npts, 255, np.uint8), np.full(6, -1, np.int32), np.full((nf, 6), -1, np.int32)
+        self.check(self.L.sdso_ba_flag_points(self.h, wid, C.byref(F), bp(dec), ip(cnt), ip(hc)))
+        return dec, cnt, hc
 
     def upload_pyramid(self, slot, pyr):
         n = len(pyr)
