@@ -1,6 +1,6 @@
 // Device functions of the CoarseDistanceMap kernels that more than one translation unit needs: the projection into the level-1 map and
 // the per-candidate gates of activatePointsMT STEP 2 (FullSystem.cpp:850-887).  k_select_classify (distmap.hip) applies them to arrays
-// the caller uploaded, k_imm_act_classify (immature.hip) to the blobs of the device-resident immature points.
+// the caller uploaded, k_imm_act_classify (imm_activate.hip) to the blobs of the device-resident immature points.
 #pragma once
 #include "sdso_internal.h"
 

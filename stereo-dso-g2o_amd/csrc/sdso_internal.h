@@ -59,12 +59,12 @@ struct ProfEntry {
 struct BaWindowDev;  // ba_window.hip
 struct BaCtxState;   // ba_window.hip
 struct TrackBatch;   // tracker_eval.hip
-struct StereoState;  // stereo.hip
+struct StereoState;  // stereo_batch.hip (a part of stereo.hip)
 struct SelState;     // selector.hip
 struct G2oState;     // g2o_factors.hip
 struct DistMapState; // distmap.hip
 struct IngestState;  // ingest.hip
-struct ImmState;     // immature.hip (compiled with stereo.hip)
+struct ImmState;     // imm_set.hip (a part of stereo.hip)
 struct Comm;         // comm.hip
 struct RefWinState;  // ref_window.hip
 struct BaDev;        // ba_kernels.h
@@ -134,6 +134,13 @@ inline int fail(sdso_ctx* ctx, int code, const std::string& msg) {
     if (!(cond)) return sdso::fail(ctx, SDSO_ERR_ARG, msg); \
   } while (0)
 
+// a step that reports like its caller: anything but SDSO_OK ends the caller with that code (the step has set the ctx's error text)
+#define SDSO_TRY(expr)          \
+  do {                          \
+    const int _rc = (expr);     \
+    if (_rc) return _rc;        \
+  } while (0)
+
 int ensure_scratch(sdso_ctx* ctx, size_t bytes);
 // n[] of a reference whose template was enqueued without a synchronisation: waits for that template's counts only
 inline int ref_counts(sdso_ctx* ctx, RefDev& R) {
@@ -148,6 +155,21 @@ inline void ref_free(RefDev& R) {
   if (R.counts_host) hipHostFree(R.counts_host);
   if (R.counts_ev) hipEventDestroy(R.counts_ev);
   R.counts_host = nullptr; R.counts_ev = nullptr; R.counts_pending = false;
+}
+// ---- a frame slot as the entry points see it.  Every refusal is SDSO_ERR_ARG; nothing is launched or waited for before them.
+// Level 0 and the sizes of the pyramid in `frame_slot`; `unknown` is the caller's refusal text where it names the slot.
+inline int frame_pyramid(sdso_ctx* ctx, int frame_slot, PyramidDev** out, const char* unknown = "unknown frame slot") {
+  auto ip = ctx->pyr.find(frame_slot);
+  SDSO_REQUIRE(ctx, ip != ctx->pyr.end(), unknown);
+  *out = &ip->second;
+  return SDSO_OK;
+}
+// the same for a slot whose level 0 must be w x h (the caller's w / h, or another frame's size), refused with the caller's text
+inline int frame_pyramid_sized(sdso_ctx* ctx, int frame_slot, int w, int h, const char* differs, PyramidDev** out, const char* unknown = "unknown frame slot") {
+  const int rc = frame_pyramid(ctx, frame_slot, out, unknown);
+  if (rc) return rc;
+  SDSO_REQUIRE(ctx, (*out)->w[0] == w && (*out)->h[0] == h, differs);
+  return SDSO_OK;
 }
 // ---- what the tracker's entry points (tracker_*.hip, g2o_factors.hip) evaluate: one template level on one image level.  Every refusal
 // is SDSO_ERR_ARG, or what ref_counts returns; nothing is launched before them.
@@ -270,7 +292,7 @@ int pyramid_finish_levels(sdso_ctx* ctx, PyramidDev& P);                        
 // where the L->R->L chain of sdso_stereo_match_batch leaves its results (device pointers into the ctx's match batches)
 struct MatchChainOut { const float *idepth_stereo, *idepth_min, *idepth_max, *fwd_uv, *back_uv; const uint8_t *status_fwd, *status_back; };
 int stereo_match_chain_dev(sdso_ctx* ctx, int slot_a, int slot_b, const float K[4], float baseline, int mode_right_first, int n,
-                           const float* const in[6], const uint8_t* skip_fwd, MatchChainOut* out);                            // stereo.hip
+                           const float* const in[6], const uint8_t* skip_fwd, MatchChainOut* out);                            // stereo_match.hip
 int track_make_ref_dev(sdso_ctx* ctx, int ref_slot, int frame_slot, int n, const int* d_u, const int* d_v, const float* d_idp, const float* d_wgt,
                        int* pc_n_out, bool sync_end);                                                                         // coarse_depth.hip
 // what a BA window offers a reader of its post-state (ba_api.hip): SDSO_ERR_ARG for an unknown window, SDSO_ERR_STATE unless an optimize

@@ -5,7 +5,7 @@
 //   trace_gn_terms / trace_gn_advance   one pattern pixel / one iteration of the DSO-native sub-pixel Gauss-Newton (:707-769)
 //   trace_interval     the new idepth interval around the refined position                          (:424-436 / :798-810)
 // with TraceDev (a batch of points), the constants, the status enum and the writer of a fresh ImmaturePoint's members.  The reference
-// writes all of this twice; k_trace_stereo_blk (stereo.hip: a workgroup per 16 points) and trace_on_point (one wave per point) differ
+// writes all of this twice; k_trace_stereo_blk (stereo_trace.hip: a workgroup per 16 points) and trace_on_point (one wave per point) differ
 // only in their lane layout, in where pr / Kt come from (a camera pair / a hostToFrame geometry) and in the pattern offsets and affine
 // pair of a sample (TracePatStereo / TracePatOn).  No helper has a lane test or a store, and none knows its caller.  Every expression
 // keeps the reference's association (the library is compiled without FP contraction): the results are bit-identical to the CPU path.
@@ -32,6 +32,12 @@ struct TraceDev {
   uint8_t* status;
   const uint8_t* skip;   // optional: 1 = leave the point alone (status 255)
 };
+
+// The constructor (ImmaturePoint.cpp:33-62) and the searches dereference the 3x3 neighbourhood of every pattern pixel unchecked: the
+// entry points refuse a point elsewhere, the chains give it no trace.
+__host__ __device__ inline bool trace_pattern_readable(float u, float v, int w, int h) { return u >= 2 && v >= 2 && u < w - 3 && v < h - 3; }
+// where a point that takes no trace is parked, both coordinates: a harmless pixel, so that the constructor kernel reads valid memory
+constexpr float kTraceParkedPixel = 8.f;
 
 // the members of a fresh ImmaturePoint (ImmaturePoint.cpp:34-38) at (u, v), with the interval its maker gives it
 __device__ __forceinline__ void fresh_point(const TraceDev& T, int j, float u, float v, float idepth_min, float imin_stereo, float imax_stereo) {

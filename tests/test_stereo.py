@@ -320,3 +320,108 @@ def test_gpu_activation_bit_exact(gpu_ctx, oracle):
     assert np.array_equal(so, sg) and np.array_equal(ro, rg)
     assert np.array_equal(io, ig, equal_nan=True)                          # same float operations in the same order: bit-exact
     assert set(np.unique(so)) == {-1, 0, 1}
+
+
+@pytest.mark.gpu
+def test_stereo_refusals(gpu_ctx, pair):
+    """What the stereo entry points refuse before they launch anything: an unknown frame slot (at every slot argument), two frames of
+    different size, a point whose pattern is not readable (u < 2 or u >= w - 3; u = 2 and u = w - 3.5 are the first and last accepted),
+    a point_geom out of range: SDSO_ERR_ARG each.  enqueue / fetch without a prepared batch: SDSO_ERR_STATE.  One correct trace and one
+    correct match before and after the refusals give the same arrays, bit for bit."""
+    ERR_ARG, ERR_STATE = -1, -4
+    pr, L, h = pair, gpu_ctx.L, gpu_ctx.h
+    left = np.ascontiguousarray(pr["pyr_l"][0]); right = np.ascontiguousarray(pr["pyr_r"][0])
+    SL, SR, SMALL, NONE = 80, 81, 82, 999
+    gpu_ctx.upload_pyramid(SL, [left]); gpu_ctx.upload_pyramid(SR, [right])
+    gpu_ctx.upload_pyramid(SMALL, [np.ascontiguousarray(right[:240, :320])])
+    w, n = pr["w"], 64
+    u, v = pr["u"][:n].copy(), pr["v"][:n].copy()
+    K = np.array(pr["K"], np.float32); bl = float(pr["calib"]["baseline"])
+    col, wgt, gH, eth = np.zeros((n, 8), np.float32), np.zeros((n, 8), np.float32), np.zeros((n, 4), np.float32), np.zeros(n, np.float32)
+
+    def init(slot, uu, vv):
+        return L.sdso_immature_init_batch(h, slot, len(uu), abi.fp(uu), abi.fp(vv), abi.fp(col), abi.fp(wgt), abi.fp(gH), abi.fp(eth))
+
+    def match(sa, sb, uu, vv):
+        m = len(uu)
+        M = abi.StereoMatch()
+        out = dict(status_fwd=np.zeros(m, np.uint8), status_back=np.zeros(m, np.uint8), idepth_stereo=np.zeros(m, np.float32),
+                   idepth_min_out=np.zeros(m, np.float32), idepth_max_out=np.zeros(m, np.float32), fwd_uv=np.zeros((m, 2), np.float32),
+                   back_uv=np.zeros((m, 2), np.float32))
+        M.n = m; M.u = abi.fp(uu); M.v = abi.fp(vv)
+        for k, a in out.items():
+            setattr(M, k, abi.bp(a) if a.dtype == np.uint8 else abi.fp(a))
+        return L.sdso_stereo_match_batch(h, sa, sb, abi.fp(K), bl, 1, C.byref(M)), out
+
+    def correct():
+        P, d = abi.make_trace_points(n, u, v, col, wgt, gH, eth)
+        st = np.zeros(n, np.uint8)
+        gpu_ctx.check(L.sdso_trace_stereo_batch(h, SR, abi.fp(K), bl, 1, C.byref(P), abi.bp(st)))
+        rc, out = match(SL, SR, u, v)
+        gpu_ctx.check(rc)
+        return [st] + [d[k] for k in FIELDS] + [out[k] for k in sorted(out)]
+
+    gpu_ctx.check(init(SL, u, v))
+    before = correct()
+    assert (before[0] == 0).any()
+
+    # ---- unknown frame slot, at every entry point and every slot argument
+    P, d = abi.make_trace_points(n, u, v, col, wgt, gH, eth)
+    st = np.zeros(n, np.uint8)
+    assert init(NONE, u, v) == ERR_ARG
+    assert L.sdso_trace_stereo_prepare(h, NONE, abi.fp(K), bl, 1, C.byref(P)) == ERR_ARG
+    G = abi.TraceGeom(); G.KRKi[:] = [1, 0, 0, 0, 1, 0, 0, 0, 1]; G.Kt[:] = [1, 0, 0]; G.aff[:] = [1, 0]
+    pg = np.zeros(n, np.int32)
+    assert L.sdso_trace_on_batch(h, NONE, 1, C.byref(G), abi.ip(pg), C.byref(P), abi.bp(st)) == ERR_ARG
+    assert match(NONE, SR, u, v)[0] == ERR_ARG and match(SL, NONE, u, v)[0] == ERR_ARG
+    nf = 3
+    one = dict(pair_R=np.tile(np.eye(3, dtype=np.float32).ravel(), nf * nf), pair_t=np.zeros(nf * nf * 3, np.float32),
+               pair_aff=np.tile(np.array([1, 0], np.float32), nf * nf), u=u[:1], v=v[:1], idepth_min=np.full(1, 0.1, np.float32),
+               idepth_max=np.full(1, 0.2, np.float32), color=col[:1].copy(), weights=wgt[:1].copy(), energyTH=eth[:1].copy())
+    a_st, a_id, a_rs = np.zeros(1, np.int8), np.zeros(1, np.float32), np.zeros((1, nf), np.uint8)
+    host0 = np.zeros(1, np.int32)
+    for slots in ([NONE, SL, SR], [SL, NONE, SR], [SL, SR, NONE], [SL, SR, SMALL]):     # the last: a pyramid that is not w x h
+        A = abi.Activate()
+        A.nf, A.w, A.h, A.n, A.minObs = nf, pr["w"], pr["h"], 1, 1
+        A.K[:] = [float(x) for x in pr["K"]]
+        for k, a in one.items():
+            setattr(A, k, abi.fp(a))
+        fs = np.array(slots, np.int32); A.host = abi.ip(host0); A.frame_slot = abi.ip(fs)
+        assert L.sdso_activate_points_batch(h, C.byref(A), a_st.ctypes.data_as(C.POINTER(C.c_int8)), abi.fp(a_id), abi.bp(a_rs)) == ERR_ARG, slots
+    sel_map = np.zeros((pr["h"], pr["w"]), np.float32)
+    assert L.sdso_imm_add_frame(h, 7001, NONE, abi.fp(sel_map), None) == ERR_ARG
+    Ki = np.eye(3, dtype=np.float32).ravel().copy()
+    no_geom = (abi.ImmGeom * 1)()
+    imm_trace = lambda sl, sr: L.sdso_imm_trace(h, sl, sr, 0, no_geom, abi.fp(K), abi.fp(Ki), bl, None)
+    assert imm_trace(NONE, SR) == ERR_ARG and imm_trace(NONE, -1) == ERR_ARG and imm_trace(SL, NONE) == ERR_ARG
+    gpu_ctx.check(imm_trace(SL, SR)); gpu_ctx.check(imm_trace(SL, -1))                 # (no host named: nothing to do)
+
+    # ---- two frames of different size
+    assert match(SL, SMALL, u, v)[0] == ERR_ARG and match(SMALL, SL, u, v)[0] == ERR_ARG
+    assert imm_trace(SL, SMALL) == ERR_ARG
+
+    # ---- the readable pattern: u in [2, w - 3)
+    for bad in (1.5, float(w - 3)):
+        ub = u.copy(); ub[n // 2] = bad
+        assert init(SL, ub, v) == ERR_ARG and match(SL, SR, ub, v)[0] == ERR_ARG, bad
+    for ok in (2.0, w - 3.5):
+        uo = u.copy(); uo[n // 2] = ok
+        assert init(SL, uo, v) == 0 and match(SL, SR, uo, v)[0] == 0, ok
+    gpu_ctx.check(init(SL, u, v))                                                       # col, wgt, gH, eth of the 64 points again
+
+    # ---- point_geom out of range
+    for bad in (-1, 1):
+        pg[n - 1] = bad
+        assert L.sdso_trace_on_batch(h, SR, 1, C.byref(G), abi.ip(pg), C.byref(P), abi.bp(st)) == ERR_ARG
+
+    # ---- no prepared batch on a ctx of its own
+    fresh = abi.Context(0)
+    try:
+        assert fresh.L.sdso_trace_stereo_enqueue(fresh.h) == ERR_STATE
+        assert fresh.L.sdso_trace_stereo_fetch(fresh.h, C.byref(P), abi.bp(st)) == ERR_STATE
+    finally:
+        fresh.close()
+
+    after = correct()
+    for a, b in zip(before, after):
+        assert np.array_equal(a, b, equal_nan=True)
