@@ -39,6 +39,17 @@ template <class T> __device__ __forceinline__ T uld(const T* p) { return *(uptr_
 // every vector-memory access of the wave has completed (s_waitcnt vmcnt(0), nothing else): ONE wait behind a batch of independent loads
 // instead of a counted one in front of each result's first use.  The scheduling barrier keeps the first uses behind it.
 __device__ __forceinline__ void vm_wait_all() { __builtin_amdgcn_s_waitcnt(0x0f70); __builtin_amdgcn_sched_barrier(0); }
+// the LDS writes of every lane of the wave are visible to every lane behind this (wave-private stages: no workgroup barrier)
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// value of lane (quad base + k) of the caller's quad (v_mov_b32 with DPP quad_perm broadcast)
+template <int K>
+__device__ __forceinline__ float quad_bcast(float v) {
+  return __uint_as_float(__builtin_amdgcn_mov_dpp(__float_as_uint(v), K * 0x55, 0xf, 0xf, true));
+}
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -46,8 +57,6 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 constexpr int BA_BLOCK = 256;
 constexpr int BA_CHUNK = 256;      // residuals per accumulate workgroup
 constexpr int BA_SC_PTS = 32;      // points per SC wave item (<= 64)
-constexpr int J_RESF = 0, J_XI0 = 8, J_XI1 = 14, J_C0 = 20, J_C1 = 24, J_DD = 28, J_IDX0 = 30, J_IDX1 = 38, J_AB0 = 46, J_AB1 = 54,
-              J_IDX2 = 62, J_ABIDX = 66, J_AB2 = 70;
 // p_out record (16 floats per point)
 // [0..7] is what a plain Gauss-Newton iteration writes (one 32-byte piece per point), [8..13] the sums of the linearised / marginalised
 // residuals (zero unless such residuals exist), [14..15] the back-substitution's own
@@ -123,7 +132,7 @@ struct BaDev {
   uint8_t* r_state; uint8_t* r_newState; uint8_t* r_lin; uint8_t* r_act; uint8_t* r_jsel;
   const uint8_t* r_isnew;   // PointFrameResidual::isNew
   float* r_energy; float* r_newEnergy; float* r_newEnergyWO;
-  float* J[2];              // 19 float4 groups x nrp each (layout: ba_kernels.hip); EFResidual::J = J[jsel], PointFrameResidual::J = J[1-jsel]
+  float* J[2];              // 19 float4 groups x nrp each (layout: ba_jac.h); EFResidual::J = J[jsel], PointFrameResidual::J = J[1-jsel]
   float* r_toZero;          // 8 x nrp SoA
   // Per-residual records of the Schur part, in the WINDOW's residual order (grouped by point, EFPoint::residualsAll order inside a point:
   // record o belongs to point res_point[o]; point p owns records [p_rbeg[p], p_rbeg[p + 1]), nibble k of p_order[p] names the target of its

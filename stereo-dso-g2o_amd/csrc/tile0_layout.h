@@ -1,6 +1,6 @@
 // The tiled copy of a level-0 image that the BA linearisation samples (PyramidDev::tiled0): 12-byte pixels {I, dx, dy} in tiles of
 // 5 x 2 pixels, one 128-byte line per tile (two rows of 60 bytes, the last 8 bytes unused and zero).  One definition for the producer
-// (ctx.hip), the consumers (ba_kernels.hip), the upload's size check (ba_window.hip) and tests/test_tile_layout_cpu.py.
+// (ctx.hip), the consumers (ba_jac.h, ba_lin.hip), the upload's size check (ba_window.hip) and tests/test_tile_layout_cpu.py.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
@@ -8,7 +8,7 @@
 namespace sdso {
 
 constexpr int TILE0_W = 5, TILE0_H = 2, TILE0_PIXEL_BYTES = 12, TILE0_ROW_BYTES = TILE0_W * TILE0_PIXEL_BYTES, TILE0_LINE_BYTES = 128;
-// A window's images are read through a buffer descriptor of 2 GiB with 32-bit offsets (ba_kernels.hip: TAP_RANGE), so its upload refuses
+// A window's images are read through a buffer descriptor of 2 GiB with 32-bit offsets (ba_lin.hip: TAP_RANGE), so its upload refuses
 // a tiled copy of TILE0_MAX_BYTES or more.  A pyramid level is at least 8 rows (four tile rows), which bounds the width of an accepted image:
 constexpr size_t TILE0_MAX_BYTES = (size_t)1 << 31;
 constexpr int TILE0_MAX_W = TILE0_W * (int)(TILE0_MAX_BYTES / TILE0_LINE_BYTES / 4 - 1);   // 20 971 515

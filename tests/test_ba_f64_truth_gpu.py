@@ -199,7 +199,7 @@ def test_device_noise_is_the_cpu_float_noise(gpu_ctx, oracle):
 
     Rounds 1-5 summed in fp32 MFMA chains and the two float paths scattered around the truth alike (profiles/r05_truth_updates.txt: first
     update 1.13e-5 / 1.31e-5 median, but 6.8e-5 / 3.1e-5 maximum: the round-5 verdict's asymmetry).  From round 6 the cross-residual and
-    cross-point sums run in f64 on the matrix cores (csrc/ba_kernels.hip: top_emit, k_ba_sc_host) and what is left is the solve's own floor.  Measured on
+    cross-point sums run in f64 on the matrix cores (csrc/ba_top.hip: top_emit, csrc/ba_sc.hip: k_ba_sc_host) and what is left is the solve's own floor.  Measured on
     MI355X over the 24 windows (profiles/r06_truth_updates.txt, profiles/r06_acc_modes.txt): first update median 1.39e-6 against the CPU's
     1.31e-5, maximum 2.39e-5 against 3.09e-5; device farther than the CPU + 5e-6 in 3 of 141 updates, the CPU farther than the device + 5e-6
     in 30; final states median 7.5e-6 against 2.4e-5, device worse on 3 windows of 24; the two maxima (1.17e-4 / 1.12e-4) are one window

@@ -381,8 +381,8 @@ def test_pose_updates_of_every_gn_iteration_c3(gpu_ctx, oracle, win_c3):
     update of every frame is compared in the units the pose moves in (x * SCALE).  FIXED bars:
       * against the reference arithmetic with its sums carried in f64 (orc_set_acc64: the float summation ORDER of the CPU path out of the
         reference value): translation and rotation entries |dx| <= 1e-5 on EVERY iteration, the first included (measured on MI355X,
-        round 6: 4.1e-6, 1.4e-6, 2.3e-7, 4.3e-7).  The device carries its cross-residual / cross-point sums in f64 on the matrix cores (ba_kernels.hip:
-        top_emit, k_ba_sc_host), so this is the comparison in which only the reference's per-residual arithmetic is left;
+        round 6: 4.1e-6, 1.4e-6, 2.3e-7, 4.3e-7).  The device carries its cross-residual / cross-point sums in f64 on the matrix cores (ba_top.hip /
+        ba_sc.hip: top_emit, k_ba_sc_host), so this is the comparison in which only the reference's per-residual arithmetic is left;
       * against the reference's float path as it is (4-byte accumulators, sequential): <= 1e-5 from the second iteration on and <= 2e-5 on
         the first (measured 9.4e-6, 1.1e-6, 2.4e-7, 5.9e-7; round 5 with fp32 chains: 1.39e-5 on the first) — what is left there is the CPU
         float path's OWN distance from the order-independent sums (5.3e-6 on this window, median 1.3e-5 over 24 windows against the

@@ -78,7 +78,7 @@ def _device_loop(ctx, W, win, its, wid=3):
 
 
 def _compare_loops(win, dev, orc, pose_bar=2e-5, truth=None):
-    """truth: the same loop with the oracle's accumulator sums in f64.  The device carries its sums in f64 too (ba_kernels.hip: top_emit, k_ba_sc_host), so
+    """truth: the same loop with the oracle's accumulator sums in f64.  The device carries its sums in f64 too (ba_top.hip: top_emit, ba_sc.hip: k_ba_sc_host), so
     against the truth the fixed bar holds by itself; against the float oracle the distance may be the float oracle's own distance from the
     truth (the momentum modes feed half of every step into the next one, and the float path's summation noise with it)."""
     sg, ig, rg, og = dev[:4]
