@@ -867,6 +867,53 @@ typedef struct { int host_id; float KRKi[9]; float Kt[3]; float aff[2]; float KR
 int sdso_imm_trace(sdso_ctx* ctx, int frame_slot, int right_slot, int ngeom, const sdso_imm_geom_t* geom, const float K[4],
                    const float Ki[9], float baseline, int* counts);
 
+/* FullSystem::stereoMatch, the loop at FullSystem.cpp:581-613 (the stereo-only mode, main_dso_pangolin.cpp:481-491), on the points of
+ * group host_id after sdso_imm_add_frame (makeNewTraces, :577).  For every point i of the group, in group order:
+ *   fwd  = the point itself — its stored u, v, colour, weights, gradH, energyTH, quality and last trace, not re-sampled from frame_slot —
+ *          with u_stereo = u, v_stereo = v, idepth_min = idepth_min_stereo = 0, idepth_max_stereo = NaN whatever interval the set stores,
+ *          traced by traceStereo(right_slot, K, 1)                                                                          (:582-587)
+ *   back = if fwd is IPS_GOOD: ImmaturePoint(fwd.lastTraceUV, right_slot) with the interval 0 / NaN, traceStereo(frame_slot, K, 0)  (:589-596)
+ *   accepted = back is IPS_GOOD and |u - back.lastTraceUV[0]| < 1 and depth > 0 and depth < max_depth, depth = 1.0f / fwd.idepth_stereo
+ *          (:598-601; the reference passes 70)
+ * A GOOD fwd.lastTraceUV outside [2, w-3) x [2, h-3), where the reference's constructor would read outside the image, takes no back trace,
+ * is counted as unreadable and is not accepted (the rule of sdso_imm_trace).  Both traces use the ctx's refinement mode
+ * (sdso_trace_set_gn_mode).  The group is NOT changed (the reference deletes the frame right after the loop): a second call returns the
+ * same bytes, and sdso_imm_get what it returned before.
+ *   build_map : non-zero = the dense image of :606-608 is built on the device: cleared, then every accepted point writes its three floats
+ *               at pixel ((int)v, (int)u).  A group of sdso_imm_add_frame holds at most one point per pixel.  For other groups
+ *               (sdso_imm_put_host) the per-point arrays are the result: a pixel claimed twice holds one of the contenders, and a point
+ *               whose pixel is not in the image writes none.  The map stays on the device until the next call that builds one;
+ *               sdso_imm_stereo_map_dev returns it (SDSO_ERR_STATE before the first such call).
+ *   out       : caller-owned arrays for the group's n points (sdso_imm_count), every member may be NULL
+ *   counts    : SDSO_IMM_MATCH_NCOUNTS ints or NULL: [0] points walked, [1] forward IPS_GOOD, [2] back traces run, [3] back IPS_GOOD,
+ *               [4] accepted (the reference's `counter`), [5] back GOOD but |du| >= 1, [6] back GOOD, |du| < 1, depth outside
+ *               (0, max_depth), [7] unreadable; [3] = [4] + [5] + [6]
+ * out == NULL and counts == NULL: the call only enqueues.  Otherwise one copy back and one synchronisation (13 bytes per point, 15 with a
+ * status array), and a second copy for out->map.  The per-point results have buffers of their own: sdso_imm_stereo_match_fetch returns
+ * them until the next sdso_imm_stereo_match, whatever other sdso_imm_* calls run in between (SDSO_ERR_STATE before the first call;
+ * SDSO_ERR_ARG for out->map when the latest call built no map).
+ * Refused with SDSO_ERR_ARG before any device work, the set, the kept results and the kept map left as they were: an unknown host_id, an
+ * unknown frame_slot or right_slot, a pyramid of another size than the group's w x h, K == NULL, a max_depth that is not > 0 (NaN
+ * included), out->map without build_map.  An empty group is not an error: the counts are 0 and the map, if asked for, is all zeros. */
+#define SDSO_IMM_MATCH_NCOUNTS 8
+typedef struct {
+  uint8_t* accepted;     /* n      1 where :601 holds                                                        */
+  float*   idepth;       /* n*3    idepth_stereo, idepth_min_stereo, idepth_max_stereo of the forward trace
+                                   (what :606-608 write); 0 0 0 where not accepted                           */
+  uint8_t* status_fwd;   /* n      ImmaturePointStatus of :587                                               */
+  uint8_t* status_back;  /* n      of :596; 255 where the back trace did not run                             */
+  float*   map;          /* w*h*3  row-major, pixel ((int)v, (int)u), 3 floats as :606-608; 0 elsewhere      */
+} sdso_imm_match_out_t;  /* every member may be NULL */
+int sdso_imm_stereo_match(sdso_ctx* ctx, int host_id, int frame_slot, int right_slot, const float K[4], float baseline,
+                          float max_depth /* the reference: 70 */, int build_map, sdso_imm_match_out_t* out /* NULL: enqueue only */,
+                          int* counts /* NCOUNTS or NULL */);
+/* the kept results of the latest sdso_imm_stereo_match again (what :598-608 decided and wrote), e.g. after an enqueue-only call; out->map
+ * only if that call built the map */
+int sdso_imm_stereo_match_fetch(sdso_ctx* ctx, sdso_imm_match_out_t* out, int* counts);
+/* the idepth image of :606-608 where the latest map-building call left it: a device pointer, valid until the next such call or
+ * sdso_ctx_destroy */
+int sdso_imm_stereo_map_dev(sdso_ctx* ctx, void** map_dev /* float*, w*h*3 */, int* w, int* h);
+
 /* host->immaturePoints.size() (0 for a host the set does not hold), and one host's points copied back in the traceOn convention of
  * sdso_trace_points_t: u_stereo / v_stereo = u / v, idepth_min_stereo / idepth_max_stereo = idepth_min / idepth_max; out->idepth_min and
  * out->idepth_stereo are not written; null members are skipped; out->n is set.  This is the per-keyframe download that feeds

@@ -1,5 +1,6 @@
 // The device-resident immature points of a ctx (sdso_imm_*): the set itself.  FullSystem::makeNewTraces (FullSystem.cpp:1600-1629) and
-// STEP 5 of activatePointsMT (:948-957) on arrays that never leave the device; imm_trace.hip and imm_activate.hip work on the set in place.
+// STEP 5 of activatePointsMT (:948-957) on arrays that never leave the device; imm_trace.hip and imm_activate.hip work on the set in place,
+// imm_match.hip reads it.
 //
 // Layout: one blob of kImmFloats * cap floats and cap status bytes per host, its members as imm_layout.h states them.  Every host has a
 // second blob of the same size: a removal gathers into it and the two swap (imm_swap_blobs).
@@ -15,8 +16,23 @@ struct ImmHost {
   int* h_n = nullptr;               // pinned
   hipEvent_t ev = nullptr;
 };
+// the results of the latest sdso_imm_stereo_match (imm_match.hip), in buffers no other call writes: counts | idepth | accepted | status_fwd |
+// status_back on the device with a pinned mirror, and the dense map of the latest call that built one
+struct ImmMatchKept {
+  char* d = nullptr;
+  char* h = nullptr;                // pinned; its first `have` bytes hold the device's
+  int cap = 0;                      // points both buffers hold
+  bool valid = false;
+  int n = 0;
+  size_t have = 0;
+  float* d_map = nullptr;
+  size_t map_cap = 0;               // floats
+  bool map_valid = false, map_latest = false;   // a map is kept; the latest call built it
+  int map_w = 0, map_h = 0;
+};
 struct ImmState {
   std::map<int, ImmHost> hosts;
+  ImmMatchKept match;
   TraceBatch fwd, back;             // the stereo chain of the non-key trace, over the concatenated points of the named hosts
   int* d_counts = nullptr;          // SDSO_IMM_NCOUNTS
   int* h_counts = nullptr;          // pinned
@@ -54,6 +70,9 @@ void release_immature(sdso_ctx* ctx) {
   if (S->d_counts) hipFree(S->d_counts);
   if (S->h_counts) hipHostFree(S->h_counts);
   if (S->h_act) hipHostFree(S->h_act);
+  if (S->match.d) hipFree(S->match.d);
+  if (S->match.h) hipHostFree(S->match.h);
+  if (S->match.d_map) hipFree(S->match.d_map);
   stage_free(S->stage);
   delete S;
   ctx->imm = nullptr;

@@ -57,21 +57,27 @@ __global__ __launch_bounds__(256) void k_imm_stereo_prepare(ImmTraceArgs A, int 
   pmin[j] = pm; pmax[j] = pM;
   fresh_point(F, j, fu, fv, pm, pm, pM);   // :681-686: idepth_min and idepth_min_stereo are both the projection
 }
+// The back point of forward point j (:691-697, and stereoMatch's :589-595): a fresh point of the other image at the forward trace's
+// lastTraceUV.  good: the forward trace ran (skipF null: every point's did) and returned GOOD; run: its lastTraceUV addresses a readable
+// pattern, and the back point takes its trace.  pmin / pmax null: the fresh interval 0 / NaN.
+__device__ __forceinline__ void imm_back_point(int j, int w, int h, const TraceDev& F, const TraceDev& Bk, const uint8_t* __restrict__ skipF, uint8_t* __restrict__ skipB,
+                                               const float* __restrict__ pmin, const float* __restrict__ pmax, bool& good, bool& run) {
+  float bu = kTraceParkedPixel, bv = kTraceParkedPixel;
+  good = !(skipF && skipF[j]) && F.lastTraceStatus[j] == IPS_GOOD;
+  run = false;
+  if (good) {
+    const float tu = F.lastTraceUV[2 * j], tv = F.lastTraceUV[2 * j + 1];
+    if (trace_pattern_readable(tu, tv, w, h)) { run = true; bu = tu; bv = tv; }
+  }
+  skipB[j] = run ? 0 : 1;
+  fresh_point(Bk, j, bu, bv, 0.f, run && pmin ? pmin[j] : 0.f, run && pmax ? pmax[j] : NAN);
+}
 // :691-697: the back points at the forward trace's lastTraceUV, with the projected interval again
 __global__ __launch_bounds__(256) void k_imm_back_points(int n, int w, int h, TraceDev F, TraceDev Bk, const uint8_t* __restrict__ skipF, uint8_t* __restrict__ skipB,
                                                          const float* __restrict__ pmin, const float* __restrict__ pmax, int* __restrict__ counts) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   bool good = false, run = false;
-  if (j < n) {
-    float bu = kTraceParkedPixel, bv = kTraceParkedPixel;
-    good = !skipF[j] && F.lastTraceStatus[j] == IPS_GOOD;
-    if (good) {
-      const float tu = F.lastTraceUV[2 * j], tv = F.lastTraceUV[2 * j + 1];
-      if (trace_pattern_readable(tu, tv, w, h)) { run = true; bu = tu; bv = tv; }
-    }
-    skipB[j] = run ? 0 : 1;
-    fresh_point(Bk, j, bu, bv, 0.f, run ? pmin[j] : 0.f, run ? pmax[j] : NAN);
-  }
+  if (j < n) imm_back_point(j, w, h, F, Bk, skipF, skipB, pmin, pmax, good, run);
   imm_count(counts, IMM_C_FWD_GOOD, good);
   imm_count(counts, IMM_C_UNREADABLE, good && !run);
 }

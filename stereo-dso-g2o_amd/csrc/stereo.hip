@@ -9,6 +9,7 @@
 //   src/FullSystem/ImmaturePoint.cpp:459-828  ImmaturePoint::traceOn
 //   src/FullSystem/FullSystem.cpp:1600-1629   makeNewTraces
 //   src/FullSystem/FullSystem.cpp:632-781     traceNewCoarseNonKey, traceNewCoarseKey
+//   src/FullSystem/FullSystem.cpp:581-613     stereoMatch's loop (sdso_imm_stereo_match)
 //   src/FullSystem/FullSystem.cpp:948-957     activatePointsMT STEP 5
 //   src/FullSystem/FullSystem.cpp:837-957     activatePointsMT STEP 2-5 in place (sdso_imm_activate)
 //
@@ -26,6 +27,7 @@
 //   imm_compact.hip   ordered compaction (segcount / scan / segwrite), the block-wide scan, one atomic per wave for a predicate
 //   imm_set.hip       the resident set: ImmHost, ImmState, the flat index over named hosts, add / count / get / put / remove / release
 //   imm_trace.hip     sdso_imm_trace: traceOn in place and the stereo chain of the non-key trace
+//   imm_match.hip     sdso_imm_stereo_match: stereoMatch's loop on a group of the set, its kept results and dense map
 //   imm_activate.hip  sdso_imm_activate: activatePointsMT STEP 2-5 on the set
 #include "sdso_internal.h"
 #include "distmap_dev.h"
@@ -43,4 +45,5 @@ using namespace sdso;
 #include "imm_compact.hip"
 #include "imm_set.hip"
 #include "imm_trace.hip"
+#include "imm_match.hip"
 #include "imm_activate.hip"

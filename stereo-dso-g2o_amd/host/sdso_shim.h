@@ -24,6 +24,7 @@
 //   CoarseDistanceMap::{makeK, makeDistanceMap, addIntoDistFinal, fwdWarpedIDDistFinal, K, Ki}                          FullSystem/CoarseTracker.h:165-197
 //   void FullSystem::activatePointsMT() STEP 1-2                                                                      FullSystem/FullSystem.cpp:796-902
 //   void FullSystem::makeNewTraces(FrameHessian*, FrameHessian*, float*), traceNewCoarseNonKey / traceNewCoarseKey(fh, fh_right)    FullSystem/FullSystem.cpp:1600, :632, :745
+//   the loop of void FullSystem::stereoMatch(ImageAndExposure*, ImageAndExposure*, int, cv::Mat&)                      FullSystem/FullSystem.cpp:579-613
 //   Undistort::{undistort<T>, getK, getSize, getOriginalSize, getBl, isValid, loadPhotometricCalibration}               util/Undistort.h:63-104
 #pragma once
 #include <algorithm>
@@ -1387,8 +1388,9 @@ inline void marginalizeFrame(int nFrames, int idx, const double* prior8, const d
 // host->immaturePoints.  The object stands for the FullSystem members the bodies read: Hcalib, frameHessians, pixelSelector,
 // setting_desiredImmatureDensity and the stereo baseline.  slot_of(frame) is the frame's pyramid slot on the device; a keyframe's slot
 // is also its host_id in the set.  activatePointsMT runs STEP 2-5 on the set and returns the activated records; upload(host) installs
-// host->immaturePoints as the host's group.  download(host) rebuilds host->immaturePoints from the set (what stereoMatch and the older
-// activation path read); remove(host, flags) is STEP 5 for the entries STEP 2 / STEP 4 set to 0; release(host) goes where the reference deletes a
+// host->immaturePoints as the host's group.  stereoMatch(fh, fh_right, idepthMap) is the loop of FullSystem::stereoMatch (:579-613) on
+// fh's group.  download(host) rebuilds host->immaturePoints from the set (what the older activation path reads, and a caller who wants
+// the objects); remove(host, flags) is STEP 5 for the entries STEP 2 / STEP 4 set to 0; release(host) goes where the reference deletes a
 // marginalized frame's immature points (and before stereoMatch deletes its temporary frame).  A frame of frameHessians without points in
 // the set is not traced, like the reference's empty loop.  The benchmark-only and debug branches of the three functions are not mirrored.
 // Mat33fT is the reference's Eigen float matrix type (element access (i, j)); products are formed row times column, summed left to right.
@@ -1458,6 +1460,34 @@ class ImmaturePoints {
       p->gradH(0, 0) = gH[i * 4 + 0]; p->gradH(0, 1) = gH[i * 4 + 1]; p->gradH(1, 0) = gH[i * 4 + 2]; p->gradH(1, 1) = gH[i * 4 + 3];
       host->immaturePoints[i] = p;
     }
+  }
+  // The loop of FullSystem::stereoMatch (FullSystem.cpp:579-613) after makeNewTraces(fh, fh_right, 0): every point of fh traced into
+  // fh_right and back, the accept rule of :601 with the reference's depth < 70, and for every accepted point idepth_stereo, idepth_min,
+  // idepth_max at (float*)(idepthMap.data + int(v) * idepthMap.step) + (int)u * 3.  No other pixel is touched, as in the reference; returns
+  // `counter`.  MatT: the reference's cv::Mat (CV_32FC3), or anything with `unsigned char* data` and `size_t step`.  The traces and the
+  // rule run on the device (sdso_imm_stereo_match); 13 bytes per point come back, and u, v (8 more) for the pixel.  fh->immaturePoints is
+  // not touched and the group stays in the set: release(fh) goes where the reference deletes fh.
+  template <class MatT>
+  int stereoMatch(FrameHessianT* fh, FrameHessianT* fh_right, MatT& idepthMap) {
+    const int n = count(fh);
+    std::vector<uint8_t> accepted(n);
+    std::vector<float> idepth((size_t)n * 3), us(n), vs(n);
+    sdso_imm_match_out_t O{accepted.data(), idepth.data(), nullptr, nullptr, nullptr};
+    const float K4[4] = {Hcalib_.fxl(), Hcalib_.fyl(), Hcalib_.cxl(), Hcalib_.cyl()};   // K of :569-573
+    int counts[SDSO_IMM_MATCH_NCOUNTS];
+    dev_.check(sdso_imm_stereo_match(dev_.ctx(), slot_of_(fh), slot_of_(fh), slot_of_(fh_right), K4, baseline_, 70.f, 0, &O, counts), "sdso_imm_stereo_match");
+    sdso_trace_points_t P{};
+    P.n = n; P.u_stereo = us.data(); P.v_stereo = vs.data();
+    if (n) dev_.check(sdso_imm_get(dev_.ctx(), slot_of_(fh), &P, nullptr), "sdso_imm_get");
+    unsigned char* idepthMapPtr = idepthMap.data;
+    int counter = 0;
+    for (int i = 0; i < n; i++)
+      if (accepted[i]) {
+        float* px = (float*)(idepthMapPtr + int(vs[i]) * idepthMap.step) + (int)us[i] * 3;
+        px[0] = idepth[(size_t)i * 3]; px[1] = idepth[(size_t)i * 3 + 1]; px[2] = idepth[(size_t)i * 3 + 2];
+        counter++;
+      }
+    return counter;
   }
   // STEP 5 (:948-957) on the device: flags[i] != 0 where STEP 2 / STEP 4 set host->immaturePoints[i] = 0
   void remove(const FrameHessianT* host, const std::vector<uint8_t>& flags) {

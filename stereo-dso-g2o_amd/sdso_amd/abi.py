@@ -168,6 +168,14 @@ IMM_MAX_HOSTS = 8
 IMM_NCOUNTS = 10   # lastTraceStatus histogram [0..5], forward GOOD, stereo outliers, intervals updated, unreadable
 
 
+IMM_MATCH_NCOUNTS = 8   # walked, forward GOOD, back traces run, back GOOD, accepted, |du| >= 1, depth outside (0, max_depth), unreadable
+
+
+class ImmMatchOut(C.Structure):
+    """sdso_imm_match_out_t: the per-point results of sdso_imm_stereo_match and its dense map (FullSystem.cpp:598-611)."""
+    _fields_ = [("accepted", c_u8_p), ("idepth", c_float_p), ("status_fwd", c_u8_p), ("status_back", c_u8_p), ("map", c_float_p)]
+
+
 IMM_ACT_NCOUNTS = 17   # candidates, KEEP / DELETE / SELECT, toOptimize.size(), statuses -1 / 0 / 1, removed, the new count of every frame's group
 
 
@@ -521,6 +529,9 @@ def load():
     L.sdso_imm_remove.argtypes = [vp, C.c_int, C.c_int, c_u8_p]
     L.sdso_imm_release_host.argtypes = [vp, C.c_int]
     L.sdso_imm_put_host.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(TracePoints), c_float_p]
+    L.sdso_imm_stereo_match.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_float_p, C.c_float, C.c_float, C.c_int, C.POINTER(ImmMatchOut), c_int_p]
+    L.sdso_imm_stereo_match_fetch.argtypes = [vp, C.POINTER(ImmMatchOut), c_int_p]
+    L.sdso_imm_stereo_map_dev.argtypes = [vp, C.POINTER(vp), c_int_p, c_int_p]
     L.sdso_imm_activate.argtypes = [vp, C.POINTER(ImmActivate), c_int_p]
     L.sdso_imm_activate_fetch.argtypes = [vp, C.POINTER(ImmActivated), c_u8_p]
     _lib = L
@@ -551,6 +562,7 @@ EXPORTED_SYMBOLS = [
     "sdso_undistort_make_remap", "sdso_ingest_calib_create", "sdso_ingest_calib_release", "sdso_ingest_frame",
     "sdso_imm_add_frame", "sdso_imm_trace", "sdso_imm_count", "sdso_imm_get", "sdso_imm_remove_order", "sdso_imm_remove", "sdso_imm_release_host",
     "sdso_imm_put_host", "sdso_imm_activate", "sdso_imm_activate_fetch",
+    "sdso_imm_stereo_match", "sdso_imm_stereo_match_fetch", "sdso_imm_stereo_map_dev",
     "sdso_track_make_ref_from_window", "sdso_track_get_ref_points",
     "sdso_ba_flag_points",
 ]
@@ -627,6 +639,43 @@ class Context:
             setattr(P, k, fp(a[k]))
         P.lastTraceStatus = bp(a["lastTraceStatus"])
         self.check(self.L.sdso_imm_put_host(self.h, host_id, w, h, C.byref(P), fp(a["my_type"])))
+
+    def imm_match_arrays(self, n, w=0, h=0, statuses=True):
+        """An ImmMatchOut over fresh arrays for n points (and a w x h map where w > 0) -> (struct, dict of the arrays, counts)."""
+        d = dict(accepted=np.full(n, 255, np.uint8), idepth=np.full((n, 3), -1, np.float32))
+        if statuses:
+            d.update(status_fwd=np.full(n, 254, np.uint8), status_back=np.full(n, 254, np.uint8))
+        if w > 0:
+            d["map"] = np.full((h, w, 3), -1, np.float32)
+        O = ImmMatchOut()
+        for k, a in d.items():
+            setattr(O, k, bp(a) if a.dtype == np.uint8 else fp(a))
+        return O, d, np.full(IMM_MATCH_NCOUNTS, -1, np.int32)
+
+    def imm_stereo_match(self, host_id, frame_slot, right_slot, K4, baseline, max_depth=70.0, map_wh=None, statuses=True):
+        """sdso_imm_stereo_match: stereoMatch's loop (FullSystem.cpp:581-613) on one group -> dict of arrays: accepted, idepth [n, 3],
+        status_fwd, status_back, counts and, with map_wh = (w, h) of the group's image, map [h, w, 3]."""
+        n = C.c_int(0)
+        self.check(self.L.sdso_imm_count(self.h, host_id, C.byref(n)))
+        w, h = map_wh if map_wh else (0, 0)
+        O, d, counts = self.imm_match_arrays(n.value, w, h, statuses)
+        K = np.ascontiguousarray(K4, np.float32)
+        self.check(self.L.sdso_imm_stereo_match(self.h, host_id, frame_slot, right_slot, fp(K), baseline, max_depth, 1 if map_wh else 0, C.byref(O), ip(counts)))
+        d["counts"] = counts
+        return d
+
+    def imm_stereo_match_fetch(self, n, w=0, h=0, statuses=True):
+        """sdso_imm_stereo_match_fetch -> the dict of imm_stereo_match for the latest call (n its group's count; a map where w > 0)."""
+        O, d, counts = self.imm_match_arrays(n, w, h, statuses)
+        self.check(self.L.sdso_imm_stereo_match_fetch(self.h, C.byref(O), ip(counts)))
+        d["counts"] = counts
+        return d
+
+    def imm_stereo_map_dev(self):
+        """sdso_imm_stereo_map_dev -> (device pointer, w, h)"""
+        p, w, h = C.c_void_p(), C.c_int(0), C.c_int(0)
+        self.check(self.L.sdso_imm_stereo_map_dev(self.h, C.byref(p), C.byref(w), C.byref(h)))
+        return p.value, w.value, h.value
 
     def imm_activate_raw(self, host_id, frame_slot, host_flagged, KRKi, Kt, pair_R, pair_t, pair_aff, w, h, K4, min_obs, min_act_dist, min_trace_quality=3.0):
         """sdso_imm_activate without the fetch -> (return code, counts)."""
