@@ -214,6 +214,36 @@ int sdso_track_get_ref_points(sdso_ctx* ctx, int ref_slot, int* n, int* point /*
 int sdso_track_get_ref(sdso_ctx* ctx, int ref_slot, int lvl, int* n_out, float* pc_u, float* pc_v,
                        float* pc_idepth, float* pc_color);
 
+/* The keyframe's published depth images: CoarseTracker::debugPlotIDepthMap / debugPlotIDepthMapFloat (CoarseTracker.cpp:1071-1188, called
+ * unconditionally by FullSystem::makeKeyFrame, FullSystem.cpp:1444-1445) from the level-0 map idepth[0] of a template.
+ *
+ * sdso_track_keep_depth_map: off by default, and nothing changes while it is off.  On: every template sdso_track_make_ref or
+ * sdso_track_make_ref_from_window builds from then on keeps a copy of its level-0 map (w*h floats, owned by the reference slot) as STEP5
+ * leaves it (:492-533): inside [2,w-2) x [2,h-2) the normalised inverse depth or -1, in the two-pixel border the UN-normalised weighted
+ * sums of STEP1 and STEP3 — the reference's sort (:1079-1082) counts those too.  A reference installed by sdso_track_set_ref has no map;
+ * sdso_track_release_ref frees it. */
+int sdso_track_keep_depth_map(sdso_ctx* ctx, int on);
+/* debugPlotIDepthMap (:1071-1176) on the kept map of `ref_slot`; `frame_slot` = the pyramid of the frame the template was built on
+ * (lastRef->dIp[0]), whose level-0 size must be the map's.
+ *   range      : allID = the pixels with idepth > 0 (:1078-1082); minID_new = allID[(int)(n*0.05)], maxID_new = allID[(int)(n*0.95)],
+ *                n = size-1 (:1085-1088), selected exactly without sorting.
+ *   smoothing  : :1094-1117 against *minID_pt / *maxID_pt (in/out, both or neither).  Both NULL: the new range is used as it is.
+ *   image      : rgb (w*h*3 bytes, or NULL) = the B3 image pushDepthImage receives: background :1122-1126, overlay :1129-1163 with
+ *                makeJet3B (globalFuncs.h:362-379) and setPixelCirc (MinimalImage.h:100-112), later sources overwriting earlier ones.
+ *                idepth (w*h floats, or NULL) = the kept map, the image pushDepthImageFloat receives (:1178-1188).
+ *   counts     : [0] allID.size(), [1] the pixels that drew a circle; may be NULL.
+ *   deviations : with no positive pixel the reference indexes an empty vector; here the image is the background alone, counts are 0, 0 and
+ *                the two range values are left untouched.  A NaN intensity gives a background byte of 0.
+ *   refusals   : before any device work.  SDSO_ERR_STATE: the slot keeps no map.  SDSO_ERR_ARG: an unknown slot, a frame of another
+ *                size, exactly one of minID_pt / maxID_pt NULL.
+ *   sync       : one enqueue of the whole chain, one copy back (range, counts and the images asked for), one synchronisation. */
+int sdso_track_depth_image(sdso_ctx* ctx, int ref_slot, int frame_slot, float* minID_pt, float* maxID_pt,
+                           uint8_t* rgb /* w*h*3 or NULL */, float* idepth /* w*h or NULL */, int* counts /* 2, or NULL */);
+/* The device images of the latest sdso_track_depth_image on `ref_slot`, valid until the next call on it (SDSO_ERR_STATE before the
+ * first).  idepth_dev is the kept map itself: debugPlotIDepthMapFloat wraps idepth[0] without copying (:1183). */
+int sdso_track_depth_image_dev(sdso_ctx* ctx, int ref_slot, void** rgb_dev /* uint8_t*, w*h*3 */, void** idepth_dev /* float*, w*h */,
+                               int* w, int* h);
+
 /* Host-only helper (no GPU work): fill the evaluation parameters for (level, pose, affine) the way
  * CoarseTracker::makeK (:108-136) and calcRes (:617-621) derive them; cutoffTH =
  * prm->coarseCutoffTH * levelCutoffRepeat. Declared after sdso_track_params_t below. */

@@ -7,6 +7,8 @@
 //   :390-441  STEP3 dilation  levels 0,1: the four diagonal neighbours
 //   :445-488  STEP4 dilation  levels >= 2: the four axis neighbours
 //   :491-533  STEP5 normalise + compaction in the scan order y in [2,h-2), x in [2,w-2)
+// With sdso_track_keep_depth_map on, the level-0 map idepth[0] is copied into the reference slot once STEP5 has run on it: the input of
+// debugPlotIDepthMap / debugPlotIDepthMapFloat (:1071-1188, depth_image.hip).
 // (the static-stereo refinement at the top of STEP1, :295-347, is sdso_stereo_match_batch; the caller applies the accept
 // rule and passes the resulting new_idepth / weight here.)
 //
@@ -209,6 +211,13 @@ int track_make_ref_dev(sdso_ctx* ctx, int ref_slot, int frame_slot, int n, const
     SDSO_HIP(ctx, hipMalloc(&R.pc[l], sizeof(float4) * (size_t)cap));
     R.cap[l] = cap;
   }
+  // the kept level-0 map (sdso_track_keep_depth_map): one block per slot, kept while the size holds
+  R.map_ok = R.image_ok = false;
+  if (ctx->keep_depth_map) {
+    if (R.dmap && (R.dmap_w != P.w[0] || R.dmap_h != P.h[0])) { SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream)); hipFree(R.dmap); R.dmap = nullptr; }
+    if (!R.dmap) SDSO_HIP(ctx, hipMalloc((void**)&R.dmap, depth_map_layout(P.w[0], P.h[0]).end));
+    R.dmap_w = P.w[0]; R.dmap_h = P.h[0];
+  }
   SDSO_HIP(ctx, hipMemsetAsync(idm, 0, sizeof(float) * 2 * tot, ctx->stream));
   if (n) hipLaunchKernelGGL(k_cd_splat, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, w0, d_u, d_v, d_idp, d_wgt, idm, wsm);
   for (int l = 1; l < L; l++)
@@ -224,9 +233,15 @@ int track_make_ref_dev(sdso_ctx* ctx, int ref_slot, int frame_slot, int n, const
   SDSO_HIP(ctx, hipMemsetAsync(d_total, 0, sizeof(int) * SDSO_PYR_LEVELS, ctx->stream));
   for (int l = 0; l < L; l++) {
     const int nrows = P.h[l] - 4;
-    if (nrows <= 0 || P.w[l] <= 4) continue;
-    hipLaunchKernelGGL(k_cd_flag, dim3(nrows), dim3(256), 0, ctx->stream, idm + off[l], wsm + off[l], P.d[l], P.w[l], P.h[l], rowcnt + roff[l]);
-    hipLaunchKernelGGL(k_cd_scan, dim3(1), dim3(256), 0, ctx->stream, rowcnt + roff[l], nrows, d_total + l);
+    if (nrows > 0 && P.w[l] > 4) {
+      hipLaunchKernelGGL(k_cd_flag, dim3(nrows), dim3(256), 0, ctx->stream, idm + off[l], wsm + off[l], P.d[l], P.w[l], P.h[l], rowcnt + roff[l]);
+      hipLaunchKernelGGL(k_cd_scan, dim3(1), dim3(256), 0, ctx->stream, rowcnt + roff[l], nrows, d_total + l);
+    }
+    // idepth[0] as STEP5 leaves it (:492-533): normalised or -1 inside [2,w-2) x [2,h-2), the raw sums of STEP1 / STEP3 in the border
+    if (l == 0 && ctx->keep_depth_map) {
+      SDSO_HIP(ctx, hipMemcpyAsync(R.dmap, idm, sizeof(float) * (size_t)P.w[0] * P.h[0], hipMemcpyDeviceToDevice, ctx->stream));
+      R.map_ok = true;
+    }
   }
   SDSO_HIP(ctx, hipMemcpyAsync(R.counts_host, d_total, sizeof(int) * SDSO_PYR_LEVELS, hipMemcpyDeviceToHost, ctx->stream));
   SDSO_HIP(ctx, hipEventRecord(R.counts_ev, ctx->stream));
@@ -272,6 +287,12 @@ extern "C" int sdso_track_make_ref(sdso_ctx* ctx, int ref_slot, int frame_slot, 
     SDSO_HIP(ctx, hipMemcpyAsync(d_v, v, sizeof(int) * n, hipMemcpyHostToDevice, ctx->stream));
   }
   return track_make_ref_dev(ctx, ref_slot, frame_slot, n, d_u, d_v, d_idp, d_wgt, pc_n_out, true);
+}
+
+extern "C" int sdso_track_keep_depth_map(sdso_ctx* ctx, int on) {
+  if (!ctx) return SDSO_ERR_STATE;
+  ctx->keep_depth_map = on ? 1 : 0;
+  return SDSO_OK;
 }
 
 extern "C" int sdso_track_get_ref(sdso_ctx* ctx, int ref_slot, int lvl, int* n_out, float* pc_u, float* pc_v, float* pc_idepth, float* pc_color) {

@@ -48,7 +48,19 @@ struct RefDev {
   bool counts_pending = false;
   int* counts_host = nullptr;
   hipEvent_t counts_ev = nullptr;
+  // The level-0 map idepth[0] this template was built from, kept under sdso_track_keep_depth_map (coarse_depth.hip) for
+  // sdso_track_depth_image (depth_image.hip).  One allocation, laid out by depth_map_layout: the map, the image call's 16-byte record and
+  // its B3 image, so that any choice of outputs is one contiguous copy.  map_ok: the block holds the map of the template now installed.
+  char* dmap = nullptr;
+  int dmap_w = 0, dmap_h = 0;
+  bool map_ok = false, image_ok = false;
 };
+// the kept block of a w x h map: [0, rec) the map (w*h floats) | [rec, rgb) {minID, maxID, allID.size(), circles} | [rgb, end) w*h*3 bytes
+struct DepthMapLayout { size_t rec, rgb, end; };
+inline DepthMapLayout depth_map_layout(int w, int h) {
+  const size_t px = (size_t)w * h;
+  return {sizeof(float) * px, sizeof(float) * px + 16, sizeof(float) * px + 16 + 3 * px};
+}
 
 struct ProfEntry {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;  // pending (start, stop) pairs
@@ -105,6 +117,7 @@ struct sdso_ctx {
   hipStream_t aux = nullptr;
   hipEvent_t ev_main = nullptr, ev_aux = nullptr;
   int aux_cus = 0;
+  int keep_depth_map = 0;   // sdso_track_keep_depth_map: templates built by track_make_ref_dev keep their level-0 map (RefDev::dmap)
   int gn_mode = 0;   // traceStereo refinement: 0 DSO-native, 1 fork-live g2o GN (sdso_trace_set_gn_mode)
   float* gammaB = nullptr;   // device copy of CalibHessian::B (256 floats) for the gamma-weighted absSquaredGrad; null = identity response
   // device buffers of released BA windows, kept for the next upload (a window is re-uploaded for every keyframe)
@@ -155,6 +168,8 @@ inline void ref_free(RefDev& R) {
   if (R.counts_host) hipHostFree(R.counts_host);
   if (R.counts_ev) hipEventDestroy(R.counts_ev);
   R.counts_host = nullptr; R.counts_ev = nullptr; R.counts_pending = false;
+  if (R.dmap) hipFree(R.dmap);
+  R.dmap = nullptr; R.dmap_w = R.dmap_h = 0; R.map_ok = R.image_ok = false;
 }
 // ---- a frame slot as the entry points see it.  Every refusal is SDSO_ERR_ARG; nothing is launched or waited for before them.
 // Level 0 and the sizes of the pyramid in `frame_slot`; `unknown` is the caller's refusal text where it names the slot.

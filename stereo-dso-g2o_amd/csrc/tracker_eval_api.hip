@@ -15,6 +15,7 @@ extern "C" int sdso_track_set_ref(sdso_ctx* ctx, int ref_slot, int lvl, int n, c
   if (rc0) return rc0;
   if (R.pc[lvl]) { SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream)); hipFree(R.pc[lvl]); R.pc[lvl] = nullptr; }
   R.n[lvl] = n; R.cap[lvl] = n;
+  R.map_ok = R.image_ok = false;   // a template that came from the host has no level-0 map
   if (n == 0) return SDSO_OK;
   std::vector<float4> h(n);
   for (int i = 0; i < n; i++) h[i] = make_float4(pc_u[i], pc_v[i], pc_idepth[i], pc_color[i]);

@@ -17,6 +17,8 @@
 //   ImmaturePointStatus ImmaturePoint::traceStereo(FrameHessian* frame, Mat33f K, bool mode_right)                   FullSystem/ImmaturePoint.h:89
 //   void CoarseTracker::setCoarseTrackingRef(std::vector<FrameHessian*>, FrameHessian* fh_right, CalibHessian)        FullSystem/CoarseTracker.h:71-72
 //   void CoarseTracker::setCTRefForFirstFrame(std::vector<FrameHessian*>)                                           FullSystem/CoarseTracker.cpp:794-805
+//   void CoarseTracker::debugPlotIDepthMap(float* minID, float* maxID, std::vector<IOWrap::Output3DWrapper*>& wraps)    FullSystem/CoarseTracker.h:94, CoarseTracker.cpp:1071-1176
+//   void CoarseTracker::debugPlotIDepthMapFloat(std::vector<IOWrap::Output3DWrapper*>& wraps)                         FullSystem/CoarseTracker.h:95, CoarseTracker.cpp:1178-1188
 //   double PointFrameResidual::linearize(CalibHessian*) / void applyRes(bool)                                        FullSystem/Residuals.h:103, :113
 //   AccumulatedTopHessianSSE::{setZero, addPoint<mode>, addPointsInternal<mode>, stitchDouble, stitchDoubleMT}        OptimizationBackend/AccumulatedTopHessian.h:66-97, :162-169
 //   AccumulatedSCHessianSSE::{setZero, addPoint, addPointsInternal, stitchDouble, stitchDoubleMT}                     OptimizationBackend/AccumulatedSCHessian.h:66-96, :155-160
@@ -103,7 +105,12 @@ inline SE3T fromAbi(const sdso_se3_t& a) {
 template <class SE3T, class AffLightT, class Mat33T, class Vec3T>
 class CoarseTracker {
  public:
-  CoarseTracker(Device& dev, int ref_slot) : dev_(dev), ref_slot_(ref_slot) {
+  // publishDepthImages: the hook for debugPlotIDepthMap / debugPlotIDepthMapFloat.  FullSystem owns the wrapper list (outputWrapper) and
+  // hands it to those two members per call, so the tracker cannot see at construction whether anyone listens: the caller says so here —
+  // pass !outputWrapper.empty() for coarseTracker and coarseTracker_forNewKF.  true switches sdso_track_keep_depth_map on for the Device
+  // (every template built on it from then on keeps its level-0 map); false leaves the library as it is and the two members throw.
+  CoarseTracker(Device& dev, int ref_slot, bool publishDepthImages = false) : dev_(dev), ref_slot_(ref_slot), publish_(publishDepthImages) {
+    if (publish_) dev_.check(sdso_track_keep_depth_map(dev_.ctx(), 1), "sdso_track_keep_depth_map");
     std::memset(&prm_, 0, sizeof(prm_));
     prm_.coarseCutoffTH = 20.f; prm_.huberTH = 9.f;                 // settings.cpp:102, :95
     const int its[5] = {10, 20, 50, 50, 50};                         // CoarseTracker.cpp:861 (DSO-native)
@@ -129,6 +136,7 @@ class CoarseTracker {
   void setCoarseTrackingRef(int lvl, int pc_n, const float* pc_u, const float* pc_v, const float* pc_idepth, const float* pc_color,
                             float lastRef_ab_exposure, const AffLightT& lastRef_aff_g2l_, int refFrameID_) {
     dev_.check(sdso_track_set_ref(dev_.ctx(), ref_slot_, lvl, pc_n, pc_u, pc_v, pc_idepth, pc_color), "sdso_track_set_ref");
+    newRef_(nullptr, -1);                                           // a template from the host carries no level-0 map
     prm_.ref_exposure = lastRef_ab_exposure;
     prm_.ref_aff_g2l.a = lastRef_aff_g2l_.a; prm_.ref_aff_g2l.b = lastRef_aff_g2l_.b;
     refFrameID = refFrameID_;
@@ -140,6 +148,7 @@ class CoarseTracker {
   void makeCoarseDepthL0(int lastRef_slot, int n, const int* u, const int* v, const float* new_idepth, const float* weight, int* pc_n,
                          float lastRef_ab_exposure, const AffLightT& lastRef_aff_g2l_, int refFrameID_) {
     dev_.check(sdso_track_make_ref(dev_.ctx(), ref_slot_, lastRef_slot, n, u, v, new_idepth, weight, pc_n), "sdso_track_make_ref");
+    newRef_(nullptr, lastRef_slot);
     prm_.ref_exposure = lastRef_ab_exposure;
     prm_.ref_aff_g2l.a = lastRef_aff_g2l_.a; prm_.ref_aff_g2l.b = lastRef_aff_g2l_.b;
     refFrameID = refFrameID_;
@@ -221,6 +230,7 @@ class CoarseTracker {
       }
     dev_.check(sdso_track_make_ref_from_window(dev_.ctx(), ref_slot_, ba.win(), slot_of(fh_right), baseline, order.data(), (int)order.size(), &n_points,
                                                &n_border, pc_n), "sdso_track_make_ref_from_window");
+    newRef_(lastRef, slot_of(lastRef));
     refFrameID = lastRef->shell->id;                         // :821-825
     lastRef_aff_g2l = lastRef->aff_g2l();
     prm_.ref_exposure = lastRef->ab_exposure;
@@ -243,6 +253,47 @@ class CoarseTracker {
     }
     installRef_(lastRef, (int)iu.size(), iu.data(), iv.data(), nid.data(), wgt.data());
   }
+  // void debugPlotIDepthMap(float* minID_pt, float* maxID_pt, std::vector<IOWrap::Output3DWrapper*>& wraps) — CoarseTracker.cpp:1071-1176,
+  // what FullSystem::makeKeyFrame calls on coarseTracker_forNewKF for every keyframe (FullSystem.cpp:1444).  The sort of :1078-1088, the
+  // smoothing of :1094-1117 and the image of :1119-1163 run on the device on the map the latest template kept (sdso_track_depth_image);
+  // here: the early return of :1072, the MinimalImageB3 the wrappers receive, and the pushes of :1167-1168.  The call also brings the
+  // float map to the host, where debugPlotIDepthMapFloat finds it.  MinimalImageB3T is named by the caller: dso::MinimalImageB3.
+  // (debugSaveImages' writeImage, :1170-1174, is the caller's: the image is the one the wrappers were handed.)
+  template <class MinimalImageB3T, class WrapT>
+  void debugPlotIDepthMap(float* minID_pt, float* maxID_pt, std::vector<WrapT*>& wraps) {
+    if (prm_.w[1] == 0) return;                              // :1072
+    requireMap_("debugPlotIDepthMap");
+    const int w = prm_.w[0], h = prm_.h[0];
+    MinimalImageB3T mf(w, h);
+    static_assert(sizeof(*mf.data) == 3, "MinimalImageB3 holds three bytes per pixel");
+    idepth0_.resize((size_t)w * h);
+    float lo = minID_pt ? *minID_pt : 0.f, hi = maxID_pt ? *maxID_pt : 0.f;
+    const bool both = minID_pt != 0 && maxID_pt != 0;        // :1094: otherwise the new range is used and nothing is written back
+    dev_.check(sdso_track_depth_image(dev_.ctx(), ref_slot_, lastRef_slot_, both ? &lo : nullptr, both ? &hi : nullptr,
+                                      reinterpret_cast<uint8_t*>(mf.data), idepth0_.data(), depthImageCounts), "sdso_track_depth_image");
+    if (both) { *minID_pt = lo; *maxID_pt = hi; }
+    idepth0_ok_ = true;
+    for (WrapT* ow : wraps) ow->pushDepthImage(&mf);         // :1167-1168
+  }
+  // void debugPlotIDepthMapFloat(std::vector<IOWrap::Output3DWrapper*>& wraps) — CoarseTracker.cpp:1178-1188: a MinimalImageF that wraps
+  // idepth[0] without copying, pushed with lastRef.  idepth[0] is the host copy debugPlotIDepthMap brought along (FullSystem.cpp:1444-1445
+  // calls the two back to back); called on its own, the member downloads the map first.  The wrapped memory stays valid until the next
+  // call of either member.  FrameHessianT is the type setCoarseTrackingRef was given (dso::FrameHessian).
+  template <class MinimalImageFT, class FrameHessianT, class WrapT>
+  void debugPlotIDepthMapFloat(std::vector<WrapT*>& wraps) {
+    if (prm_.w[1] == 0) return;                              // :1179
+    requireMap_("debugPlotIDepthMapFloat");
+    const int w = prm_.w[0], h = prm_.h[0];
+    if (!idepth0_ok_) {
+      idepth0_.resize((size_t)w * h);
+      dev_.check(sdso_track_depth_image(dev_.ctx(), ref_slot_, lastRef_slot_, nullptr, nullptr, nullptr, idepth0_.data(), depthImageCounts), "sdso_track_depth_image");
+      idepth0_ok_ = true;
+    }
+    MinimalImageFT mim(w, h, idepth0_.data());               // :1183
+    FrameHessianT* lastRef = static_cast<FrameHessianT*>(const_cast<void*>(lastRef_));
+    for (WrapT* ow : wraps) ow->pushDepthImageFloat(&mim, lastRef);   // :1185-1187
+  }
+  int depthImageCounts[2] = {0, 0};                          // of the latest image: allID.size(), pixels that drew a circle
   // bool trackNewestCoarse(FrameHessian* newFrameHessian, SE3& lastToNew_out, AffLight& aff_g2l_out, int coarsestLvl, Vec5 minResForAbort,
   //                        IOWrap::Output3DWrapper* wrap = 0) — CoarseTracker.h:62-66 verbatim (the debug wrapper is not used)
   template <class FrameHessianT, class Vec5T>
@@ -297,14 +348,26 @@ class CoarseTracker {
   template <class FrameHessianT>
   void installRef_(FrameHessianT* lastRef, int n, const int* u, const int* v, const float* new_idepth, const float* weight) {
     dev_.check(sdso_track_make_ref(dev_.ctx(), ref_slot_, slot_of(lastRef), n, u, v, new_idepth, weight, pc_n), "sdso_track_make_ref");
+    newRef_(lastRef, slot_of(lastRef));
     refFrameID = lastRef->shell->id;                         // :821-825
     lastRef_aff_g2l = lastRef->aff_g2l();
     prm_.ref_exposure = lastRef->ab_exposure;
     prm_.ref_aff_g2l.a = lastRef_aff_g2l.a; prm_.ref_aff_g2l.b = lastRef_aff_g2l.b;
     firstCoarseRMSE = -1;
   }
+  // a new template: lastRef (null where the caller gave a slot only) and its pyramid slot, for the two debugPlot members
+  void newRef_(const void* lastRef, int lastRef_slot) { lastRef_ = lastRef; lastRef_slot_ = lastRef_slot; idepth0_ok_ = false; }
+  void requireMap_(const char* who) const {
+    if (!publish_) throw Error(std::string(who) + ": the tracker was constructed without publishDepthImages");
+    if (lastRef_slot_ < 0) throw Error(std::string(who) + ": no template built on the device is installed");
+  }
   Device& dev_;
   int ref_slot_;
+  bool publish_;
+  const void* lastRef_ = nullptr;
+  int lastRef_slot_ = -1;
+  std::vector<float> idepth0_;                               // idepth[0] on the host, as debugPlotIDepthMapFloat wraps it
+  bool idepth0_ok_ = false;
   sdso_track_params_t prm_;
 };
 

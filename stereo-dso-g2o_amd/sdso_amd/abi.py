@@ -533,6 +533,9 @@ def load():
     L.sdso_imm_stereo_match_fetch.argtypes = [vp, C.POINTER(ImmMatchOut), c_int_p]
     L.sdso_imm_stereo_map_dev.argtypes = [vp, C.POINTER(vp), c_int_p, c_int_p]
     L.sdso_imm_activate.argtypes = [vp, C.POINTER(ImmActivate), c_int_p]
+    L.sdso_track_keep_depth_map.argtypes = [vp, C.c_int]
+    L.sdso_track_depth_image.argtypes = [vp, C.c_int, C.c_int, c_float_p, c_float_p, c_u8_p, c_float_p, c_int_p]
+    L.sdso_track_depth_image_dev.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), c_int_p, c_int_p]
     L.sdso_imm_activate_fetch.argtypes = [vp, C.POINTER(ImmActivated), c_u8_p]
     _lib = L
     return L
@@ -565,6 +568,7 @@ EXPORTED_SYMBOLS = [
     "sdso_imm_stereo_match", "sdso_imm_stereo_match_fetch", "sdso_imm_stereo_map_dev",
     "sdso_track_make_ref_from_window", "sdso_track_get_ref_points",
     "sdso_ba_flag_points",
+    "sdso_track_keep_depth_map", "sdso_track_depth_image", "sdso_track_depth_image_dev",
 ]
 
 
@@ -720,6 +724,45 @@ class Context:
         dec, cnt, hc = np.full(npts, 255, np.uint8), np.full(6, -1, np.int32), np.full((nf, 6), -1, np.int32)
         self.check(self.L.sdso_ba_flag_points(self.h, wid, C.byref(F), bp(dec), ip(cnt), ip(hc)))
         return dec, cnt, hc
+
+    def keep_depth_map(self, on=True):
+        """sdso_track_keep_depth_map: templates built from now on keep their level-0 map."""
+        self.check(self.L.sdso_track_keep_depth_map(self.h, 1 if on else 0))
+
+    def depth_image_raw(self, ref_slot, frame_slot, w, h, prev=None, rgb=True, idepth=True):
+        """sdso_track_depth_image without the check -> (return code, dict).  prev = (minID, maxID) stands for *minID_pt / *maxID_pt,
+        None for two null pointers; dict: rgb [h, w, 3] uint8, idepth [h, w], counts [2], range (the two values after the call, or None)."""
+        d = dict(counts=np.full(2, -1, np.int32))
+        if rgb:
+            d["rgb"] = np.full((h, w, 3), 77, np.uint8)
+        if idepth:
+            d["idepth"] = np.full((h, w), -7, np.float32)
+        r = None if prev is None else np.array(prev, np.float32)
+        rc = self.L.sdso_track_depth_image(self.h, ref_slot, frame_slot, None if r is None else fp(r[0:1]), None if r is None else fp(r[1:2]),
+                                           bp(d["rgb"]) if rgb else None, fp(d["idepth"]) if idepth else None, ip(d["counts"]))
+        d["range"] = None if r is None else (r[0], r[1])
+        return rc, d
+
+    def depth_image(self, ref_slot, frame_slot, w, h, prev=None, rgb=True, idepth=True):
+        """sdso_track_depth_image (debugPlotIDepthMap / debugPlotIDepthMapFloat on the slot's kept map) -> the dict of depth_image_raw."""
+        rc, d = self.depth_image_raw(ref_slot, frame_slot, w, h, prev, rgb, idepth)
+        self.check(rc)
+        return d
+
+    def depth_image_dev(self, ref_slot):
+        """sdso_track_depth_image_dev -> (rgb device pointer, idepth device pointer, w, h)"""
+        a, b, w, h = C.c_void_p(), C.c_void_p(), C.c_int(0), C.c_int(0)
+        self.check(self.L.sdso_track_depth_image_dev(self.h, ref_slot, C.byref(a), C.byref(b), C.byref(w), C.byref(h)))
+        return a.value, b.value, w.value, h.value
+
+    def read_device(self, ptr, nbytes):
+        """nbytes at a device pointer of this context, after its stream has drained (hipMemcpy through the HIP runtime the library uses)"""
+        self.sync()
+        out = np.zeros(nbytes, np.uint8)
+        rc = self.L.hipMemcpy(C.c_void_p(out.ctypes.data), C.c_void_p(ptr), C.c_size_t(nbytes), 2)   # hipMemcpyDeviceToHost
+        if rc != 0:
+            raise SdsoError("hipMemcpy from the device failed (%d)" % rc)
+        return out
 
     def upload_pyramid(self, slot, pyr):
         n = len(pyr)
