@@ -1092,6 +1092,86 @@ typedef struct {
 int sdso_g2o_lba_eval(sdso_ctx* ctx, const sdso_g2o_lba_t* L, double* error, double* J, uint8_t* state, float* energy,
                       float* centerProjectedTo, float* idepth_hessian, uint8_t* edge_level);
 
+/* ------------------------------------------------------------------ the device-resident map
+ * What FullSystem::makeKeyFrame publishes through publishKeyframes (FullSystem.cpp:1467 for the whole window, FullSystemMarginalize.cpp:184
+ * for a frame that leaves) and the one consumer the reference ships, KeyFrameDisplay::setFromKF / refreshPC
+ * (IOWrapper/Pangolin/KeyFrameDisplay.cpp:85-165, :174-323): the points of every keyframe as 3-D vertices and colours.
+ *
+ * The map is one per ctx.  Keyframes are keyed by FrameHessian::frameID; each holds three growable device lists of records — pointHessians
+ * (list 1), pointHessiansMarginalized (2), pointHessiansOut (3); the list is the record's status (:129, :144, :158), the immature points
+ * (status 0, :104-117) are read from the resident immature set.  A record is 16 floats (csrc/map_cloud.h states it and every rule below):
+ *   u, v, idepth, idepth_hessian, maxRelBaseline, color[8], 3 floats of padding (0 when the device wrote the record)
+ *
+ * sdso_map_update — setFromKF's copy, made while the window's post-state is valid.  For every frame of the window the keyframe's active
+ * list is REPLACED by the named points in the given order; the leaving points are APPENDED to their host keyframe's marginalised or out
+ * list in the given order.  A keyframe is created by the first update that names it.  Values come from the resident window (u, v, idepth;
+ * maxRelBaseline and idepth_hessian of the closing linearizeAll / the last solve; the colours): only the 4-byte indices cross the bus.
+ * The host supplies the orders because removeOutliers and flagPointsForRemoval walk fh->pointHessians with swap-with-back compaction,
+ * which the caller's pointer graph already runs; the window's own order differs (see point_order of sdso_track_make_ref_from_window).
+ *   valid when : as for sdso_ba_flag_points — an optimize call has ended on the window, no sdso_ba_window_update has run since, it holds
+ *                no linearised residual (so: before sdso_ba_marginalize_points) and is outside a batch.  Otherwise SDSO_ERR_STATE.
+ *   refusals   : SDSO_ERR_ARG before any device work: an unknown window, a NULL struct, an index out of range or named twice across
+ *                active and gone, a gone_list byte other than 2 or 3, n_active + n_gone != np when active is given.  A refused call
+ *                leaves the map as it was, and so does one that fails in its device phase (SDSO_ERR_HIP): room is made first, the
+ *                new sizes are committed once the gather is enqueued.  The call changes nothing in the window.
+ *   cost       : one upload of the index lists, one kernel, no read-back: enqueue only.  A list that has to grow is allocated anew
+ *                (doubling) and copied device to device, which synchronises once. */
+typedef struct {
+  int n_active; const int* active;     /* window point indices: fh->pointHessians after FullSystem.cpp:1044-1053, frame by frame.
+                                          NULL: every point not named in `gone`, in window order */
+  int n_gone;   const int* gone;       /* window point indices in the order the reference pushed them this keyframe:
+                                          removeOutliers' (FullSystemOptimize.cpp:1073-1079) before flagPointsForRemoval's (:997-1041) */
+  const uint8_t* gone_list;            /* n_gone: 2 = pointHessiansMarginalized, 3 = pointHessiansOut */
+} sdso_map_update_t;
+int sdso_map_update(sdso_ctx* ctx, int win, const sdso_map_update_t* upd);
+/* list sizes of a keyframe: active, marginalised, out.  SDSO_ERR_ARG for an unknown frameID (as in every call below that names one) */
+int sdso_map_counts(sdso_ctx* ctx, int frameID, int* counts /* 3 */);
+/* tests / debugging: list 1, 2 or 3 of a keyframe as records (counts[list - 1] * 16 floats) */
+int sdso_map_get(sdso_ctx* ctx, int frameID, int list, float* records);
+/* the inverse of sdso_map_get, as sdso_imm_put_host is of sdso_imm_get: REPLACES the list by n host records (a caller that joins in
+ * mid-run, and the tests); creates the keyframe where it is unknown */
+int sdso_map_put(sdso_ctx* ctx, int frameID, int list, int n, const float* records);
+/* forget a keyframe (after its `final = true` publication) / every keyframe.  sdso_ctx_destroy frees everything. */
+int sdso_map_release_keyframe(sdso_ctx* ctx, int frameID);
+int sdso_map_clear(sdso_ctx* ctx);
+
+/* refreshPC (:174-295) for up to 8 keyframes in one call.
+ *   order      : frames in the given order; per frame immature, active, marginalised, out (:104-160), each in list order; per kept point
+ *                its 8 vertices in patternP order.  The output is packed: first[k] is the first vertex of frame k, first[n_frames] the
+ *                total.  kept[4k + s]: the POINTS of frame k with status s that passed (8 vertices each).
+ *   keep tests : :215-234 in the reference's order and arithmetic (var = (float)(1.0f / ((double)idepth_hessian + 0.01))); every
+ *                comparison as written, so a NaN passes — an immature point whose idepth_max is still NaN is emitted, with NaN vertices,
+ *                wherever minBS <= 0 and the mode shows status 0.  Modes above 2 show nothing.
+ *   vertex     : ((u + dx) * fxi + cxi) * depth, the y analogue, z = depth; float, one rounding per operation; fxi = 1/fx, cxi = -cx/fx
+ *                in float (setFromF, :77-80).  camToWorld == NULL: camera-frame vertices, the buffer the reference uploads.  Otherwise
+ *                X = R[0]*x + R[1]*y + R[2]*z + t[0] (rows 1, 2 alike), float, summed left to right: what Pangolin leaves to the GL matrix.
+ *   colour     : mode 0 the fixed colours of :250-282, otherwise the grey triple (unsigned char)color[pnt]
+ *   deviations : (1) refreshPC draws rand() for a z jitter of relative size +-fxi (:246) and for sparsity > 1 (:240), from the
+ *                process-wide generator in emission order; a library cannot reproduce either.  Here z = depth — the reference's
+ *                expression with every draw at 0.5 — and there is no sparsification.  (2) With no vertex the reference returns before
+ *                touching its buffers; here first[] is all zeros and the arrays are untouched.  (3) The colour byte is truncation for
+ *                0 <= c < 256; outside it is the low byte of x86's float -> int conversion, 0 for a NaN or a value beyond int.
+ *   refusals   : SDSO_ERR_ARG before anything is launched or copied: n_frames outside 1..8, a NaN threshold, a frame named twice, an
+ *                unknown frameID — these first, without touching the device —, then an unknown immature group and cap below the
+ *                upper bound 8 x the sum of the list sizes (sdso_map_counts, sdso_imm_count), decided on the bound, not on the
+ *                outcome.  The bound needs the groups' counts: a group whose sdso_imm_add_frame has not reported its count yet is
+ *                waited for here (that add's event, as sdso_imm_count waits; not the stream).
+ *   cost       : one upload of the query, two kernels, and two waits (measured equal to one wait on a copy of the upper bound,
+ *                profiles/map_cloud_timing.txt): for the 128 bytes of per-list counts, which size the copy, and
+ *                for the copy of the used prefix of the two arrays.  Integer counting only: a second call returns the same bytes. */
+typedef struct {
+  int n_frames; const int* frameID; const int* imm_host_id;   /* imm_host_id[k] < 0 or NULL: no immature list; else the sdso_imm_* group */
+  float fx, fy, cx, cy;                                       /* HCalib->fxl() .. cyl() */
+  float scaledTH, absTH, minBS; int mode;                     /* Pangolin's defaults: 0.001, 0.001, 0.1, 1 */
+  const float* camToWorld;                                    /* n_frames*12 (R row-major, t) or NULL */
+  int cap;                                                    /* vertices the caller's arrays hold */
+} sdso_map_cloud_t;
+int sdso_map_cloud(sdso_ctx* ctx, const sdso_map_cloud_t* q, float* xyz /* cap*3 */, uint8_t* rgb /* cap*3 */,
+                   int* first /* n_frames+1 */, int* kept /* n_frames*4 per status, or NULL */);
+/* the latest call's device buffers (float xyz[n*3], uint8_t rgb[n*3]) for a renderer, valid until the next sdso_map_cloud;
+ * SDSO_ERR_STATE before the first */
+int sdso_map_cloud_dev(sdso_ctx* ctx, void** xyz_dev, void** rgb_dev, int* n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -607,5 +607,12 @@ int ba_ref_view(sdso_ctx* ctx, int win, BaRefView* out) {
   out->K[0] = W->d.fxl; out->K[1] = W->d.fyl; out->K[2] = W->d.cxl; out->K[3] = W->d.cyl;
   return SDSO_OK;
 }
+int ba_window_hosts(sdso_ctx* ctx, int win, int frameID[8], int host_pt_beg[9]) {
+  BaWindowDev* W = find_win(ctx, win);
+  if (!W) return sdso::fail(ctx, SDSO_ERR_ARG, "unknown window");
+  for (int f = 0; f < 8; f++) frameID[f] = f < W->d.nf ? W->frames[f].frameID : -1;
+  std::memcpy(host_pt_beg, W->d.host_pt_beg, sizeof(W->d.host_pt_beg));
+  return SDSO_OK;
+}
 }  // namespace sdso
 

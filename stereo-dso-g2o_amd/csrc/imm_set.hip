@@ -93,6 +93,13 @@ static int imm_find_resolved(sdso_ctx* ctx, int host_id, ImmHost** out) {
   *out = &it->second;
   return imm_resolve(ctx, it->second);
 }
+int imm_host_view(sdso_ctx* ctx, int host_id, const float** f, int* n, int* cap) {
+  ImmHost* H = nullptr;
+  *f = nullptr; *n = 0; *cap = 0;
+  const int rc = imm_find_resolved(ctx, host_id, &H);
+  if (H) { *f = H->f[0]; *n = rc ? 0 : H->n; *cap = H->cap; }
+  return rc;
+}
 // after a gather into the second blob has been enqueued: that blob is the host's current one
 static void imm_swap_blobs(ImmHost& H) { std::swap(H.f[0], H.f[1]); std::swap(H.st[0], H.st[1]); }
 

@@ -80,6 +80,7 @@ struct ImmState;     // imm_set.hip (a part of stereo.hip)
 struct Comm;         // comm.hip
 struct RefWinState;  // ref_window.hip
 struct BaDev;        // ba_kernels.h
+struct MapState;     // map.hip
 
 }  // namespace sdso
 
@@ -100,6 +101,7 @@ struct sdso_ctx {
   sdso::IngestState* ingest = nullptr;  // calibration tables and raw-image staging of sdso_ingest_frame
   sdso::ImmState* imm = nullptr;        // the device-resident immature points, per host keyframe (sdso_imm_*)
   sdso::RefWinState* refwin = nullptr;  // STEP1 records of sdso_track_make_ref_from_window, per reference slot
+  sdso::MapState* map = nullptr;        // the device-resident map: the point lists of every keyframe (sdso_map_*)
   std::shared_ptr<sdso::Comm> comm;     // shared with the contexts joined by sdso_comm_attach
   // generic scratch
   void* scratch = nullptr;
@@ -314,6 +316,10 @@ int track_make_ref_dev(sdso_ctx* ctx, int ref_slot, int frame_slot, int n, const
 // call has ended on it and nothing has edited it since, it is outside a batch and none of its residuals is linearised
 struct BaRefView { const BaDev* dev; int nf, np, nr, w, h, last_frame_slot; float K[4]; };
 int ba_ref_view(sdso_ctx* ctx, int win, BaRefView* out);
+// the frames of a window as the map keys them (map.hip): frameID of every frame, and the points of host h: [host_pt_beg[h], host_pt_beg[h + 1])
+int ba_window_hosts(sdso_ctx* ctx, int win, int frameID[8], int host_pt_beg[9]);
+// the current blob of an immature group (imm_layout.h) with its count resolved; *f = nullptr without such a group (imm_set.hip)
+int imm_host_view(sdso_ctx* ctx, int host_id, const float** f, int* n, int* cap);
 
 // ------------------------------------------------------------------ device helpers
 // getInterpolatedElement33 (src/util/globalFuncs.h:73-86) on the float4 image.

@@ -102,6 +102,7 @@ struct FrameHessian {
   float frameEnergyTH = 0, ab_exposure = 1;                         // :116-117
   bool flaggedForMarginalization = false;                           // :119
   std::vector<PointHessian*> pointHessians;                         // :121
+  std::vector<PointHessian*> pointHessiansMarginalized, pointHessiansOut;   // :122-123
   std::vector<ImmaturePoint*> immaturePoints;                       // :125
   SE3 worldToCam_evalPT;                                            // :132
   Vec10 state_zero, state, step;                                    // :135-138

@@ -147,6 +147,21 @@ def make_flag_points(frame_marg, last_gone=None, minGoodActiveResForMarg=3, minG
     return F, keep
 
 
+class MapUpdate(C.Structure):
+    """sdso_map_update_t: the orders of a keyframe's point lists (window point indices)."""
+    _fields_ = [("n_active", C.c_int), ("active", c_int_p), ("n_gone", C.c_int), ("gone", c_int_p), ("gone_list", c_u8_p)]
+
+
+class MapCloud(C.Structure):
+    """sdso_map_cloud_t: KeyFrameDisplay::refreshPC for up to 8 keyframes."""
+    _fields_ = [("n_frames", C.c_int), ("frameID", c_int_p), ("imm_host_id", c_int_p), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("scaledTH", C.c_float), ("absTH", C.c_float), ("minBS", C.c_float), ("mode", C.c_int), ("camToWorld", c_float_p),
+                ("cap", C.c_int)]
+
+
+MAP_REC_FLOATS = 16          # u, v, idepth, idepth_hessian, maxRelBaseline, color[8], padding (csrc/map_cloud.h)
+
+
 class TracePoints(C.Structure):
     _fields_ = [("n", C.c_int), ("u_stereo", c_float_p), ("v_stereo", c_float_p), ("idepth_min", c_float_p),
                 ("idepth_min_stereo", c_float_p), ("idepth_max_stereo", c_float_p), ("idepth_stereo", c_float_p),
@@ -537,6 +552,14 @@ def load():
     L.sdso_track_depth_image.argtypes = [vp, C.c_int, C.c_int, c_float_p, c_float_p, c_u8_p, c_float_p, c_int_p]
     L.sdso_track_depth_image_dev.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), c_int_p, c_int_p]
     L.sdso_imm_activate_fetch.argtypes = [vp, C.POINTER(ImmActivated), c_u8_p]
+    L.sdso_map_update.argtypes = [vp, C.c_int, C.POINTER(MapUpdate)]
+    L.sdso_map_counts.argtypes = [vp, C.c_int, c_int_p]
+    L.sdso_map_get.argtypes = [vp, C.c_int, C.c_int, c_float_p]
+    L.sdso_map_put.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_float_p]
+    L.sdso_map_release_keyframe.argtypes = [vp, C.c_int]
+    L.sdso_map_clear.argtypes = [vp]
+    L.sdso_map_cloud.argtypes = [vp, C.POINTER(MapCloud), c_float_p, c_u8_p, c_int_p, c_int_p]
+    L.sdso_map_cloud_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), c_int_p]
     _lib = L
     return L
 
@@ -569,6 +592,8 @@ EXPORTED_SYMBOLS = [
     "sdso_track_make_ref_from_window", "sdso_track_get_ref_points",
     "sdso_ba_flag_points",
     "sdso_track_keep_depth_map", "sdso_track_depth_image", "sdso_track_depth_image_dev",
+    "sdso_map_update", "sdso_map_counts", "sdso_map_get", "sdso_map_put", "sdso_map_release_keyframe", "sdso_map_clear",
+    "sdso_map_cloud", "sdso_map_cloud_dev",
 ]
 
 
@@ -754,6 +779,75 @@ class Context:
         a, b, w, h = C.c_void_p(), C.c_void_p(), C.c_int(0), C.c_int(0)
         self.check(self.L.sdso_track_depth_image_dev(self.h, ref_slot, C.byref(a), C.byref(b), C.byref(w), C.byref(h)))
         return a.value, b.value, w.value, h.value
+
+    def map_update_raw(self, wid, active, gone, gone_list):
+        """sdso_map_update without the check -> return code.  active: window point indices or None (every point not in gone)."""
+        U = MapUpdate()
+        a = None if active is None else np.ascontiguousarray(active, np.int32)
+        g, gl = np.ascontiguousarray(gone, np.int32), np.ascontiguousarray(gone_list, np.uint8)
+        U.n_active = 0 if a is None else len(a)
+        U.active = None if a is None else ip(a)
+        U.n_gone = len(g); U.gone = ip(g); U.gone_list = bp(gl)
+        return self.L.sdso_map_update(self.h, wid, C.byref(U))
+
+    def map_update(self, wid, active, gone, gone_list):
+        self.check(self.map_update_raw(wid, active, gone, gone_list))
+
+    def map_counts(self, frame_id):
+        """sdso_map_counts -> [active, marginalised, out]"""
+        c = np.full(3, -1, np.int32)
+        self.check(self.L.sdso_map_counts(self.h, frame_id, ip(c)))
+        return c
+
+    def map_get(self, frame_id, lst):
+        """sdso_map_get -> records [n, 16] of list 1 (active), 2 (marginalised) or 3 (out)"""
+        n = int(self.map_counts(frame_id)[lst - 1])
+        r = np.full((n, MAP_REC_FLOATS), -9, np.float32)
+        self.check(self.L.sdso_map_get(self.h, frame_id, lst, fp(r)))
+        return r
+
+    def map_put(self, frame_id, lst, records):
+        r = np.ascontiguousarray(records, np.float32).reshape(-1, MAP_REC_FLOATS)
+        self.check(self.L.sdso_map_put(self.h, frame_id, lst, len(r), fp(r)))
+
+    def map_cloud_raw(self, frame_ids, K4, scaledTH=0.001, absTH=0.001, minBS=0.1, mode=1, imm_host_id=None, camToWorld=None, cap=None, bound=None):
+        """sdso_map_cloud without the check -> (return code, dict: xyz [cap, 3], rgb [cap, 3] (untouched past n), first, kept [n_frames, 4], n).
+        cap defaults to the bound 8 x the sum of the list sizes."""
+        nfr = len(frame_ids)
+        fid = np.ascontiguousarray(frame_ids, np.int32)
+        imm = None if imm_host_id is None else np.ascontiguousarray(imm_host_id, np.int32)
+        if cap is None:
+            cap = 0
+            for k in range(nfr):
+                cap += 8 * int(self.map_counts(int(fid[k])).sum())
+                if imm is not None and imm[k] >= 0:
+                    n = C.c_int(0)
+                    self.check(self.L.sdso_imm_count(self.h, int(imm[k]), C.byref(n)))
+                    cap += 8 * n.value
+        T = None if camToWorld is None else np.ascontiguousarray(camToWorld, np.float32)
+        Q = MapCloud()
+        Q.n_frames = nfr; Q.frameID = ip(fid); Q.imm_host_id = None if imm is None else ip(imm)
+        Q.fx, Q.fy, Q.cx, Q.cy = [float(x) for x in K4]
+        Q.scaledTH, Q.absTH, Q.minBS, Q.mode = scaledTH, absTH, minBS, mode
+        Q.camToWorld = None if T is None else fp(T)
+        Q.cap = cap
+        d = dict(xyz=np.full((max(cap, 1), 3), -77, np.float32), rgb=np.full((max(cap, 1), 3), 77, np.uint8), first=np.full(nfr + 1, -1, np.int32),
+                 kept=np.full((nfr, 4), -1, np.int32))
+        rc = self.L.sdso_map_cloud(self.h, C.byref(Q), fp(d["xyz"]), bp(d["rgb"]), ip(d["first"]), ip(d["kept"]))
+        d["n"] = int(d["first"][nfr])
+        return rc, d
+
+    def map_cloud(self, frame_ids, K4, **kw):
+        """sdso_map_cloud -> the dict of map_cloud_raw"""
+        rc, d = self.map_cloud_raw(frame_ids, K4, **kw)
+        self.check(rc)
+        return d
+
+    def map_cloud_dev(self):
+        """sdso_map_cloud_dev -> (xyz device pointer, rgb device pointer, n)"""
+        a, b, n = C.c_void_p(), C.c_void_p(), C.c_int(0)
+        self.check(self.L.sdso_map_cloud_dev(self.h, C.byref(a), C.byref(b), C.byref(n)))
+        return a.value, b.value, n.value
 
     def read_device(self, ptr, nbytes):
         """nbytes at a device pointer of this context, after its stream has drained (hipMemcpy through the HIP runtime the library uses)"""
