@@ -851,6 +851,72 @@ typedef struct {
 int sdso_stereo_match_batch(sdso_ctx* ctx, int slot_a, int slot_b, const float K[4], float baseline,
                             int mode_right_first, sdso_stereo_match_t* m);
 
+/* ------------------------------------------------------------------ the stereo initialiser
+ * The start of a sequence: the live part of CoarseInitializer::setFirstStereo (src/FullSystem/CoarseInitializer.cpp:838-1034, called at
+ * FullSystem.cpp:1092-1093) and STEP 3 of FullSystem::initializeFromInitializer (FullSystem.cpp:1487-1597, called from trackNewCoarse at
+ * :309).  One initialiser state per ctx, with buffers of its own: no other entry point reads or writes them, and these calls touch
+ * neither the resident immature set nor the batches of the other stereo entry points.
+ * Not built, because nothing live reads it: levels >= 1 (makePixelStatus and the idepth[lvl] sums, CoarseInitializer.cpp:975-1013), makeNN
+ * (:1249), dGrads, setFirst, trackFrame and calcResAndGS.  Their only reader is the monocular trackFrame, which this fork never calls;
+ * the uses outside the class (FullSystem.cpp:1092-1093 and :1498-1576) touch points[0] / numPoints[0] only.
+ *
+ * sdso_init_set_first_stereo = setFirstStereo, level 0 (CoarseInitializer.cpp:842-972).  For y in [3, h-4), x in [3, w-4) in raster order
+ * every pixel with map != 0 becomes one Pnt: ImmaturePoint(x, y, firstFrame, map[i]) (ImmaturePoint.cpp:33-62) with u_stereo = u,
+ * v_stereo = v, idepth_min_stereo = 0, idepth_max_stereo = NaN, traced by traceStereo(right_slot, K, 1) (:897-903) in the ctx's refinement
+ * mode (sdso_trace_set_gn_mode).  IPS_GOOD: idepth = iR = idepth_stereo (:905-911); any other status: idepth = iR = 0.01f (:942-947);
+ * both branches: u = x, v = y, my_type = map[i].  isGood = true and outlierTH = patternNum * setting_outlierTH are the same for every
+ * Pnt and not stored.  Unlike makeNewTraces (sdso_imm_add_frame), a point whose energyTH is not finite is NOT dropped.  Such a point (a
+ * NaN among its colours) has no best search step, and the reference then refines around (0, 0), reading in front of the image; its
+ * status does not depend on what it reads (ImmaturePoint.cpp:413 holds for a NaN energyTH).  Here it takes no search and gets that
+ * status: IPS_OOB where the search line fails its tests (:118-238), IPS_OUTLIER otherwise; its interval stays 0 / NaN.  What the caller
+ * sets afterwards (:1027-1029: thisToNext = SE3(), snapped = false, frameID = snappedAt = 0) stays with the caller.
+ *   selection_map : w*h host floats, or NULL = PixelSelector::makeMaps(firstFrame, statusMap, 0.03f*w*h, 1, false, 2) with a fresh
+ *                   currentPotential of 3 (:848-871), run by the library on frame_slot as sdso_pixel_select does; that map then is "the
+ *                   map of the latest sdso_pixel_select" of this ctx
+ *   numPoints     : numPoints[0], the number of Pnts.  It can be smaller than makeMaps' return value: selected pixels in the excluded
+ *                   border are skipped
+ *   counts        : SDSO_INIT_NCOUNTS ints: [0] non-zero map entries (= makeMaps' return value when the library selected), [1]
+ *                   numPoints[0], [2..7] the histogram of the returned ImmaturePointStatus 0..5 over the Pnts
+ * Copies nothing up except a caller-supplied map.  With its own map the call reads the candidate count back once to size its launches
+ * (sdso_pixel_select synchronises as well); with a caller's map nothing is waited for unless counts is given, which copies the counts
+ * back: numPoints == NULL and counts == NULL only enqueue.  The call replaces an earlier state of this ctx.  A map with no entry in the
+ * walked area is not an error: the counts are 0 and n = 0.
+ * Refused before any device work, an earlier state left as it was: SDSO_ERR_ARG for an unknown frame_slot or right_slot, a right pyramid
+ * of another size, K == NULL, an image under 16 x 16, or selection_map == NULL on a frame without pyramid levels 0..2; SDSO_ERR_STATE
+ * when selection_map == NULL and no sdso_pixel_select state can be made on frame_slot (an image smaller than one 32 x 32 cell).
+ *
+ * sdso_init_get_pnts: the Pnt members in points[0] order, one copy; null members are skipped; out->n is set.
+ *
+ * sdso_init_from_initializer = initializeFromInitializer STEP 3 (FullSystem.cpp:1533-1573) on the kept state.  For every Pnt i in order:
+ *   keep[i] == 0: `rand()/(float)RAND_MAX > keepPercentage` held (:1535; the draws belong to the caller's process); NULL = no Pnt skipped
+ *   ImmaturePoint(point->u+0.5f, point->v+0.5f, firstFrame, point->my_type, &Hcalib) (:1538: the (int u_, int v_, ...) constructor,
+ *   ImmaturePoint.cpp:33, so the pixel is (x, y) again), the interval 0 / NaN, traceStereo(firstFrameRight, K, 1) (:1540-1545): the same
+ *   inputs, pixel and interval as in setFirstStereo and a deterministic trace, so the device keeps the first trace's color, weights,
+ *   energyTH, idepth_min_stereo, idepth_max_stereo, idepth_stereo and status per Pnt and does not trace again
+ *   dropped if !isfinite(energyTH) || !isfinite(idepth_min) || !isfinite(idepth_max) || idepth_min < 0 || idepth_max < 0 (:1552-1559).
+ *   Every survivor is IPS_GOOD: all other exits of traceStereo leave idepth_max_stereo NaN, except ImmaturePoint.cpp:440-443 (OUTLIER with
+ *   idepth_max_stereo < 0)
+ *   PointHessian(pt) copies u v my_type color[8] weights[8] energyTH (HessianBlocks.cpp:35-68; maxRelBaseline, numGoodResiduals and
+ *   idepth_hessian are 0); setIdepthScaled(idepth_stereo), setIdepthZero(idepth_stereo), hasDepthPrior = true, ACTIVE (:1565-1568)
+ *   counts (4 ints, may be NULL): [0] Pnts walked, [1] skipped by keep, [2] dropped by :1552-1559, [3] points made
+ * Copies the flags up and the counts back; n_points == NULL and counts == NULL only enqueue.  Does not change the Pnt state: the call is
+ * repeatable with other flags, and sdso_init_get_pnts returns the same bytes before and after.
+ *
+ * sdso_init_get_points: firstFrame->pointHessians of the latest sdso_init_from_initializer in push order, one copy; null members are
+ * skipped; out->n is set.  pnt = the index into points[0]; idepth = idepth_scaled = idepth_zero; idepth_min / idepth_max are the
+ * ImmaturePoint's (:1547-1548), which PointHessian does not keep.
+ * SDSO_ERR_STATE: sdso_init_from_initializer / sdso_init_get_* before a sdso_init_set_first_stereo (or after sdso_init_release), and
+ * sdso_init_get_points before a sdso_init_from_initializer on the current state. */
+#define SDSO_INIT_NCOUNTS 8
+int sdso_init_set_first_stereo(sdso_ctx* ctx, int frame_slot, int right_slot, const float K[4], float baseline,
+                               const float* selection_map, int* numPoints, int* counts);
+typedef struct { int n; float *u, *v, *idepth, *iR, *my_type; uint8_t* status; } sdso_init_pnts_t;
+int sdso_init_get_pnts(sdso_ctx* ctx, sdso_init_pnts_t* out);
+int sdso_init_from_initializer(sdso_ctx* ctx, const uint8_t* keep, int* n_points, int* counts);
+typedef struct { int n; int* pnt; float *u, *v, *my_type, *idepth, *idepth_min, *idepth_max, *energyTH, *color /* n*8 */, *weights /* n*8 */; } sdso_init_points_t;
+int sdso_init_get_points(sdso_ctx* ctx, sdso_init_points_t* out);
+int sdso_init_release(sdso_ctx* ctx);
+
 /* ------------------------------------------------------------------ the device-resident immature points
  * One set per ctx: the ImmaturePoint objects of every keyframe of the window (host->immaturePoints, HessianBlocks.h), grouped by a
  * caller-chosen host_id, each group in the order of the reference's vector.  Stored per point, exactly the members the reference carries

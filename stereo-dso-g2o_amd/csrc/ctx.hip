@@ -148,6 +148,7 @@ void release_g2o(sdso_ctx* ctx);
 void release_distmap(sdso_ctx* ctx);
 void release_ingest(sdso_ctx* ctx);
 void release_immature(sdso_ctx* ctx);
+void release_init_stereo(sdso_ctx* ctx);
 void release_comm(sdso_ctx* ctx);
 void release_refwin(sdso_ctx* ctx);
 void release_map(sdso_ctx* ctx);
@@ -171,6 +172,7 @@ extern "C" void sdso_ctx_destroy(sdso_ctx* ctx) {
   release_distmap(ctx);
   release_ingest(ctx);
   release_immature(ctx);
+  release_init_stereo(ctx);
   release_refwin(ctx);
   release_map(ctx);
   release_comm(ctx);

@@ -77,6 +77,7 @@ struct G2oState;     // g2o_factors.hip
 struct DistMapState; // distmap.hip
 struct IngestState;  // ingest.hip
 struct ImmState;     // imm_set.hip (a part of stereo.hip)
+struct InitState;    // init_stereo.hip (a part of stereo.hip)
 struct Comm;         // comm.hip
 struct RefWinState;  // ref_window.hip
 struct BaDev;        // ba_kernels.h
@@ -100,6 +101,7 @@ struct sdso_ctx {
   sdso::DistMapState* dm = nullptr;     // the level-1 CoarseDistanceMap
   sdso::IngestState* ingest = nullptr;  // calibration tables and raw-image staging of sdso_ingest_frame
   sdso::ImmState* imm = nullptr;        // the device-resident immature points, per host keyframe (sdso_imm_*)
+  sdso::InitState* init = nullptr;      // the stereo initialiser: the Pnts of setFirstStereo and what STEP 3 reads of them (sdso_init_*)
   sdso::RefWinState* refwin = nullptr;  // STEP1 records of sdso_track_make_ref_from_window, per reference slot
   sdso::MapState* map = nullptr;        // the device-resident map: the point lists of every keyframe (sdso_map_*)
   std::shared_ptr<sdso::Comm> comm;     // shared with the contexts joined by sdso_comm_attach

@@ -12,6 +12,8 @@
 //   src/FullSystem/FullSystem.cpp:581-613     stereoMatch's loop (sdso_imm_stereo_match)
 //   src/FullSystem/FullSystem.cpp:948-957     activatePointsMT STEP 5
 //   src/FullSystem/FullSystem.cpp:837-957     activatePointsMT STEP 2-5 in place (sdso_imm_activate)
+//   src/FullSystem/CoarseInitializer.cpp:838-972   setFirstStereo, level 0 (sdso_init_set_first_stereo)
+//   src/FullSystem/FullSystem.cpp:1533-1573   initializeFromInitializer STEP 3 (sdso_init_from_initializer)
 //
 // One translation unit in parts: they share static helpers and __forceinline__ device code (trace_on_point, activate_point), which
 // separate objects would duplicate.  Per-point arithmetic keeps the reference's operation order (no FP contraction) => statuses, bestIdx
@@ -29,12 +31,14 @@
 //   imm_trace.hip     sdso_imm_trace: traceOn in place and the stereo chain of the non-key trace
 //   imm_match.hip     sdso_imm_stereo_match: stereoMatch's loop on a group of the set, its kept results and dense map
 //   imm_activate.hip  sdso_imm_activate: activatePointsMT STEP 2-5 on the set
+//   init_stereo.hip   sdso_init_*: the live part of CoarseInitializer::setFirstStereo and STEP 3 of initializeFromInitializer
 #include "sdso_internal.h"
 #include "distmap_dev.h"
 #include "trace_dev.h"
 #include "imm_layout.h"
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 
 using namespace sdso;
 
@@ -47,3 +51,4 @@ using namespace sdso;
 #include "imm_trace.hip"
 #include "imm_match.hip"
 #include "imm_activate.hip"
+#include "init_stereo.hip"

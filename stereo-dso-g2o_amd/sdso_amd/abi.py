@@ -179,6 +179,20 @@ class ImmGeom(C.Structure):
     _fields_ = [("host_id", C.c_int), ("KRKi", C.c_float * 9), ("Kt", C.c_float * 3), ("aff", C.c_float * 2), ("KRi", C.c_float * 9), ("t", C.c_float * 3)]
 
 
+INIT_NCOUNTS = 8   # non-zero map entries, numPoints[0], the histogram of the returned ImmaturePointStatus 0..5 over the Pnts
+
+
+class InitPnts(C.Structure):
+    """sdso_init_pnts_t: the Pnt members of CoarseInitializer::points[0] (CoarseInitializer.cpp:905-969)."""
+    _fields_ = [("n", C.c_int), ("u", c_float_p), ("v", c_float_p), ("idepth", c_float_p), ("iR", c_float_p), ("my_type", c_float_p), ("status", c_u8_p)]
+
+
+class InitPoints(C.Structure):
+    """sdso_init_points_t: firstFrame->pointHessians after initializeFromInitializer STEP 3 (FullSystem.cpp:1533-1573)."""
+    _fields_ = [("n", C.c_int), ("pnt", c_int_p), ("u", c_float_p), ("v", c_float_p), ("my_type", c_float_p), ("idepth", c_float_p), ("idepth_min", c_float_p),
+                ("idepth_max", c_float_p), ("energyTH", c_float_p), ("color", c_float_p), ("weights", c_float_p)]
+
+
 IMM_MAX_HOSTS = 8
 IMM_NCOUNTS = 10   # lastTraceStatus histogram [0..5], forward GOOD, stereo outliers, intervals updated, unreadable
 
@@ -536,6 +550,11 @@ def load():
     L.sdso_ingest_calib_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, C.c_int, c_float_p, c_float_p, C.c_int, C.c_int]
     L.sdso_ingest_calib_release.argtypes = [vp, C.c_int]
     L.sdso_ingest_frame.argtypes = [vp, C.c_int, C.c_int, c_int_p, C.POINTER(vp), c_float_p, C.c_float, c_float_p]
+    L.sdso_init_set_first_stereo.argtypes = [vp, C.c_int, C.c_int, c_float_p, C.c_float, c_float_p, c_int_p, c_int_p]
+    L.sdso_init_get_pnts.argtypes = [vp, C.POINTER(InitPnts)]
+    L.sdso_init_from_initializer.argtypes = [vp, c_u8_p, c_int_p, c_int_p]
+    L.sdso_init_get_points.argtypes = [vp, C.POINTER(InitPoints)]
+    L.sdso_init_release.argtypes = [vp]
     L.sdso_imm_add_frame.argtypes = [vp, C.c_int, C.c_int, c_float_p, c_int_p]
     L.sdso_imm_trace.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(ImmGeom), c_float_p, c_float_p, C.c_float, c_int_p]
     L.sdso_imm_count.argtypes = [vp, C.c_int, c_int_p]
@@ -586,6 +605,7 @@ EXPORTED_SYMBOLS = [
     "sdso_g2o_track_add_edges", "sdso_g2o_track_linearize", "sdso_g2o_track_newest_coarse", "sdso_g2o_lba_eval", "sdso_trace_set_gn_mode",
     "sdso_distmap_make", "sdso_distmap_add", "sdso_distmap_get", "sdso_activate_select",
     "sdso_undistort_make_remap", "sdso_ingest_calib_create", "sdso_ingest_calib_release", "sdso_ingest_frame",
+    "sdso_init_set_first_stereo", "sdso_init_get_pnts", "sdso_init_from_initializer", "sdso_init_get_points", "sdso_init_release",
     "sdso_imm_add_frame", "sdso_imm_trace", "sdso_imm_count", "sdso_imm_get", "sdso_imm_remove_order", "sdso_imm_remove", "sdso_imm_release_host",
     "sdso_imm_put_host", "sdso_imm_activate", "sdso_imm_activate_fetch",
     "sdso_imm_stereo_match", "sdso_imm_stereo_match_fetch", "sdso_imm_stereo_map_dev",
@@ -640,6 +660,49 @@ class Context:
         out = np.zeros(n, np.float32)
         self.check(self.L.sdso_ingest_frame(self.h, calib, n, (C.c_int * n)(*slots), ptrs, fp(ex), factor, fp(out)))
         return out
+
+    def init_set_first_stereo(self, frame_slot, right_slot, K4, baseline, selection_map=None, read=True):
+        """sdso_init_set_first_stereo -> (numPoints[0], counts); read=False: the enqueue-only form -> (None, None)."""
+        K = np.ascontiguousarray(K4, np.float32)
+        m = None if selection_map is None else np.ascontiguousarray(selection_map, np.float32)
+        n = C.c_int(-1)
+        counts = np.full(INIT_NCOUNTS, -1, np.int32)
+        self.check(self.L.sdso_init_set_first_stereo(self.h, frame_slot, right_slot, fp(K), baseline, None if m is None else fp(m),
+                                                     C.byref(n) if read else None, ip(counts) if read else None))
+        return (n.value, counts) if read else (None, None)
+
+    def init_get_pnts(self, cap):
+        """sdso_init_get_pnts into arrays of cap entries -> dict of the Pnt members, cut to the n the library set."""
+        d = dict(u=np.full(cap, -1, np.float32), v=np.full(cap, -1, np.float32), idepth=np.full(cap, -1, np.float32), iR=np.full(cap, -1, np.float32),
+                 my_type=np.full(cap, -1, np.float32), status=np.full(cap, 254, np.uint8))
+        P = InitPnts()
+        P.n = -1
+        for k, a in d.items():
+            setattr(P, k, bp(a) if a.dtype == np.uint8 else fp(a))
+        self.check(self.L.sdso_init_get_pnts(self.h, C.byref(P)))
+        assert 0 <= P.n <= cap
+        return {k: a[:P.n] for k, a in d.items()}
+
+    def init_from_initializer(self, keep=None, read=True):
+        """sdso_init_from_initializer -> (points made, counts); read=False: the enqueue-only form -> (None, None)."""
+        k = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+        n = C.c_int(-1)
+        counts = np.full(4, -1, np.int32)
+        self.check(self.L.sdso_init_from_initializer(self.h, None if k is None else bp(k), C.byref(n) if read else None, ip(counts) if read else None))
+        return (n.value, counts) if read else (None, None)
+
+    def init_get_points(self, cap):
+        """sdso_init_get_points into arrays of cap entries -> dict of the PointHessian records, cut to the n the library set."""
+        d = dict(pnt=np.full(cap, -1, np.int32))
+        d.update({k: np.full(cap, -1, np.float32) for k in ("u", "v", "my_type", "idepth", "idepth_min", "idepth_max", "energyTH")})
+        d.update(color=np.full((cap, 8), -1, np.float32), weights=np.full((cap, 8), -1, np.float32))
+        P = InitPoints()
+        P.n = -1
+        for k, a in d.items():
+            setattr(P, k, ip(a) if a.dtype == np.int32 else fp(a))
+        self.check(self.L.sdso_init_get_points(self.h, C.byref(P)))
+        assert 0 <= P.n <= cap
+        return {k: a[:P.n] for k, a in d.items()}
 
     def imm_get(self, host_id):
         """sdso_imm_get: one host's immature points as a dict of numpy arrays (the members of ImmaturePoint, in the set's order)."""
