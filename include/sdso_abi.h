@@ -597,6 +597,35 @@ int sdso_ba_window_plan(int nf, int np, int nr, const int* host, const int* res_
  * touches points that leave), a frame removal without the matching sdso_ba_marginalize_frame_dev calls, and an edit that removes no
  * frame after sdso_ba_marginalize_frame_dev has run (its prior would be lost). */
 int sdso_ba_window_update(sdso_ctx* ctx, int win, const sdso_ba_window_edit_t* E);
+/* sdso_ba_window_update with stage 7 taken from the latest sdso_imm_activate of this ctx, device to device: the tail of
+ * optimizeImmaturePoint (FullSystemOptPoint.cpp:196-237) and STEP 4 of activatePointsMT (FullSystem.cpp:919-945) on the resident window.
+ * Stages 1-6 of E are as above; stage 7 of E must be empty (n_add_points == n_pt_res == 0, else SDSO_ERR_ARG).
+ *   appended points : toOptimize is walked in order; every entry with status 1 is one point, in that order (FullSystem.cpp:923-928
+ *                     `newpoint != 0 && newpoint != -1`; the non-finite energyTH of FullSystemOptPoint.cpp:199-202 is already status -1)
+ *       host                 act_frame[rec.frame]                      (HessianBlocks.cpp:37 `host = rawPoint->host`)
+ *       u, v, colour, weights   the record's                           (HessianBlocks.cpp:45-46, :60-61)
+ *       idepth, idepth_zero  both rec.idepth                           (FullSystemOptPoint.cpp:208-209 setIdepthZero / setIdepth(currentIdepth))
+ *       hasDepthPrior, maxRelBaseline, numGoodResiduals   0            (HessianBlocks.cpp:38, :41-42)
+ *   their residuals : for f = 0 .. nf_act-1 in the activation's frame order, rec.res_state[f] == IN is one residual with target
+ *                     act_frame[f], state IN, isNew 1 (FullSystemOptPoint.cpp:213-219; FullSystem.cpp:931-932 inserts them in that order;
+ *                     the host's own entry is 255 and gives none)
+ *   act_frame       : nf of the activation entries, the window frame of every activation frame in the edit's convention: an index of the
+ *                     window before the call, nf_before + k for the k-th appended frame.  The appended residuals follow stage 6's in
+ *                     res_src, as stage 7's do in sdso_ba_window_update.
+ *   n_points, n_res : the numbers appended (each may be NULL)
+ *   act_index       : act_index[k] = the toOptimize index of the k-th appended point (may be NULL; size it for counts[4] of the activation)
+ * The host reads the integer members of the records (frame, status, res_state), plans the edit as sdso_ba_window_plan does and stages the
+ * integers; the float rows of the appended points are filled from the records on the device.  No float of an activated point is read
+ * from or written to host memory.  Enqueue only.  sdso_ba_window_get_order works as after any update.
+ * Refused before any device work, the window, the set and the records left as they were:
+ *   SDSO_ERR_STATE  no sdso_imm_activate on this ctx yet; its result was already taken by an earlier successful call of this function
+ *                   (every sdso_imm_activate makes a fresh one); everything sdso_ba_window_update refuses with this code
+ *   SDSO_ERR_ARG    null act_frame; an entry out of range of the edited window or naming a frame that leaves in stage 4; two activation
+ *                   frames mapped to one window frame; the activation's w x h other than the window's; everything sdso_ba_window_plan
+ *                   refuses
+ * A call with no activated point is a plain update; it consumes the (empty) result all the same. */
+int sdso_ba_window_update_activated(sdso_ctx* ctx, int win, const sdso_ba_window_edit_t* E, const int* act_frame,
+                                    int* n_points, int* n_res, int* act_index);
 /* The maps of the latest sdso_ba_window_update of this window (sizes: its current nf / np / nr; each may be NULL); SDSO_ERR_STATE when
  * the window has not been updated since its upload. */
 int sdso_ba_window_get_order(sdso_ctx* ctx, int win, int* frame_src, int* point_src, int* res_src);
@@ -803,6 +832,15 @@ int sdso_activate_points_batch(sdso_ctx* ctx, const sdso_activate_t* A, int8_t* 
 typedef struct { float KRKi[9]; float Kt[3]; } sdso_distmap_geom_t;
 int sdso_distmap_make(sdso_ctx* ctx, int w, int h, int ngeom, const sdso_distmap_geom_t* geom, int n, const int* point_geom,
                       const float* u, const float* v, const float* idepth_scaled, int* n_seeds);
+/* sdso_distmap_make on the points of the device-resident BA window `win`, read where they lie: point p of host frame f is projected with
+ * geom[f], its u, v and its current idepth — the value sdso_ba_get_state returns (idepth_scaled, SCALE_IDEPTH = 1).
+ *   geom : one entry per frame of the window (fhToNew of :1235-1236); skip : nf flags or NULL — the points of a frame with skip[f] != 0
+ *          contribute nothing (`if (fh == frame) continue`, CoarseTracker.cpp:1232, when the newest frame is already in the window)
+ * The window's own point order stands in for "the reference's loop order": every seed stores the same 0 and numItems only counts them, so
+ * the map does not depend on the order of the points (and the window keeps the reference's order anyway, makeIDX).
+ * Only geom and skip travel to the device.  With n_seeds == NULL the call does not synchronise.
+ * SDSO_ERR_ARG, decided before any device work (the previous map stays valid): an unknown window, w / h other than the window's, null geom. */
+int sdso_distmap_make_from_window(sdso_ctx* ctx, int win, int w, int h, const sdso_distmap_geom_t* geom, const uint8_t* skip, int* n_seeds);
 int sdso_distmap_add(sdso_ctx* ctx, int n, const int* iu, const int* iv);
 int sdso_distmap_get(sdso_ctx* ctx, float* map /* w1*h1 */);
 
@@ -1073,6 +1111,8 @@ typedef struct {
 int sdso_imm_activate(sdso_ctx* ctx, const sdso_imm_activate_t* A, int* counts);
 
 /* The results of the latest sdso_imm_activate of this ctx, kept by the library until the next one (SDSO_ERR_STATE before the first).
+ * The records are also kept on the device, in a buffer of the set that no other call writes, with the w x h of the call and a
+ * "consumed" flag that every sdso_imm_activate clears: sdso_ba_window_update_activated reads them there.
  * One entry per selected candidate in toOptimize order, n = counts[4]; arrays are caller-owned, null members are skipped, out->n and
  * out->nf are set.
  *   frame, index : the candidate's frame and idxInImmaturePoints, its index in the group BEFORE the removal

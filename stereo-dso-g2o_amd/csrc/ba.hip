@@ -10,7 +10,7 @@
 //   ba_marg.hip    sdso_ba_marginalize_points / _frame / _frame_dev, sdso_ba_adopt_prior
 //   ba_batch.hip   the batch's lifetime, its sdso_ba_batch_* phase calls, the accumulator blocks comm.hip reduces
 //   ba_loop.hip    both Gauss-Newton loops: the resident one (single window and batch) and the host loop of sdso_ba_optimize
-//   ba_update.hip  sdso_ba_window_plan / _update / _get_order
+//   ba_update.hip  sdso_ba_window_plan / _update / _update_activated / _get_order
 //   ba_flag.hip    sdso_ba_flag_points: removeOutliers / flagPointsForRemoval on the resident window (the rule itself: ba_flag.h)
 // Forward declarations cross the files only where two of them need each other: free_batch / free_optrun / free_optbufs (a window's
 // release ends the batch, the batch's end ends its loop) and launch_window_gather (the upload is the builder of an updated window).
@@ -29,6 +29,7 @@
 #include <atomic>
 #include <thread>
 #include <string>
+#include "imm_layout.h"          // ImmActRec: what sdso_ba_window_update_activated reads of an activation
 #include "ba_layout.h"
 #include "ba_window.hip"
 #include "ba_launch.hip"

@@ -1,6 +1,6 @@
 // BA host API, part 3 (included by ba.hip): the per-window step calls (FullSystem::linearizeAll, EnergyFunctional::accumulate*,
 // solveSystemF, resubstituteF, calc*Energy) and the getters, sdso_ba_linearize ... sdso_ba_get_deltas, sdso_ba_get_state,
-// sdso_ba_get_post_state, sdso_ba_get_counts, ba_ref_view.
+// sdso_ba_get_post_state, sdso_ba_get_counts, ba_ref_view, ba_window_points.
 extern "C" int sdso_ba_accum_floats(int nf) { return (int)acc_floats(nf); }
 
 namespace sdso {
@@ -612,6 +612,13 @@ int ba_window_hosts(sdso_ctx* ctx, int win, int frameID[8], int host_pt_beg[9]) 
   if (!W) return sdso::fail(ctx, SDSO_ERR_ARG, "unknown window");
   for (int f = 0; f < 8; f++) frameID[f] = f < W->d.nf ? W->frames[f].frameID : -1;
   std::memcpy(host_pt_beg, W->d.host_pt_beg, sizeof(W->d.host_pt_beg));
+  return SDSO_OK;
+}
+int ba_window_points(sdso_ctx* ctx, int win, BaPointsView* out) {
+  BaWindowDev* W = find_win(ctx, win);
+  if (!W) return sdso::fail(ctx, SDSO_ERR_ARG, "unknown window");
+  out->p_geo = W->d.p_geo; out->p_host = W->d.p_host;
+  out->nf = W->d.nf; out->np = W->d.np; out->w = W->d.w; out->h = W->d.h;
   return SDSO_OK;
 }
 }  // namespace sdso

@@ -4,11 +4,13 @@
 //   build_window_layout  the range / order validations of an upload, the stable sort of the residuals by (host, target) pair, the
 //                        per-point tables and the work lists of the accumulate and Schur kernels (ba_window.hip stages them as they are)
 //   plan_window_edit     the integer list surgery of sdso_ba_window_update / sdso_ba_window_plan (ba_update.hip), O(np + nr)
+//   plan_activated_stage7  stage 7 of such an edit from the records of an activation (sdso_ba_window_update_activated): integers only
 #pragma once
 #include <algorithm>
 #include <cstdint>
 #include <vector>
 #include "../../include/sdso_abi.h"
+#include "imm_layout.h"   // ImmActRec (plain C++ as well)
 
 constexpr int BA_LAYOUT_CHUNK = 256;   // residuals per accumulate workgroup: BA_CHUNK of ba_kernels.h (checked where the chunks are staged)
 constexpr int BA_LAYOUT_ITEM = 64;     // points per item of the Schur kernel (it deals 64-point slices to its waves)
@@ -267,6 +269,48 @@ static bool plan_window_edit(int nf, int np, int nr, const int* host, const int*
   }
   P.point_src.resize(p2); P.host.resize(p2); P.res_src.resize(r2); P.res_point.resize(r2); P.res_target.resize(r2);
   P.nf2 = nf2; P.np2 = (int)P.point_src.size(); P.nr2 = (int)P.res_src.size();
+  return true;
+#undef BAD
+}
+
+// Stage 7 of an edit from the records of sdso_imm_activate, by the tail of optimizeImmaturePoint (FullSystemOptPoint.cpp:196-237) and STEP 4
+// of activatePointsMT (FullSystem.cpp:919-945): walking toOptimize in order, every record with status 1 is one appended point on host
+// act_frame[rec.frame] (:923-928; the non-finite energyTH of :199-202 is already status -1), and for f = 0 .. nf_act-1 in frame order
+// res_state[f] == IN is one residual into act_frame[f], state IN (:213-219; the host's own entry is 255).  Reads the integer members
+// of the records only.  rec[k] = the toOptimize index of the k-th appended point.
+struct ActStage7 {
+  std::vector<int> pt_host, rec, res_point, res_target;
+  std::vector<uint8_t> res_state;
+};
+// nf: frames of the window before the edit E (whose stages 4 and 5 are read); act_frame: nf_act indices in the edit's numbering.  Returns
+// false with *why set for a map the call refuses: an entry outside [0, nf + n_add_frames), one that names a frame leaving in stage 4,
+// two entries naming one frame.  What the plan itself refuses is left to plan_window_edit.
+static bool plan_activated_stage7(int nf, const sdso_ba_window_edit_t& E, int nf_act, const int* act_frame, int n_rec, const sdso::ImmActRec* R, ActStage7& S,
+                                  const char** why) {
+#define BAD(cond, msg) do { if (!(cond)) { *why = (msg); return false; } } while (0)
+  BAD(nf >= 1 && nf <= 8 && E.n_add_frames >= 0 && E.n_add_frames <= 8 && nf_act >= 0 && nf_act <= 8, "window or activation sizes out of range");
+  const int nfa = nf + E.n_add_frames;
+  unsigned leaving = 0, named = 0;
+  if (E.remove_frames)
+    for (int i = 0; i < E.n_remove_frames; i++) if (E.remove_frames[i] >= 0 && E.remove_frames[i] < nf) leaving |= 1u << E.remove_frames[i];
+  for (int f = 0; f < nf_act; f++) {
+    const int t = act_frame[f];
+    BAD(t >= 0 && t < nfa, "act_frame: frame index out of range of the edited window");
+    BAD(!((leaving >> t) & 1u), "act_frame: names a frame that leaves in stage 4");
+    BAD(!((named >> t) & 1u), "act_frame: two activation frames mapped to one window frame");
+    named |= 1u << t;
+  }
+  S = ActStage7();
+  for (int p = 0; p < n_rec; p++) {
+    const sdso::ImmActRec& r = R[p];
+    if (r.status != 1) continue;
+    BAD(r.frame >= 0 && r.frame < nf_act, "activation record names a frame outside the activation");
+    const int q = (int)S.pt_host.size();
+    S.pt_host.push_back(act_frame[r.frame]);
+    S.rec.push_back(p);
+    for (int f = 0; f < nf_act; f++)
+      if (r.res_state[f] == 0) { S.res_point.push_back(q); S.res_target.push_back(act_frame[f]); S.res_state.push_back(0); }   // ResState::IN
+  }
   return true;
 #undef BAD
 }

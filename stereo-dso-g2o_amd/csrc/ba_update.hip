@@ -7,6 +7,10 @@
 //                      one (so the two cannot drift apart), staged in one copy together with the appended entries' payload
 //   k_ba_window_gather device: the surviving points' and residuals' rows, old slab -> new slab through the plan's maps
 //   k_ba_prior_adopt   device: HM / bM (or the chained prior of sdso_ba_marginalize_frame_dev) into the new dimension (ba_solve.hip)
+// sdso_ba_window_update_activated: the same edit with stage 7 taken from the latest sdso_imm_activate of the ctx — the tail of
+// optimizeImmaturePoint (FullSystemOptPoint.cpp:196-237) and STEP 4 of activatePointsMT (FullSystem.cpp:919-945).
+//   plan_activated_stage7  host (ba_layout.h): stage 7's integers from the records' integer members
+//   k_ba_window_fill_activated  device: the float rows of the points that came from a record, record -> new slab
 
 // Rows of the surviving points and residuals, old slab -> new slab.  One thread per 16-byte row: six rows per point (p_geo, p_track, two of
 // colour, two of weights), then one thread per residual for its two state bytes.  src < 0: the entry is new, its row came with the staged copy.
@@ -43,7 +47,34 @@ __global__ __launch_bounds__(BA_BLOCK) void k_ba_window_gather(const GatherArgs 
   }
 }
 
-static void launch_window_gather(sdso_ctx* ctx, const BaWindowDev* W, const WindowCarry& cy, const int* d_psrc, const int* d_rsrc) {
+// Rows of the points that sdso_ba_window_update_activated appended: record asrc[p] of the latest sdso_imm_activate -> point p of the new
+// slab (asrc < 0: not such a point).  One thread per 16-byte row, the six rows of k_ba_window_gather: what
+// PointHessian::PointHessian(const ImmaturePoint*, ...) copies (HessianBlocks.cpp:35-70) and setIdepthZero / setIdepth(currentIdepth)
+// (FullSystemOptPoint.cpp:208-209); maxRelBaseline = numGoodResiduals = 0 (HessianBlocks.cpp:41-42).
+struct FillActArgs {
+  const ImmActRec* rec; const int* asrc;
+  float4 *n_geo, *n_track, *n_color, *n_weights; float* n_delta; int np;
+};
+__global__ __launch_bounds__(BA_BLOCK) void k_ba_window_fill_activated(const FillActArgs a) {
+  const int t = blockIdx.x * BA_BLOCK + threadIdx.x;
+  if (t >= a.np * 6) return;
+  const int p = t / 6, k = t - p * 6, s = a.asrc[p];
+  if (s < 0) return;
+  const ImmActRec& r = a.rec[s];
+  if (k == 0) {
+    const float4 g = make_float4(r.u, r.v, r.idepth, r.idepth);
+    a.n_geo[p] = g;
+    a.n_delta[p] = g.z - g.w;                          // EFPoint::deltaF as the upload forms it from equal idepths (0, or NaN with them)
+  } else if (k == 1) {
+    a.n_track[p] = make_float4(0.f, 0.f, 0.f, 0.f);
+  } else if (k < 4) {
+    a.n_color[2 * p + (k - 2)] = ((const float4*)r.color)[k - 2];
+  } else {
+    a.n_weights[2 * p + (k - 4)] = ((const float4*)r.weights)[k - 4];
+  }
+}
+
+static void launch_window_gather(sdso_ctx* ctx, const BaWindowDev* W, const WindowCarry& cy, const int* d_psrc, const int* d_rsrc, const int* d_asrc) {
   const BaDev& o = cy.old->d;
   const BaDev& d = W->d;
   GatherArgs a;
@@ -56,6 +87,12 @@ static void launch_window_gather(sdso_ctx* ctx, const BaWindowDev* W, const Wind
   if (work > 0) {
     ProfScope ps(ctx, "k_ba_window_gather");
     hipLaunchKernelGGL(k_ba_window_gather, dim3((unsigned)((work + BA_BLOCK - 1) / BA_BLOCK)), dim3(BA_BLOCK), 0, ctx->stream, a);
+  }
+  if (d_asrc && d.np > 0) {
+    FillActArgs f;
+    f.rec = cy.act_dev; f.asrc = d_asrc; f.n_geo = a.n_geo; f.n_track = a.n_track; f.n_color = a.n_color; f.n_weights = a.n_weights; f.n_delta = a.n_delta; f.np = d.np;
+    ProfScope ps(ctx, "k_ba_window_fill_activated");
+    hipLaunchKernelGGL(k_ba_window_fill_activated, dim3((unsigned)(((long)d.np * 6 + BA_BLOCK - 1) / BA_BLOCK)), dim3(BA_BLOCK), 0, ctx->stream, f);
   }
   // HM / bM from the old window's (or from the chained prior of sdso_ba_marginalize_frame_dev): the leading prior_dim rows / columns, zeros for
   // the appended frames (insertFrame, EnergyFunctional.cpp:476-482)
@@ -76,7 +113,10 @@ extern "C" int sdso_ba_window_plan(int nf, int np, int nr, const int* host, cons
   return SDSO_OK;
 }
 
-static int window_update_impl(sdso_ctx* ctx, int win, BaWindowDev* O, const sdso_ba_window_edit_t& E, BaWindowDev** made) {
+// act_rec / act_dev: stage 7 of E came from plan_activated_stage7 — its k-th point is record act_rec[k] of act_dev, whose float rows the
+// device fills in (E's stage-7 float arrays are not read); nullptr: sdso_ba_window_update
+static int window_update_impl(sdso_ctx* ctx, int win, BaWindowDev* O, const sdso_ba_window_edit_t& E, BaWindowDev** made, const int* act_rec = nullptr,
+                              const ImmActRec* act_dev = nullptr) {
   const int nf = O->d.nf, np = O->d.np, nr = O->d.nr;
   if (O->in_batch) return sdso::fail(ctx, SDSO_ERR_STATE, "the window is a member of a batch: update it before sdso_ba_batch_create");
   // ---- the window's own order from its mirrors (h_point / h_target are pair-sorted; perm maps sorted -> window order)
@@ -88,13 +128,13 @@ static int window_update_impl(sdso_ctx* ctx, int win, BaWindowDev* O, const sdso
   const int nf2 = P.nf2, np2 = P.np2, nr2 = P.nr2;
   SDSO_REQUIRE(ctx, !E.n_add_frames || (E.evalPT && E.state && E.state_zero && E.ab_exposure && E.frameEnergyTH && E.frameID && E.frame_slot), "null stage-5 frame arrays");
   SDSO_REQUIRE(ctx, !E.n_add_res || E.add_res_state, "null stage-6 residual states");
-  SDSO_REQUIRE(ctx, !E.n_add_points || (E.pt_u && E.pt_v && E.pt_idepth && E.pt_idepth_zero && E.pt_color && E.pt_weights && E.pt_hasDepthPrior), "null stage-7 point arrays");
+  SDSO_REQUIRE(ctx, !E.n_add_points || act_rec || (E.pt_u && E.pt_v && E.pt_idepth && E.pt_idepth_zero && E.pt_color && E.pt_weights && E.pt_hasDepthPrior), "null stage-7 point arrays");
   SDSO_REQUIRE(ctx, !E.n_pt_res || E.pt_res_state, "null stage-7 residual states");
   for (int r = 0; r < nr2; r++)
     if (P.res_src[r] >= 0 && O->h_lin[O->inv[P.res_src[r]]])
       return sdso::fail(ctx, SDSO_ERR_STATE, "a surviving residual is linearised (fixLinearizationF only touches points that leave)");
   // ---- the prior (sdso_abi.h)
-  WindowCarry cy{O, P.point_src.data(), P.res_src.data(), O->dt_HM, O->dt_bM, O->d.n};
+  WindowCarry cy{O, P.point_src.data(), P.res_src.data(), O->dt_HM, O->dt_bM, O->d.n, act_rec, act_dev};
   if (!E.n_remove_frames && O->marg_chain)
     return sdso::fail(ctx, SDSO_ERR_STATE, "sdso_ba_marginalize_frame_dev has run on this window but the edit removes no frame: its prior would be lost");
   if (E.n_remove_frames) {
@@ -130,6 +170,7 @@ static int window_update_impl(sdso_ctx* ctx, int win, BaWindowDev* O, const sdso
     const int s = P.point_src[p];
     if (s >= 0) { hdp[p] = O->h_prior[s] > 0.f; continue; }   // (EFPoint::priorF is positive exactly where hasDepthPrior was set)
     const int k = -1 - s;
+    if (act_rec) continue;                               // (hasDepthPrior = false, HessianBlocks.cpp:38; the float rows: k_ba_window_fill_activated)
     u[p] = E.pt_u[k]; v[p] = E.pt_v[k]; idp[p] = E.pt_idepth[k]; idz[p] = E.pt_idepth_zero[k]; hdp[p] = E.pt_hasDepthPrior[k];
     std::memcpy(&color[(size_t)p * 8], E.pt_color + (size_t)k * 8, 32); std::memcpy(&weights[(size_t)p * 8], E.pt_weights + (size_t)k * 8, 32);
     if (E.pt_maxRelBaseline) mrb[p] = E.pt_maxRelBaseline[k];
@@ -175,6 +216,40 @@ extern "C" int sdso_ba_window_update(sdso_ctx* ctx, int win, const sdso_ba_windo
   }
   ctx->wins[win] = made;
   free_window(ctx, W);                                 // old slab back to the pool: the stream orders its reuse behind the gather
+  return SDSO_OK;
+}
+
+extern "C" int sdso_ba_window_update_activated(sdso_ctx* ctx, int win, const sdso_ba_window_edit_t* E, const int* act_frame, int* n_points, int* n_res,
+                                               int* act_index) {
+  GET_WIN();
+  SDSO_REQUIRE(ctx, E, "null edit");
+  SDSO_REQUIRE(ctx, E->n_add_points == 0 && E->n_pt_res == 0, "stage 7 of the edit must be empty: it is taken from the latest sdso_imm_activate");
+  ImmActView A;
+  imm_activation_view(ctx, &A);
+  if (!A.valid) return sdso::fail(ctx, SDSO_ERR_STATE, "no sdso_imm_activate on this ctx yet");
+  if (A.consumed) return sdso::fail(ctx, SDSO_ERR_STATE, "the latest sdso_imm_activate has already been taken into a window");
+  SDSO_REQUIRE(ctx, act_frame, "null act_frame");
+  SDSO_REQUIRE(ctx, A.w == W->d.w && A.h == W->d.h, "the activation's w / h differ from the window's");
+  ActStage7 S7;
+  const char* why = nullptr;
+  if (!plan_activated_stage7(W->d.nf, *E, A.nf, act_frame, A.n, A.h_rec, S7, &why)) return sdso::fail(ctx, SDSO_ERR_ARG, why);
+  sdso_ba_window_edit_t E2 = *E;
+  E2.n_add_points = (int)S7.pt_host.size(); E2.pt_host = S7.pt_host.data();
+  E2.n_pt_res = (int)S7.res_point.size(); E2.pt_res_point = S7.res_point.data(); E2.pt_res_target = S7.res_target.data();
+  E2.pt_res_state = S7.res_state.data(); E2.pt_res_isNew = nullptr;   // setState(ResState::IN) (FullSystemOptPoint.cpp:218), isNew as constructed
+  BaWindowDev* made = nullptr;
+  const bool any = E2.n_add_points > 0;
+  const int rc = window_update_impl(ctx, win, W, E2, &made, any ? S7.rec.data() : nullptr, any ? A.d_rec : nullptr);
+  if (rc) {
+    if (made) { const std::string err = ctx->err; free_window(ctx, made); ctx->err = err; }
+    return rc;
+  }
+  ctx->wins[win] = made;
+  free_window(ctx, W);
+  imm_activation_consumed(ctx);
+  if (n_points) *n_points = E2.n_add_points;
+  if (n_res) *n_res = E2.n_pt_res;
+  if (act_index) std::copy(S7.rec.begin(), S7.rec.end(), act_index);
   return SDSO_OK;
 }
 

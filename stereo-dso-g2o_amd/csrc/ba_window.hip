@@ -199,8 +199,13 @@ extern "C" int sdso_ba_release_window(sdso_ctx* ctx, int win) {
 
 // What sdso_ba_window_update (ba_update.hip) hands to the upload: the window being replaced and, per point / residual of the new window
 // (window order), the index in the old one whose device state is carried (< 0: the entry is new and comes from Win like any uploaded one).
-struct WindowCarry { BaWindowDev* old; const int* point_src; const int* res_src; const double* prior_H; const double* prior_b; int prior_dim; };
-static void launch_window_gather(sdso_ctx* ctx, const BaWindowDev* W, const WindowCarry& cy, const int* d_psrc, const int* d_rsrc);   // ba_update.hip
+// act_rec != nullptr (sdso_ba_window_update_activated): the new entry -1-k of point_src is record act_rec[k] of act_dev, and its float rows are
+// filled from that record on the device.
+struct WindowCarry {
+  BaWindowDev* old; const int* point_src; const int* res_src; const double* prior_H; const double* prior_b; int prior_dim;
+  const int* act_rec = nullptr; const ImmActRec* act_dev = nullptr;
+};
+static void launch_window_gather(sdso_ctx* ctx, const BaWindowDev* W, const WindowCarry& cy, const int* d_psrc, const int* d_rsrc, const int* d_asrc);   // ba_update.hip
 
 // phase times of the upload on stderr under SDSO_BA_UPLOAD_TIMING (diagnostic; tools/dbg_upload_timing.py reads the phase names)
 struct UploadTimer {
@@ -261,8 +266,8 @@ static int upload_mirror(sdso_ctx* ctx, BaWindowDev* W, const sdso_ba_window_t* 
 // are filled by one staged H2D copy (a pinned staging buffer of the ctx, same layout); everything behind them is cleared by one memset.
 // (~60 separate buffers with a memset each and ~40 small pageable copies cost 0.7 of the 0.96 ms an upload took.)
 struct SlabSeg { void** slot; size_t bytes; bool init; size_t off; };   // where the segment's address goes; init: filled by the staged copy
-struct WindowSlab { char* slab = nullptr; char* stage = nullptr; size_t init_bytes = 0, total = 0; int *g_psrc = nullptr, *g_rsrc = nullptr; };
-static int upload_lay_out_slab(sdso_ctx* ctx, BaWindowDev* W, bool carry, WindowSlab& S) {
+struct WindowSlab { char* slab = nullptr; char* stage = nullptr; size_t init_bytes = 0, total = 0; int *g_psrc = nullptr, *g_rsrc = nullptr, *g_asrc = nullptr; };
+static int upload_lay_out_slab(sdso_ctx* ctx, BaWindowDev* W, bool carry, bool activated, WindowSlab& S) {
   BaDev& d = W->d;
   const int nf = d.nf, np = d.np, nr = d.nr, n = d.n;
   std::vector<SlabSeg> segs;
@@ -294,6 +299,7 @@ static int upload_lay_out_slab(sdso_ctx* ctx, BaWindowDev* W, bool carry, Window
   PL(W->d_pflag, uint8_t, np, false); PL(W->d_sums, float, 2 * (W->nblk_pts + 1), false);
   PL(W->d_opt, BaOptDev, 1, false);
   if (carry) { PL(S.g_psrc, int, np, true); PL(S.g_rsrc, int, nr, true); }   // sdso_ba_window_update: the gather maps (pair-sorted for the residuals), staged with the rest
+  if (carry && activated) PL(S.g_asrc, int, np, true);                        // sdso_ba_window_update_activated: per point its activation record, or -1
 #undef PL
   for (int pass = 0; pass < 2; pass++) {
     for (SlabSeg& sg : segs)
@@ -353,6 +359,11 @@ static void upload_stage_entries(BaWindowDev* W, const sdso_ba_window_t* Win, co
     std::vector<int> rs(nr);
     for (int j = 0; j < nr; j++) { const int o = carry->res_src[W->perm[j]]; rs[j] = o >= 0 ? carry->old->inv[o] : -1; }
     put(S.g_psrc, carry->point_src, sizeof(int) * np); put(S.g_rsrc, rs.data(), sizeof(int) * nr);
+    if (S.g_asrc) {
+      std::vector<int> as(np);
+      for (int p = 0; p < np; p++) as[p] = carry->point_src[p] < 0 ? carry->act_rec[-1 - carry->point_src[p]] : -1;
+      put(S.g_asrc, as.data(), sizeof(int) * np);
+    }
   }
 }
 
@@ -399,7 +410,7 @@ static int upload_window_impl(sdso_ctx* ctx, int win, const sdso_ba_window_t* Wi
   tm.mark("validation, sort, work lists");
 
   WindowSlab S;
-  if ((rc = upload_lay_out_slab(ctx, W, carry != nullptr, S))) return rc;
+  if ((rc = upload_lay_out_slab(ctx, W, carry != nullptr, carry && carry->act_rec, S))) return rc;
   tm.mark("slab + staging reservation");
   upload_stage_entries(W, Win, L, imgs, carry, S);
   tm.mark("staging of points / residuals");
@@ -409,7 +420,7 @@ static int upload_window_impl(sdso_ctx* ctx, int win, const sdso_ba_window_t* Wi
 
   SDSO_HIP(ctx, hipMemcpyAsync(S.slab, S.stage, S.init_bytes, hipMemcpyHostToDevice, ctx->stream));
   if (S.total > S.init_bytes) SDSO_HIP(ctx, hipMemsetAsync(S.slab + S.init_bytes, 0, S.total - S.init_bytes, ctx->stream));
-  if (carry) launch_window_gather(ctx, W, *carry, S.g_psrc, S.g_rsrc);   // the survivors' rows and the prior: old slab -> new slab
+  if (carry) launch_window_gather(ctx, W, *carry, S.g_psrc, S.g_rsrc, S.g_asrc);   // the survivors' rows and the prior: old slab -> new slab; activated points: record -> new slab
   // per-residual record: target in slot 15, newState OUTLIER, newEnergyWO -1
   if (d.nr) hipLaunchKernelGGL(k_ba_init_res, dim3(W->nblk_res), dim3(BA_BLOCK), 0, ctx->stream, W->d_self);
   SDSO_HIP(ctx, hipGetLastError());

@@ -2,7 +2,8 @@
 // STEP 2 (src/FullSystem/FullSystem.cpp:837-902) on the device.
 //
 // The level-1 map lives in the ctx as BYTES: 0..39 = the step of growDistBFS that set the pixel, 255 = untouched (the reference's 1000).
-//   k_distmap_seed   : project every active point (CoarseTracker.cpp:1242-1248), store 0 at the seeds, count them (numItems)
+//   k_distmap_seed   : project every active point (CoarseTracker.cpp:1242-1248), store 0 at the seeds, count them (numItems);
+//                      k_distmap_seed_window: the same from the points of a resident BA window (sdso_distmap_make_from_window)
 //   k_distmap_grow   : growDistBFS (:1260-1363) from scratch, one workgroup per 64x64 tile with a 39-pixel halo in LDS — a pixel's value
 //                      depends only on seeds within 39 pixels and on paths inside that radius, so tiles never exchange anything
 //   k_select_classify: the per-candidate gates of STEP 2 (FullSystem.cpp:850-887), independent per candidate
@@ -30,6 +31,7 @@ struct DistMapState {
   bool valid = false;          // a map has been made for (w1, h1)
   uint8_t* seed = nullptr;     // w1*h1 bytes (padded to 16): 0 at the seeds, 255 elsewhere
   uint8_t* map = nullptr;      // w1*h1 bytes (padded to 16)
+  int* cnt = nullptr;          // numItems of sdso_distmap_make_from_window (the host route counts in the ctx scratch)
   size_t cap = 0;
 };
 
@@ -37,6 +39,7 @@ void release_distmap(sdso_ctx* ctx) {
   if (!ctx->dm) return;
   if (ctx->dm->seed) hipFree(ctx->dm->seed);
   if (ctx->dm->map) hipFree(ctx->dm->map);
+  if (ctx->dm->cnt) hipFree(ctx->dm->cnt);
   delete ctx->dm;
   ctx->dm = nullptr;
 }
@@ -51,6 +54,28 @@ __global__ __launch_bounds__(256) void k_distmap_seed(int n, const sdso_distmap_
     float p0;
     in = dm_project(geom[pg[i]], u[i], v[i], idepth[i], w1, h1, iu, iv, p0);
     if (in) seed[iu + w1 * iv] = 0;       // every writer stores 0
+  }
+  const unsigned long long b = __ballot(in);
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(n_seeds, __popcll(b));
+}
+
+// The same seeds from a device-resident BA window (sdso_distmap_make_from_window): point p of the window is projected with the geometry of
+// its host frame, its u, v and its current idepth (p_geo.z: idepth_scaled, SCALE_IDEPTH = 1).  G holds the window's frames (at most 8) and
+// travels as a kernel argument; skip[f] != 0: the points of frame f contribute nothing (`if (fh == frame) continue`, CoarseTracker.cpp:1232).
+struct DmWinGeoms { sdso_distmap_geom_t G[8]; uint8_t skip[8]; };
+__global__ __launch_bounds__(256) void k_distmap_seed_window(int n, int nf, const DmWinGeoms A, const float4* __restrict__ p_geo, const int* __restrict__ p_host,
+                                                             int w1, int h1, uint8_t* __restrict__ seed, int* __restrict__ n_seeds) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool in = false;
+  if (i < n) {
+    const int f = p_host[i];
+    if (f >= 0 && f < nf && !A.skip[f]) {
+      const float4 g = p_geo[i];
+      int iu, iv;
+      float p0;
+      in = dm_project(A.G[f], g.x, g.y, g.z, w1, h1, iu, iv, p0);
+      if (in) seed[iu + w1 * iv] = 0;     // every writer stores 0
+    }
   }
   const unsigned long long b = __ballot(in);
   if ((threadIdx.x & 63) == 0 && b) atomicAdd(n_seeds, __popcll(b));
@@ -266,6 +291,7 @@ static int dm_ensure(sdso_ctx* ctx, int w1, int h1) {
     SDSO_HIP(ctx, hipMalloc(&D.map, need));
     D.cap = need;
   }
+  if (!D.cnt) SDSO_HIP(ctx, hipMalloc(&D.cnt, 16));
   if (D.w1 != w1 || D.h1 != h1) D.valid = false;
   D.w1 = w1; D.h1 = h1;
   return SDSO_OK;
@@ -333,6 +359,41 @@ extern "C" int sdso_distmap_make(sdso_ctx* ctx, int w, int h, int ngeom, const s
   SDSO_HIP(ctx, hipMemcpyAsync(hp + o_cnt, dp + o_cnt, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (n_seeds) *n_seeds = *(int*)(hp + o_cnt);
+  D.valid = true;
+  return SDSO_OK;
+}
+
+// makeDistanceMap on the points of a resident window.  The reference walks frameHessians and each frame's pointHessians (:1231-1249); the
+// window keeps its points in exactly that order (makeIDX), but the order does not matter anyway: every seed stores the same 0 and numItems
+// only counts, so any order of the same points gives the same seed image, and k_distmap_grow starts from that image alone.
+extern "C" int sdso_distmap_make_from_window(sdso_ctx* ctx, int win, int w, int h, const sdso_distmap_geom_t* geom, const uint8_t* skip, int* n_seeds) {
+  if (!ctx) return SDSO_ERR_STATE;
+  BaPointsView V;
+  SDSO_TRY(ba_window_points(ctx, win, &V));
+  SDSO_REQUIRE(ctx, w >= 16 && h >= 16 && w <= 32768 && h <= 32768, "image size out of range");
+  SDSO_REQUIRE(ctx, w == V.w && h == V.h, "w / h differ from the window's");
+  SDSO_REQUIRE(ctx, geom, "null argument");
+  SDSO_HIP(ctx, hipSetDevice(ctx->device));
+  const int w1 = w >> 1, h1 = h >> 1;
+  SDSO_TRY(dm_ensure(ctx, w1, h1));
+  DistMapState& D = *ctx->dm;
+  D.valid = false;
+  DmWinGeoms A;
+  std::memset(&A, 0, sizeof(A));
+  for (int f = 0; f < V.nf; f++) { A.G[f] = geom[f]; A.skip[f] = skip && skip[f] ? 1 : 0; }
+  int* d_cnt = D.cnt;
+  SDSO_HIP(ctx, hipMemsetAsync(D.seed, DM_FAR, D.cap, ctx->stream));
+  SDSO_HIP(ctx, hipMemsetAsync(d_cnt, 0, sizeof(int), ctx->stream));
+  if (V.np)
+    launch_timed(ctx, "k_distmap_seed_window", 2, k_distmap_seed_window, dim3((V.np + 255) / 256), dim3(256), V.np, V.nf, A, V.p_geo, V.p_host, w1, h1, D.seed, d_cnt);
+  launch_timed(ctx, "k_distmap_grow", 1, k_distmap_grow, dim3((w1 + DM_T - 1) / DM_T, (h1 + DM_T - 1) / DM_T), dim3(256), (const uint8_t*)D.seed, D.map, w1, h1);
+  SDSO_HIP(ctx, hipGetLastError());
+  if (n_seeds) {
+    SDSO_TRY(ensure_pinned(ctx, sizeof(int)));
+    SDSO_HIP(ctx, hipMemcpyAsync(ctx->pinned, d_cnt, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *n_seeds = *(int*)ctx->pinned;
+  }
   D.valid = true;
   return SDSO_OK;
 }

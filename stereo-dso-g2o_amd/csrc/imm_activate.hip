@@ -17,16 +17,7 @@ struct ImmActArgs {
   uint8_t flagged[SDSO_IMM_MAX_HOSTS];
 };
 struct ImmActOut { float* f[SDSO_IMM_MAX_HOSTS]; uint8_t* st[SDSO_IMM_MAX_HOSTS]; };
-// one entry of toOptimize as sdso_imm_activate_fetch hands it out
-struct ImmActRec {
-  int frame, index;
-  int8_t status; uint8_t lastTraceStatus; uint8_t pad[2];
-  float idepth;
-  uint8_t res_state[8];
-  float u, v, my_type, idepth_min, idepth_max, energyTH;
-  float color[8], weights[8];
-};
-static_assert(sizeof(ImmActRec) == 112, "records are copied as 16-byte aligned blocks");
+// (one entry of toOptimize: ImmActRec, imm_layout.h)
 // header of the result blob: ints
 enum { ACT_H_DELETE = 0, ACT_H_NSEL = 1, ACT_H_NLIST = 2, ACT_H_STATUS = 3 /* -1, 0, 1 */, ACT_H_FLAGGED = 6 /* per walked frame */, ACT_H_INTS = 16 };
 
@@ -196,13 +187,19 @@ extern "C" int sdso_imm_activate(sdso_ctx* ctx, const sdso_imm_activate_t* P, in
   const size_t o_flag = take(N), o_iu = take(4 * N), o_iv = take(4 * N), o_frac = take(4 * N), o_thr = take(4 * N), o_list = take(4 * N), o_pref = take(4 * N),
                o_back = take(4 * N), o_src = take(4 * N), o_seg = take(4 * (nseg + 1));
   SDSO_TRY(ensure_scratch(ctx, bytes));
+  S.act_valid = false;                                    // from here on the previous activation's records (h_act, d_act) may be freed or overwritten
   if (S.h_act_cap < res_bytes) {
     if (S.h_act) { SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream)); hipHostFree(S.h_act); S.h_act = nullptr; S.h_act_cap = 0; }
     const size_t want = (res_bytes * 3 / 2 + 4095) & ~(size_t)4095;
     SDSO_HIP(ctx, hipHostMalloc((void**)&S.h_act, want));
     S.h_act_cap = want;
   }
-  S.act_valid = false;
+  if (S.d_act_cap < sizeof(ImmActRec) * N) {              // the records' own buffer (below): the scratch is the next call's to overwrite
+    if (S.d_act) { SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream)); hipFree(S.d_act); S.d_act = nullptr; S.d_act_cap = 0; }
+    const size_t want = (sizeof(ImmActRec) * N * 3 / 2 + 4095) & ~(size_t)4095;
+    SDSO_HIP(ctx, hipMalloc((void**)&S.d_act, want));
+    S.d_act_cap = want;
+  }
   char* dp = (char*)ctx->scratch;
   int* d_hdr = (int*)(dp + o_hdr);
   uint8_t* d_dec = (uint8_t*)(dp + o_dec);
@@ -255,6 +252,9 @@ extern "C" int sdso_imm_activate(sdso_ctx* ctx, const sdso_imm_activate_t* P, in
                                    hipMemcpyDeviceToHost, ctx->stream));
       SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
+    // the records outlive the scratch: device to device into the set's own buffer, enqueued behind the chain (nothing waits for it here;
+    // sdso_ba_window_update_activated reads them on this stream)
+    if (nsel) SDSO_HIP(ctx, hipMemcpyAsync(S.d_act, dp + o_rec, sizeof(ImmActRec) * nsel, hipMemcpyDeviceToDevice, ctx->stream));
     for (int g = 0; g < nh; g++) {
       const int nflag = h_hdr[ACT_H_FLAGGED + g];
       if (!hosts[g] || nflag == 0) continue;
@@ -263,6 +263,7 @@ extern "C" int sdso_imm_activate(sdso_ctx* ctx, const sdso_imm_activate_t* P, in
     }
   }
   S.act_valid = true; S.act_nf = nf; S.act_ntot = n; S.act_nsel = h_hdr[ACT_H_NLIST];
+  S.act_w = P->w; S.act_h = P->h; S.act_consumed = false;
   if (counts) {
     for (int k = 0; k < SDSO_IMM_ACT_NCOUNTS; k++) counts[k] = 0;
     int removed = 0;
@@ -306,3 +307,16 @@ extern "C" int sdso_imm_activate_fetch(sdso_ctx* ctx, sdso_imm_activated_t* out,
   }
   return SDSO_OK;
 }
+
+namespace sdso {
+void imm_activation_view(sdso_ctx* ctx, ImmActView* out) {
+  *out = ImmActView();
+  if (!ctx->imm || !ctx->imm->act_valid) return;
+  const ImmState& S = *ctx->imm;
+  const size_t o_rec = sizeof(int) * ACT_H_INTS + (((size_t)S.act_ntot + 15) & ~(size_t)15);   // header | decisions | records, as sdso_imm_activate lays them out
+  out->valid = true; out->consumed = S.act_consumed;
+  out->nf = S.act_nf; out->n = S.act_nsel; out->w = S.act_w; out->h = S.act_h;
+  out->h_rec = (const ImmActRec*)(S.h_act + o_rec); out->d_rec = (const ImmActRec*)S.d_act;
+}
+void imm_activation_consumed(sdso_ctx* ctx) { if (ctx->imm) ctx->imm->act_consumed = true; }
+}  // namespace sdso

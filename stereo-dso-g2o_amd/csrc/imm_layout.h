@@ -47,6 +47,21 @@ IMM_HD inline ImmMember imm_member_of_float(int c) {
   return {IMM_INTERVAL, 1};
 }
 
+// ---- one entry of toOptimize as sdso_imm_activate leaves it on the device and sdso_imm_activate_fetch hands it out.  The integer members
+// (frame, index, status, lastTraceStatus, res_state) are what the host reads of it; sdso_ba_window_update_activated (ba_update.hip) reads
+// the float members where they lie.
+struct ImmActRec {
+  int frame, index;
+  int8_t status; uint8_t lastTraceStatus; uint8_t pad[2];
+  float idepth;
+  uint8_t res_state[8];
+  float u, v, my_type, idepth_min, idepth_max, energyTH;
+  float color[8], weights[8];
+};
+static_assert(sizeof(ImmActRec) == 112, "records are copied as 16-byte aligned blocks");
+static_assert(offsetof(ImmActRec, idepth) == 12 && offsetof(ImmActRec, u) == 24 && offsetof(ImmActRec, v) == 28, "k_ba_window_fill_activated reads these as floats 3, 6, 7");
+static_assert(offsetof(ImmActRec, color) == 48 && offsetof(ImmActRec, weights) == 80, "colour and weights are read as two float4 each");
+
 // ---- STEP 5: `if (!ph) { immaturePoints[i] = back(); pop_back(); i--; }`.  src[0 .. size) = the old index of every entry of the new
 // vector; a flagged entry stands for the reference's null pointer.  Returns size.
 inline int imm_remove_order(int n, const uint8_t* flags, int* src) {

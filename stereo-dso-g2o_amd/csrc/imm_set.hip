@@ -42,6 +42,12 @@ struct ImmState {
   size_t h_act_cap = 0;
   bool act_valid = false;
   int act_nf = 0, act_ntot = 0, act_nsel = 0;
+  // the same records once more on the device, in a buffer no other call writes, for sdso_ba_window_update_activated: act_nsel entries of
+  // ImmActRec (imm_layout.h); the w x h of that call; consumed: an update has taken them into a window (cleared by every sdso_imm_activate)
+  char* d_act = nullptr;
+  size_t d_act_cap = 0;
+  int act_w = 0, act_h = 0;
+  bool act_consumed = false;
 };
 static ImmState& imm_state(sdso_ctx* ctx) { if (!ctx->imm) ctx->imm = new ImmState(); return *ctx->imm; }
 static void imm_free_host(ImmHost& H) {
@@ -70,6 +76,7 @@ void release_immature(sdso_ctx* ctx) {
   if (S->d_counts) hipFree(S->d_counts);
   if (S->h_counts) hipHostFree(S->h_counts);
   if (S->h_act) hipHostFree(S->h_act);
+  if (S->d_act) hipFree(S->d_act);
   if (S->match.d) hipFree(S->match.d);
   if (S->match.h) hipHostFree(S->match.h);
   if (S->match.d_map) hipFree(S->match.d_map);

@@ -322,6 +322,16 @@ int ba_ref_view(sdso_ctx* ctx, int win, BaRefView* out);
 int ba_window_hosts(sdso_ctx* ctx, int win, int frameID[8], int host_pt_beg[9]);
 // the current blob of an immature group (imm_layout.h) with its count resolved; *f = nullptr without such a group (imm_set.hip)
 int imm_host_view(sdso_ctx* ctx, int host_id, const float** f, int* n, int* cap);
+// the latest sdso_imm_activate of the ctx (imm_activate.hip): its n records in toOptimize order, on the host (pinned; the integer members
+// are what a caller may read there) and on the device in the set's own buffer; consumed: imm_activation_consumed has been called since
+struct ImmActRec;   // imm_layout.h
+struct ImmActView { bool valid = false, consumed = false; int nf = 0, n = 0, w = 0, h = 0; const ImmActRec* h_rec = nullptr; const ImmActRec* d_rec = nullptr; };
+void imm_activation_view(sdso_ctx* ctx, ImmActView* out);
+void imm_activation_consumed(sdso_ctx* ctx);
+// the points of a window where they lie (ba_api.hip): p_geo = {u, v, idepth, idepth_zero} and the host frame of every point, in the
+// window's order.  SDSO_ERR_ARG for an unknown window.
+struct BaPointsView { const float4* p_geo; const int* p_host; int nf, np, w, h; };
+int ba_window_points(sdso_ctx* ctx, int win, BaPointsView* out);
 
 // ------------------------------------------------------------------ device helpers
 // getInterpolatedElement33 (src/util/globalFuncs.h:73-86) on the float4 image.

@@ -148,6 +148,7 @@ struct WindowGraph {
       fh->affFromState = true;
       fh->ab_exposure = exposure[f]; fh->frameEnergyTH = eTH[f]; fh->frameID = frameID[f]; fh->idx = f; fh->shell->id = 100 + f;
       effs.push_back(new EFFrame{fh, {}, f});
+      fh->efFrame = effs.back();
       if (f < nf) ef.frames.push_back(effs.back());
     }
     int r = 0;

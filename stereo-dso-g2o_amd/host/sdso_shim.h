@@ -25,6 +25,7 @@
 //   EnergyFunctional::{calcLEnergyF_MT, calcMEnergyF, setDeltaF, setAdjointsF}                                       OptimizationBackend/EnergyFunctional.h:75-86
 //   CoarseDistanceMap::{makeK, makeDistanceMap, addIntoDistFinal, fwdWarpedIDDistFinal, K, Ki}                          FullSystem/CoarseTracker.h:165-197
 //   void FullSystem::activatePointsMT() STEP 1-2                                                                      FullSystem/FullSystem.cpp:796-902
+//   the tail of optimizeImmaturePoint + STEP 4 of activatePointsMT into the resident window (WindowedBA::updateActivated)   FullSystem/FullSystemOptPoint.cpp:196-237, FullSystem.cpp:919-945
 //   void FullSystem::makeNewTraces(FrameHessian*, FrameHessian*, float*), traceNewCoarseNonKey / traceNewCoarseKey(fh, fh_right)    FullSystem/FullSystem.cpp:1600, :632, :745
 //   the loop of void FullSystem::stereoMatch(ImageAndExposure*, ImageAndExposure*, int, cv::Mat&)                      FullSystem/FullSystem.cpp:579-613
 //   Undistort::{undistort<T>, getK, getSize, getOriginalSize, getBl, isValid, loadPhotometricCalibration}               util/Undistort.h:63-104
@@ -892,8 +893,35 @@ class WindowedBA {
     for (size_t i = 0; i < residuals_.size(); i++)         // FullSystem::marginalizeFrame drops them next (FullSystemMarginalize.cpp:150-180)
       if (residuals_[i] && residuals_[i]->target == f) { res_index_.erase(residuals_[i]->data); residuals_[i] = nullptr; }
   }
+  //   updateActivated(ef, slot_of, frameHessians, n_records)
+  //                                   update() for the keyframe whose new points come from ImmaturePoints::activatePointsMT on this Device:
+  //                                   stage 7 is taken from the activation's records where they lie (sdso_ba_window_update_activated), so
+  //                                   no float of an activated point is read from the caller's objects.  The caller has run its loop over
+  //                                   the Activated records with their integer members alone — status 1: a PointHessian on a.host, a
+  //                                   PointFrameResidual per IN entry of a.res_state, ef->insertPoint / insertResidual (FullSystemOptPoint.cpp:
+  //                                   196-237, FullSystem.cpp:923-933) — frameHessians is the vector that activation walked and n_records the
+  //                                   size of the vector it returned.  Returns
+  //                                   act_index: the k-th appended point is entry act_index[k] of the Activated vector; the order check
+  //                                   below holds the caller's objects against what the device appended.
   template <class SlotOf>
-  void update(EnergyFunctionalT* ef, SlotOf slot_of) {
+  void update(EnergyFunctionalT* ef, SlotOf slot_of) { update_(ef, slot_of, nullptr, 0); }
+  template <class SlotOf, class FrameHessianT>
+  std::vector<int> updateActivated(EnergyFunctionalT* ef, SlotOf slot_of, const std::vector<FrameHessianT*>& frameHessians, size_t n_records) {
+    std::vector<const void*> act(frameHessians.begin(), frameHessians.end());
+    return update_(ef, slot_of, &act, n_records);
+  }
+  // the index of ef frame `f` in the device window (after upload() / update()); -1: not part of it
+  template <class EFFrameT>
+  int frameIndex(const EFFrameT* f) const {
+    for (size_t k = 0; k < frames_.size(); k++) if (frames_[k] == f) return (int)k;
+    return -1;
+  }
+  int windowId() const { return win_; }
+  int frameCount() const { return nf_; }
+
+ private:
+  template <class SlotOf>
+  std::vector<int> update_(EnergyFunctionalT* ef, SlotOf slot_of, const std::vector<const void*>* act_frames, size_t act_records) {
     const int nf_old = nf_;
     std::unordered_map<const void*, int> frame_old;        // EFFrame* -> index before the call (appended frames: nf_old + k)
     for (int k = 0; k < nf_old; k++)
@@ -963,7 +991,29 @@ class WindowedBA {
     E.pt_hasDepthPrior = pt.prior.data(); E.pt_maxRelBaseline = pt.maxRelBaseline.data(); E.pt_numGoodResiduals = pt.numGood.data();
     E.n_pt_res = (int)pr.point.size(); E.pt_res_point = pr.point.data(); E.pt_res_target = pr.target.data();
     E.pt_res_state = pr.state.data(); E.pt_res_isNew = pr.isNew.data();
-    dev_.check(sdso_ba_window_update(dev_.ctx(), win_, &E), "sdso_ba_window_update");
+    std::vector<int> act_index;
+    if (!act_frames) {
+      dev_.check(sdso_ba_window_update(dev_.ctx(), win_, &E), "sdso_ba_window_update");
+    } else {
+      // act_frame: the window frame (numbering before the call) of every frame the activation walked
+      std::vector<int> act_frame;
+      for (const void* fh : *act_frames) {
+        int at = -1;
+        for (auto* f : ef->frames) if ((const void*)f->data == fh) at = frame_of(f);
+        if (at < 0) throw Error("updateActivated: a frame of the activation is not part of the EnergyFunctional");
+        // (the reference's frameHessians and ef->frames are in one order; the order check below relies on it: the device numbers the
+        // appended points in toOptimize order, which is then the order the walk above met the caller's objects in)
+        if (!act_frame.empty() && at <= act_frame.back()) throw Error("updateActivated: the activation's frames are not in the EnergyFunctional's order");
+        act_frame.push_back(at);
+      }
+      const int want_np = E.n_add_points, want_nr = E.n_pt_res;
+      E.n_add_points = 0; E.n_pt_res = 0;                    // stage 7 comes from the records
+      int n_pt = 0, n_res = 0;
+      std::vector<int> idx_all(std::max<size_t>(act_records, 1), -1);   // the library writes one entry per appended point, at most one per record
+      dev_.check(sdso_ba_window_update_activated(dev_.ctx(), win_, &E, act_frame.data(), &n_pt, &n_res, idx_all.data()), "sdso_ba_window_update_activated");
+      if (n_pt != want_np || n_res != want_nr) throw Error("updateActivated: the caller inserted other points / residuals than the activation made");
+      act_index.assign(idx_all.begin(), idx_all.begin() + n_pt);
+    }
     // ---- the device's order is the EnergyFunctional's, or the two have drifted apart
     const int nf2 = (int)ef->frames.size();
     std::vector<int> fs(nf2), ps(new_points.size()), rs(new_residuals.size());
@@ -981,9 +1031,9 @@ class WindowedBA {
     clearPending_();
     window_serial_++;
     lin_valid_ = app_valid_ = acc_valid_ = marg_valid_ = false;
+    return act_index;
   }
 
- private:
   // optimize() / willRemovePoint / willDropPoints / marginalizeFrame left null slots in points_ / residuals_: the members that walk those
   // lists need update() (or upload()) first
   void requireNoPendingEdit_(const char* who) const {
@@ -1353,6 +1403,24 @@ class CoarseDistanceMap {
     }
     dev_.check(sdso_distmap_make(dev_.ctx(), w[0], h[0], (int)geom.size(), geom.data(), (int)u.size(), pg.data(), u.data(), v.data(), id.data(), &numItems),
                "sdso_distmap_make");
+    stale_ = true;
+  }
+  // The same on the points of the device-resident window of `ba` (sdso_distmap_make_from_window): u, v and the current idepth of every
+  // active point are read where they lie, only the geometries travel.  frameHessians must be the frames of that window (each with its
+  // efFrame); `frame` itself, when it is already part of the window, contributes nothing (:1232).
+  template <class WindowedBAT, class FrameHessianT>
+  void makeDistanceMap(WindowedBAT& ba, std::vector<FrameHessianT*> frameHessians, FrameHessianT* frame) {
+    const int nf = ba.frameCount();
+    std::vector<sdso_distmap_geom_t> geom((size_t)nf);
+    std::vector<uint8_t> skip((size_t)nf, 1);             // a window frame the caller does not name contributes nothing
+    for (FrameHessianT* fh : frameHessians) {
+      if (frame == fh) continue;
+      const int k = ba.frameIndex(fh->efFrame);
+      if (k < 0) throw Error("makeDistanceMap: a frame is not part of the device window");
+      geom[(size_t)k] = geomOf(fh, frame);
+      skip[(size_t)k] = 0;
+    }
+    dev_.check(sdso_distmap_make_from_window(dev_.ctx(), ba.windowId(), w[0], h[0], geom.data(), skip.data(), &numItems), "sdso_distmap_make_from_window");
     stale_ = true;
   }
   // addIntoDistFinal(int u, int v) — CoarseTracker.cpp:1366-1372

@@ -98,6 +98,7 @@ struct CalibHessian {
 struct FrameHessian {
   FrameShell* shell = &shellStore;                                  // :105
   Vec3f* dIp[SDSO_PYR_LEVELS] = {};                                 // :108
+  EFFrame* efFrame = nullptr;                                       // :101
   int frameID = 0, idx = -1;                                        // :111, :113
   float frameEnergyTH = 0, ab_exposure = 1;                         // :116-117
   bool flaggedForMarginalization = false;                           // :119

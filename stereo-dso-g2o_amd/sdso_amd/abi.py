@@ -511,6 +511,7 @@ def load():
     L.sdso_ba_window_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, C.POINTER(BAWindowEdit), c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p]
     L.sdso_ba_window_update.argtypes = [vp, C.c_int, C.POINTER(BAWindowEdit)]
     L.sdso_ba_window_get_order.argtypes = [vp, C.c_int, c_int_p, c_int_p, c_int_p]
+    L.sdso_ba_window_update_activated.argtypes = [vp, C.c_int, C.POINTER(BAWindowEdit), c_int_p, c_int_p, c_int_p, c_int_p]
     L.sdso_ba_flag_points.argtypes = [vp, C.c_int, C.POINTER(BAFlagPoints), c_u8_p, c_int_p, c_int_p]
     L.sdso_ba_get_deltas.argtypes = [vp, C.c_int, c_float_p, c_double_p, c_double_p, c_float_p]
     L.sdso_comm_unique_id.argtypes = [vp]
@@ -543,6 +544,7 @@ def load():
     L.sdso_g2o_lba_eval.argtypes = [vp, C.POINTER(G2oLba), c_double_p, c_double_p, c_u8_p, c_float_p, c_float_p, c_float_p, c_u8_p]
     L.sdso_trace_set_gn_mode.argtypes = [vp, C.c_int]
     L.sdso_distmap_make.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(DistMapGeom), C.c_int, c_int_p, c_float_p, c_float_p, c_float_p, c_int_p]
+    L.sdso_distmap_make_from_window.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(DistMapGeom), c_u8_p, c_int_p]
     L.sdso_distmap_add.argtypes = [vp, C.c_int, c_int_p, c_int_p]
     L.sdso_distmap_get.argtypes = [vp, c_float_p]
     L.sdso_activate_select.argtypes = [vp, C.POINTER(ActivateSelect), c_u8_p, c_int_p, c_int_p, c_int_p]
@@ -599,11 +601,11 @@ EXPORTED_SYMBOLS = [
     "sdso_immature_init_batch", "sdso_trace_stereo_batch", "sdso_trace_stereo_prepare", "sdso_trace_stereo_enqueue",
     "sdso_trace_stereo_fetch", "sdso_stereo_match_batch", "sdso_activate_points_batch", "sdso_ba_marginalize_frame", "sdso_ba_batch_linearize", "sdso_ba_batch_schur", "sdso_pixel_select", "sdso_pixel_selector_pattern", "sdso_trace_on_batch", "sdso_track_make_ref", "sdso_track_newest_coarse_batch", "sdso_track_get_ref",
     "sdso_ba_get_post_state", "sdso_ba_batch_keep_system", "sdso_ba_get_stitched", "sdso_ba_batch_exchange_mode", "sdso_ba_resubstitute", "sdso_ba_get_counts", "sdso_ba_calc_energies", "sdso_ba_get_deltas", "sdso_ba_marginalize_frame_dev", "sdso_ba_adopt_prior",
-    "sdso_ba_window_plan", "sdso_ba_window_update", "sdso_ba_window_get_order",
+    "sdso_ba_window_plan", "sdso_ba_window_update", "sdso_ba_window_update_activated", "sdso_ba_window_get_order",
     "sdso_ba_batch_optimize", "sdso_ba_batch_optimize_begin", "sdso_ba_batch_step", "sdso_ba_batch_solve_step", "sdso_ba_batch_optimize_end", "sdso_ba_get_state",
     "sdso_comm_unique_id", "sdso_comm_init", "sdso_comm_init_host", "sdso_comm_attach", "sdso_comm_info", "sdso_comm_destroy", "sdso_ba_allreduce", "sdso_ba_allreduce_window",
     "sdso_g2o_track_add_edges", "sdso_g2o_track_linearize", "sdso_g2o_track_newest_coarse", "sdso_g2o_lba_eval", "sdso_trace_set_gn_mode",
-    "sdso_distmap_make", "sdso_distmap_add", "sdso_distmap_get", "sdso_activate_select",
+    "sdso_distmap_make", "sdso_distmap_make_from_window", "sdso_distmap_add", "sdso_distmap_get", "sdso_activate_select",
     "sdso_undistort_make_remap", "sdso_ingest_calib_create", "sdso_ingest_calib_release", "sdso_ingest_frame",
     "sdso_init_set_first_stereo", "sdso_init_get_pnts", "sdso_init_from_initializer", "sdso_init_get_points", "sdso_init_release",
     "sdso_imm_add_frame", "sdso_imm_trace", "sdso_imm_count", "sdso_imm_get", "sdso_imm_remove_order", "sdso_imm_remove", "sdso_imm_release_host",
@@ -805,6 +807,24 @@ class Context:
         rc, counts = self.imm_activate_raw(host_id, *args, **kw)
         self.check(rc)
         return counts, self.imm_activate_fetch(int(counts[0]), int(counts[4]), len(host_id))
+
+    def distmap_make_from_window(self, wid, w, h, KRKi, Kt, skip=None, count=True):
+        """sdso_distmap_make_from_window -> (return code, n_seeds); count=False passes n_seeds = NULL (no synchronisation) -> (rc, None).
+        KRKi = None passes a null geom."""
+        G = None if KRKi is None else make_distmap_geoms(KRKi, Kt)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+        n = C.c_int(-1)
+        rc = self.L.sdso_distmap_make_from_window(self.h, wid, w, h, G, None if sk is None else bp(sk), C.byref(n) if count else None)
+        return rc, (n.value if count else None)
+
+    def window_update_activated(self, wid, E, act_frame, cap):
+        """sdso_ba_window_update_activated with the BAWindowEdit E -> (return code, n_points, n_res, act_index); act_frame = None passes a
+        null map; cap: entries act_index is sized for (counts[4] of the activation)."""
+        af = None if act_frame is None else np.ascontiguousarray(act_frame, np.int32)
+        n_pt, n_res = C.c_int(-1), C.c_int(-1)
+        idx = np.full(max(1, cap), -1, np.int32)
+        rc = self.L.sdso_ba_window_update_activated(self.h, wid, C.byref(E), None if af is None else ip(af), C.byref(n_pt), C.byref(n_res), ip(idx))
+        return rc, n_pt.value, n_res.value, idx[:max(0, n_pt.value)]
 
     def flag_points(self, wid, nf, npts, frame_marg, last_gone=None, **settings):
         """sdso_ba_flag_points -> (decision [np], counts [6], host_counts [nf, 6])."""
