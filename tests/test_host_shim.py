@@ -5,6 +5,10 @@ stand-ins that carry the reference's member names, goes through the shim, and pr
 problems pushed through the C-ABI from Python must give the same numbers (identical code path on the
 device, so equality is exact up to the %.17g / %.9g round trip of the printout)."""
 import ctypes as C
+import glob
+import os
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -23,6 +27,27 @@ def _run(d, what, arrays):
 def test_shim_header_compiles():
     """CPU: the shim + driver compile against the ABI header with the plain host compiler."""
     shim_driver.rebuild("test_shim")
+
+
+_PARTS = sorted(glob.glob(os.path.join(shim_driver.HOST, "shim", "*.h")))
+
+
+@pytest.mark.parametrize("part", _PARTS, ids=[os.path.basename(p) for p in _PARTS])
+def test_shim_part_compiles_alone(part):
+    """CPU: sdso_shim.h is an umbrella over host/shim/*.h, one part per concern.  Every part compiles as the only file of a translation
+    unit, whatever order a caller includes the parts in.  Like test_shim_header_compiles, it fails where there is no host compiler."""
+    r = subprocess.run([os.environ.get("CXX") or shutil.which("g++") or "g++", "-std=c++17", "-Wall", "-fsyntax-only", "-x", "c++", part], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+    # (a header given as the main file draws "#pragma once in main file", which says nothing about the header)
+    assert [ln for ln in r.stderr.splitlines() if "warning:" in ln and "#pragma once in main file" not in ln] == [], r.stderr[-4000:]
+
+
+def test_shim_parts_are_all_there():
+    """one part per concern, under the names the umbrella includes"""
+    names = {"device", "marshal", "tracker", "windowed_ba", "accumulators", "immature", "activation", "selector", "init", "undistort", "map"}
+    assert {os.path.basename(p)[:-2] for p in _PARTS} == names
+    umbrella = open(os.path.join(shim_driver.HOST, "sdso_shim.h")).read()
+    assert all('#include "shim/%s.h"' % n in umbrella for n in names)
 
 
 @pytest.mark.gpu
