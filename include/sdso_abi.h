@@ -244,6 +244,56 @@ int sdso_track_depth_image(sdso_ctx* ctx, int ref_slot, int frame_slot, float* m
 int sdso_track_depth_image_dev(sdso_ctx* ctx, int ref_slot, void** rgb_dev /* uint8_t*, w*h*3 */, void** idepth_dev /* float*, w*h */,
                                int* w, int* h);
 
+/* ------------------------------------------------------------------ hand-off between contexts
+ * The reference hands two objects from one mutex domain to the other: the tracked frame (fh, fh_right), built under trackMutex and
+ * queued for mappingLoop by deliverTrackedFrame (FullSystem.cpp:1203-1221), and the tracking template, built by makeKeyFrame on
+ * coarseTracker_forNewKF and swapped in by the tracking thread (FullSystem.cpp:1102-1109).  Each domain has a ctx of its own (one
+ * thread per ctx); the calls below pass the device buffers of a pyramid or a template from one ctx to any number of others ON THE SAME
+ * DEVICE without a copy and without a trip through the host.
+ *
+ * sdso_shared is an opaque handle on one reference to a block of level buffers.  It may be passed between threads; every call below
+ * is safe from any thread for DIFFERENT ctxs, and follows the one-thread-per-ctx rule for the ctx it names.
+ *   frozen    : from its first export on a block is never written again, by any ctx.  A call that would fill the buffers of a slot
+ *               that views such a block in place (sdso_upload_pyramid / sdso_make_pyramid / sdso_ingest_frame of the same size,
+ *               sdso_track_set_ref, sdso_track_make_ref*, the first-frame template) gives the slot fresh buffers first and leaves
+ *               the block to its other holders; sdso_track_set_ref, which replaces one level, copies the slot's other levels over.
+ *               A slot that was never exported from or imported into keeps its buffers and their reuse exactly as before.
+ *   lifetime  : the holders of a block are the slots that view it and the handles not yet released.  sdso_release_pyramid,
+ *               sdso_track_release_ref, sdso_ctx_destroy, a detaching write and sdso_shared_release each drop one reference; the
+ *               memory is freed by whoever drops the last one, after all work that any holder enqueued on the block has completed
+ *               (a holder that leaves with work in flight leaves an event behind).  A handle outlives its source slot and its
+ *               source ctx.
+ *   per ctx   : what a ctx derives from a pyramid (the tiled and planar level-0 copies, the pixel selector's map) or keeps next to a
+ *               template (the kept level-0 map, the STEP1 records of sdso_track_make_ref_from_window) is that ctx's own and does not
+ *               travel: on an imported template sdso_track_depth_image and sdso_track_get_ref_points return SDSO_ERR_STATE, as on a
+ *               template without a kept map / not built from a window.
+ *   gamma     : a pyramid carries the absSquaredGrad weighting (sdso_set_gamma) of the ctx that BUILT it, whatever the importer's.
+ *   refusals  : SDSO_ERR_ARG before any device work: a null argument, an unknown source slot, a handle of the other kind, a
+ *               destination ctx on another device than the block's (peer copies are out of scope: frames are replicated per GPU). */
+typedef struct sdso_shared sdso_shared;
+/* fh / fh_right as deliverTrackedFrame queues them (FullSystem.cpp:1203-1221).  Runs on the source's thread; *out is one more holder
+ * of the slot's buffers.  Enqueues one event on the source's stream behind everything enqueued so far (the pyramid may still be on its
+ * way, as after sdso_ingest_frame); no host wait. */
+int sdso_pyramid_export(sdso_ctx* src, int frame_slot, sdso_shared** out);
+/* mappingLoop taking the frame from unmappedTrackedFrames (FullSystem.cpp:1203-1221).  Runs on the destination's thread: the slot
+ * gives up what it held and views the block; the destination's stream waits for the export's event.  No copy; no host wait unless
+ * the slot held buffers of its own, which are freed as by sdso_release_pyramid.  One handle may be imported into any number of ctxs
+ * and slots, the source ctx under another slot included, also after the source slot or ctx is gone. */
+int sdso_pyramid_import(sdso_ctx* dst, int frame_slot, sdso_shared* h);
+/* coarseTracker_forNewKF as makeKeyFrame leaves it for the swap of FullSystem.cpp:1102-1109.  As sdso_pyramid_export; waits for the
+ * template's counts (pc_n) if they are still on their way, and for nothing else. */
+int sdso_track_export_ref(sdso_ctx* src, int ref_slot, sdso_shared** out);
+/* the swap of FullSystem.cpp:1102-1109 on the tracking thread's ctx.  As sdso_pyramid_import: the slot views the block's levels with
+ * their counts.  (A slot that held a template of its own, or a ctx with sdso_g2o_track_* edge sets, frees those behind a wait.) */
+int sdso_track_import_ref(sdso_ctx* dst, int ref_slot, sdso_shared* h);
+/* kind: 0 pyramid, 1 template; holders: slots + handles (FullSystem.cpp:1203-1221: the queue's entry counts as one) */
+int sdso_shared_info(const sdso_shared* h, int* kind, int* device, int* holders);
+/* the handle's reference goes (FullSystem.cpp:1203-1221: the frame leaves the queue); the handle is invalid afterwards */
+void sdso_shared_release(sdso_shared* h);
+/* tests / debugging of the hand-off (FullSystem.cpp:1203-1221): the device addresses behind a slot (SDSO_PYR_LEVELS entries; kind as
+ * above) and whether they are a view of an exported block.  They stay the same across in-place rebuilds of a slot nobody exported. */
+int sdso_shared_debug_buffers(sdso_ctx* ctx, int kind, int slot, unsigned long long* addr, int* is_view /* may be NULL */);
+
 /* Host-only helper (no GPU work): fill the evaluation parameters for (level, pose, affine) the way
  * CoarseTracker::makeK (:108-136) and calcRes (:617-621) derive them; cutoffTH =
  * prm->coarseCutoffTH * levelCutoffRepeat. Declared after sdso_track_params_t below. */

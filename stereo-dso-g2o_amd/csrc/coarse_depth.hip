@@ -197,6 +197,7 @@ int track_make_ref_dev(sdso_ctx* ctx, int ref_slot, int frame_slot, int n, const
   if (!R.counts_ev) SDSO_HIP(ctx, hipEventCreateWithFlags(&R.counts_ev, hipEventDisableTiming));
   rc = ref_counts(ctx, R);   // (a template of this slot still on its way: its counts are about to be replaced)
   if (rc) return rc;
+  ref_detach(ctx, R);   // a view of an exported (frozen) block is left to its other holders: every level is allocated below
   // the templates: kept while they are large enough (earlier kernels that read them are ahead of the scatter on the stream)
   int need[SDSO_PYR_LEVELS] = {0, 0, 0, 0, 0, 0};
   for (int l = 0; l < L; l++) {

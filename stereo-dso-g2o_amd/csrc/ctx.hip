@@ -133,8 +133,10 @@ extern "C" int sdso_ctx_create(int device_ordinal, sdso_ctx** out) {
   return SDSO_OK;
 }
 
+// (the caller has synchronised the stream)
 static void free_pyramid(PyramidDev& P) {
-  for (int l = 0; l < P.levels; l++) hipFree(P.d[l]);
+  if (P.blk) { share_drop(P.blk, nullptr, false); P.blk = nullptr; }
+  else for (int l = 0; l < P.levels; l++) hipFree(P.d[l]);
   if (P.tiled0) hipFree(P.tiled0);
   if (P.plane0) hipFree(P.plane0);
 }
@@ -268,9 +270,13 @@ extern "C" int sdso_release_pyramid(sdso_ctx* ctx, int frame_slot) {
   if (!ctx) return SDSO_ERR_STATE;
   auto it = ctx->pyr.find(frame_slot);
   if (it == ctx->pyr.end()) return SDSO_OK;
-  SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  PyramidDev& P = it->second;
+  // a view with no derived copy of the ctx's own has nothing to free here: the event share_drop leaves in the block stands for the wait
+  const bool wait = !P.blk || P.tiled0 || P.plane0;
+  if (wait) SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   selector_forget_slot(ctx, frame_slot);
-  free_pyramid(it->second);
+  if (P.blk && !wait) { share_drop(P.blk, ctx->stream, true); P.blk = nullptr; P.levels = 0; }
+  free_pyramid(P);
   ctx->pyr.erase(it);
   return SDSO_OK;
 }
@@ -278,19 +284,34 @@ extern "C" int sdso_release_pyramid(sdso_ctx* ctx, int frame_slot) {
 static int alloc_pyramid(sdso_ctx* ctx, int frame_slot, int levels, const int* w, const int* h) {
   SDSO_REQUIRE(ctx, levels >= 1 && levels <= SDSO_PYR_LEVELS, "levels out of range");
   auto it = ctx->pyr.find(frame_slot);
+  PyramidDev P;
   if (it != ctx->pyr.end()) {
     bool same = it->second.levels == levels;
     for (int l = 0; same && l < levels; l++) same = it->second.w[l] == w[l] && it->second.h[l] == h[l];
-    if (same) { selector_forget_slot(ctx, frame_slot); it->second.tiled_ok = false; it->second.plane_ok = false; return SDSO_OK; }   // new content arrives in the same buffers
-    int rc = sdso_release_pyramid(ctx, frame_slot);
-    if (rc) return rc;
+    if (same) {
+      selector_forget_slot(ctx, frame_slot); it->second.tiled_ok = false; it->second.plane_ok = false;
+      if (!it->second.blk) return SDSO_OK;   // new content arrives in the same buffers
+      // the levels are a view of an exported block, which is frozen: the slot detaches — it leaves the block to its other holders (no
+      // host wait: share_drop records what this ctx still runs on it) and takes fresh level buffers; its own tiled0 / plane0 stay
+      share_drop(it->second.blk, ctx->stream, true);
+      P.tiled0 = it->second.tiled0; P.plane0 = it->second.plane0;
+      ctx->pyr.erase(it);
+    } else {
+      int rc = sdso_release_pyramid(ctx, frame_slot);
+      if (rc) return rc;
+    }
   }
-  PyramidDev P;
   P.levels = levels;
-  for (int l = 0; l < levels; l++) {
-    SDSO_REQUIRE(ctx, w[l] >= 8 && h[l] >= 8, "pyramid level too small");
+  int rc = SDSO_OK;
+  for (int l = 0; l < levels && !rc; l++) {
     P.w[l] = w[l]; P.h[l] = h[l];
-    SDSO_HIP(ctx, hipMalloc(&P.d[l], sizeof(float4) * (size_t)w[l] * h[l]));
+    if (w[l] < 8 || h[l] < 8) rc = sdso::fail(ctx, SDSO_ERR_ARG, "pyramid level too small");
+    else if (hipMalloc(&P.d[l], sizeof(float4) * (size_t)w[l] * h[l]) != hipSuccess) { P.d[l] = nullptr; rc = sdso::fail(ctx, SDSO_ERR_HIP, "hipMalloc of a pyramid level failed"); }
+  }
+  if (rc) {   // (the derived copies of a detached slot may still be read by enqueued work)
+    if (P.tiled0 || P.plane0) hipStreamSynchronize(ctx->stream);
+    free_pyramid(P);
+    return rc;
   }
   ctx->pyr[frame_slot] = P;
   return SDSO_OK;

@@ -44,8 +44,15 @@ struct RefRecDev {
   __host__ __device__ uint8_t* bytes(int k) const { return u8 + (size_t)k * cap; }
   __host__ __device__ int* counts() const { return i32 + (size_t)RW_NINT * cap; }
 };
-struct RefRecSet { RefRecDev d{nullptr, nullptr, nullptr, 0}; int n = 0; };
+// stale: the slot has taken a template from elsewhere since (sdso_track_import_ref): the records are not that template's
+struct RefRecSet { RefRecDev d{nullptr, nullptr, nullptr, 0}; int n = 0; bool stale = false; };
 struct RefWinState { std::map<int, RefRecSet> sets; };
+
+void refwin_forget_slot(sdso_ctx* ctx, int ref_slot) {
+  if (!ctx->refwin) return;
+  auto it = ctx->refwin->sets.find(ref_slot);
+  if (it != ctx->refwin->sets.end()) it->second.stale = true;   // (the buffers stay for the slot's next sdso_track_make_ref_from_window)
+}
 
 void release_refwin(sdso_ctx* ctx) {
   if (!ctx->refwin) return;
@@ -189,6 +196,7 @@ extern "C" int sdso_track_make_ref_from_window(sdso_ctx* ctx, int ref_slot, int 
   // ---- STEP1 gather
   if (!ctx->refwin) ctx->refwin = new RefWinState();
   RefRecSet& S = ctx->refwin->sets[ref_slot];
+  S.stale = false;
   rc = reserve_records(ctx, S, std::max(n_items, 1));
   if (rc) return rc;
   const RefRecDev R = S.d;
@@ -223,7 +231,7 @@ extern "C" int sdso_track_get_ref_points(sdso_ctx* ctx, int ref_slot, int* n, in
   if (!ctx) return SDSO_ERR_STATE;
   SDSO_HIP(ctx, hipSetDevice(ctx->device));
   auto it = ctx->refwin ? ctx->refwin->sets.find(ref_slot) : std::map<int, RefRecSet>::iterator();
-  if (!ctx->refwin || it == ctx->refwin->sets.end()) return sdso::fail(ctx, SDSO_ERR_STATE, "no sdso_track_make_ref_from_window has run on this reference slot");
+  if (!ctx->refwin || it == ctx->refwin->sets.end() || it->second.stale) return sdso::fail(ctx, SDSO_ERR_STATE, "no sdso_track_make_ref_from_window has run on this reference slot");
   const RefRecSet& S = it->second;
   if (n) *n = S.n;
   if (S.n == 0) return SDSO_OK;

@@ -11,6 +11,7 @@
 #include <vector>
 #include "../../include/sdso_abi.h"
 #include "tile0_layout.h"
+#include "share.h"
 
 namespace sdso {
 
@@ -25,11 +26,37 @@ namespace sdso {
 constexpr float kHuberTH = 9.0f;                 // settings.cpp:95
 constexpr float kOutlierTHSumComponent = 2500.f; // settings.cpp:73
 
+// The level buffers of an exported pyramid / template (share.h, share.hip): reference-counted, frozen, viewed by slots of any ctx on
+// the device.  A slot whose `blk` is null owns its buffers alone, as every slot did before sdso_*_export existed.
+struct HipShareBackend {   // share.h's backend
+  typedef hipEvent_t Event;
+  typedef hipStream_t Stream;
+  int event_create(Event* e) { return hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess ? 0 : 1; }
+  void event_destroy(Event e) { hipEventDestroy(e); }
+  int event_record(Event e, Stream s) { return hipEventRecord(e, s) == hipSuccess ? 0 : 1; }
+  int event_wait(Event e) { return hipEventSynchronize(e) == hipSuccess ? 0 : 1; }
+  int stream_wait(Stream s, Event e) { return hipStreamWaitEvent(s, e, 0) == hipSuccess ? 0 : 1; }
+  int stream_sync(Stream s) { return hipStreamSynchronize(s) == hipSuccess ? 0 : 1; }
+  int alloc(void** p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess ? 0 : 1; }
+  // the last holder may be a handle released on a thread whose current device is another one
+  void free(void* p, int device) {
+    int cur = -1;
+    if (hipGetDevice(&cur) == hipSuccess && cur != device) { hipSetDevice(device); hipFree(p); hipSetDevice(cur); }
+    else hipFree(p);
+  }
+};
+typedef share::Block<HipShareBackend> ShareBlock;
+// the slot gives up its view of `blk`; unsynced: work the ctx enqueued on it may still run on `stream` (an event is left in the block
+// for whoever frees it), false after a stream synchronisation
+void share_drop(ShareBlock* blk, hipStream_t stream, bool unsynced);
+
 // A pyramid level on the device: one float4 {I, dx, dy, 0} per pixel (16-byte taps).
 struct PyramidDev {
   int levels = 0;
   int w[SDSO_PYR_LEVELS] = {0}, h[SDSO_PYR_LEVELS] = {0};
   float4* d[SDSO_PYR_LEVELS] = {nullptr};
+  ShareBlock* blk = nullptr;   // non-null: d[] are views into this exported block and must not be written (alloc_pyramid detaches first)
+  // the two derived copies below are the ctx's own, built on its own stream, also where d[] is a view
   // level 0 once more as 12-byte pixels {I, dx, dy} in 5x2-pixel tiles (one 128-B line per tile, tile0_layout.h) for the BA
   // linearisation, built on first use
   char* tiled0 = nullptr;
@@ -43,6 +70,8 @@ struct RefDev {
   int n[SDSO_PYR_LEVELS] = {0};
   float4* pc[SDSO_PYR_LEVELS] = {nullptr};
   int cap[SDSO_PYR_LEVELS] = {0};   // entries pc[l] was allocated for (>= n[l])
+  ShareBlock* blk = nullptr;        // non-null: pc[] are views into this exported block and must not be written (ref_detach first)
+  // everything below is the ctx's own and is never shared
   // A template built on the device without waiting for it (track_make_ref_dev): its counts are on their way into `counts_host`
   // (pinned) behind `counts_ev`; ref_counts() brings n[] up to date.  Every reader of n[] calls it first.
   bool counts_pending = false;
@@ -167,13 +196,27 @@ inline int ref_counts(sdso_ctx* ctx, RefDev& R) {
   R.counts_pending = false;
   return SDSO_OK;
 }
+// the levels of a template leave the slot: its own buffers are freed, a view drops its reference (the caller has synchronised the stream)
+inline void ref_free_levels(RefDev& R) {
+  if (R.blk) { share_drop(R.blk, nullptr, false); R.blk = nullptr; }
+  else for (int l = 0; l < SDSO_PYR_LEVELS; l++) if (R.pc[l]) hipFree(R.pc[l]);
+  for (int l = 0; l < SDSO_PYR_LEVELS; l++) { R.pc[l] = nullptr; R.n[l] = 0; R.cap[l] = 0; }
+}
 inline void ref_free(RefDev& R) {
-  for (int l = 0; l < SDSO_PYR_LEVELS; l++) { if (R.pc[l]) hipFree(R.pc[l]); R.pc[l] = nullptr; R.n[l] = 0; R.cap[l] = 0; }
+  ref_free_levels(R);
   if (R.counts_host) hipHostFree(R.counts_host);
   if (R.counts_ev) hipEventDestroy(R.counts_ev);
   R.counts_host = nullptr; R.counts_ev = nullptr; R.counts_pending = false;
   if (R.dmap) hipFree(R.dmap);
   R.dmap = nullptr; R.dmap_w = R.dmap_h = 0; R.map_ok = R.image_ok = false;
+}
+// A writer is about to fill pc[] of a slot whose levels are a view: the slot leaves the frozen block to its other holders and starts
+// from no buffers at all.  No host wait: what this ctx still runs on the block is covered by the event share_drop leaves in it.
+inline void ref_detach(sdso_ctx* ctx, RefDev& R) {
+  if (!R.blk) return;
+  share_drop(R.blk, ctx->stream, true);
+  R.blk = nullptr;
+  for (int l = 0; l < SDSO_PYR_LEVELS; l++) { R.pc[l] = nullptr; R.n[l] = 0; R.cap[l] = 0; }
 }
 // ---- a frame slot as the entry points see it.  Every refusal is SDSO_ERR_ARG; nothing is launched or waited for before them.
 // Level 0 and the sizes of the pyramid in `frame_slot`; `unknown` is the caller's refusal text where it names the slot.

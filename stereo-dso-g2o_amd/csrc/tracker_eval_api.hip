@@ -13,6 +13,25 @@ extern "C" int sdso_track_set_ref(sdso_ctx* ctx, int ref_slot, int lvl, int n, c
   RefDev& R = ctx->refs[ref_slot];
   int rc0 = ref_counts(ctx, R);
   if (rc0) return rc0;
+  if (R.blk) {
+    // the levels are a view of an exported block, which is frozen: the slot detaches.  The call replaces ONE level, so the others come
+    // along as copies in buffers of the slot's own (enqueued before share_drop records what this ctx still runs on the block).
+    float4* own[SDSO_PYR_LEVELS] = {nullptr};
+    for (int l = 0; l < SDSO_PYR_LEVELS; l++) {
+      if (l == lvl || R.n[l] <= 0) continue;
+      hipError_t e = hipMalloc(&own[l], sizeof(float4) * (size_t)R.n[l]);
+      if (e == hipSuccess) e = hipMemcpyAsync(own[l], R.pc[l], sizeof(float4) * (size_t)R.n[l], hipMemcpyDeviceToDevice, ctx->stream);
+      if (e != hipSuccess) {
+        hipStreamSynchronize(ctx->stream);
+        for (int k = 0; k < SDSO_PYR_LEVELS; k++) if (own[k]) hipFree(own[k]);
+        return sdso::fail(ctx, SDSO_ERR_HIP, std::string("detaching the shared template: ") + hipGetErrorString(e));
+      }
+    }
+    int n_keep[SDSO_PYR_LEVELS];
+    for (int l = 0; l < SDSO_PYR_LEVELS; l++) n_keep[l] = R.n[l];
+    ref_detach(ctx, R);
+    for (int l = 0; l < SDSO_PYR_LEVELS; l++) if (own[l]) { R.pc[l] = own[l]; R.n[l] = R.cap[l] = n_keep[l]; }
+  }
   if (R.pc[lvl]) { SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream)); hipFree(R.pc[lvl]); R.pc[lvl] = nullptr; }
   R.n[lvl] = n; R.cap[lvl] = n;
   R.map_ok = R.image_ok = false;   // a template that came from the host has no level-0 map

@@ -33,8 +33,9 @@
 //   bool KeyFrameDisplay::refreshPC(bool canRefresh, float scaledTH, float absTH, int mode, float minBS, int sparsity)  IOWrapper/Pangolin/KeyFrameDisplay.h:66, .cpp:174-323
 //   void CoarseInitializer::setFirstStereo(CalibHessian*, FrameHessian* newFrameHessian, FrameHessian* newFrameHessian_Right)   FullSystem/CoarseInitializer.h:108, .cpp:838-1034
 //   STEP 3 of void FullSystem::initializeFromInitializer(FrameHessian* newFrame)                                  FullSystem/FullSystem.cpp:1533-1573
+//   the swap of coarseTracker / coarseTracker_forNewKF (CoarseTracker::exportRef / adoptRef) and the frames deliverTrackedFrame queues (Device::exportFrame / importFrame)   FullSystem/FullSystem.cpp:1102-1109, :1203-1221
 #pragma once
-#include "shim/device.h"        // Error, Device.  (One part per concern; this header is the whole layer, namespace sdso_shim.)
+#include "shim/device.h"        // Error, Shared, Device.  (One part per concern; this header is the whole layer, namespace sdso_shim.)
 #include "shim/marshal.h"       // the marshalling rules the parts share, each stated once
 #include "shim/tracker.h"       // CoarseTracker
 #include "shim/windowed_ba.h"   // WindowedBA, and in detail its bodies that touch only the pointer graph or plain buffers

@@ -7,6 +7,28 @@
 #include "../../../include/sdso_abi.h"
 namespace sdso_shim {
 struct Error : std::runtime_error { using std::runtime_error::runtime_error; };
+// One reference to an exported block of device buffers (sdso_shared): a frame's pyramid on its way from the tracking domain to the
+// mapping domain (FullSystem.cpp:1203-1221), or a tracking template on its way back (:1102-1109).  Move-only; may be handed to
+// another thread; the block lives while a slot of any Device or a Shared holds it.
+class Shared {
+ public:
+  Shared() = default;
+  explicit Shared(sdso_shared* h) : h_(h) {}
+  ~Shared() { sdso_shared_release(h_); }
+  Shared(Shared&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  Shared& operator=(Shared&& o) noexcept {
+    if (this != &o) { sdso_shared_release(h_); h_ = o.h_; o.h_ = nullptr; }
+    return *this;
+  }
+  Shared(const Shared&) = delete;
+  Shared& operator=(const Shared&) = delete;
+  sdso_shared* get() const { return h_; }
+  explicit operator bool() const { return h_ != nullptr; }
+  int holders() const { int n = 0; return sdso_shared_info(h_, nullptr, nullptr, &n) == SDSO_OK ? n : 0; }   // slots + handles
+
+ private:
+  sdso_shared* h_ = nullptr;
+};
 // One GPU + stream.  The reference serialises tracking under trackMutex and mapping under mapMutex;
 // use one Device per such domain (or one shared Device and the same mutexes).
 class Device {
@@ -28,6 +50,15 @@ class Device {
     check(sdso_upload_pyramid(ctx_, slot, levels, w, h, p.data()), "sdso_upload_pyramid");
   }
   void releaseFrame(int slot) { sdso_release_pyramid(ctx_, slot); }
+  // deliverTrackedFrame (FullSystem.cpp:1203-1221) between two Devices on one GPU: the domain that built or ingested the pyramid exports
+  // it, the other imports it under a slot of its own — no copy, no host wait, and the pyramid may still be on its way on the exporter's
+  // stream.  From the export on the buffers are frozen: a later upload / ingest into either slot goes to fresh buffers.
+  Shared exportFrame(int slot) {
+    sdso_shared* h = nullptr;
+    check(sdso_pyramid_export(ctx_, slot, &h), "sdso_pyramid_export");
+    return Shared(h);
+  }
+  void importFrame(int slot, const Shared& s) { check(sdso_pyramid_import(ctx_, slot, s.get()), "sdso_pyramid_import"); }
   // Multi-GPU: one process per GPU; rank 0 makes the id (static uniqueId()), the caller ships the 128 bytes to the other ranks,
   // then every rank calls commInit (collective).  RCCL is resolved at run time; a missing librccl is an error, not a fallback.
   static void uniqueId(unsigned char id[128]) {

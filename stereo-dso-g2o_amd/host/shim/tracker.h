@@ -134,6 +134,38 @@ template <class SE3T, class AffLightT, class Mat33T, class Vec3T> class CoarseTr
     }
     installRef_(lastRef, (int)iu.size(), iu.data(), iv.data(), nid.data(), wgt.data());
   }
+  // The swap of FullSystem.cpp:1102-1109 between two Devices.  The reference swaps the POINTERS coarseTracker / coarseTracker_forNewKF
+  // under coarseTrackerSwapMutex, after which the tracking thread calls into the object the mapping thread built; here each thread keeps
+  // its own tracker on its own Device, and the template travels: makeKeyFrame ends with exportRef() on coarseTracker_forNewKF (under
+  // the same mutex), the tracking thread's adoptRef() takes the place of the swap.  Device to device, no copy, no host wait.
+  struct TrackingRef {
+    Shared shared;                       // the template's levels
+    const void* lastRef = nullptr;       // FrameHessian* of the keyframe it was built on
+    int lastRef_slot = -1;               // ... and its pyramid slot ON THE BUILDER'S Device
+    int refFrameID = -1;
+    float ab_exposure = 0.f;
+    AffLightT lastRef_aff_g2l{};
+    int pc_n[SDSO_PYR_LEVELS] = {0, 0, 0, 0, 0, 0};
+  };
+  TrackingRef exportRef() {
+    TrackingRef r;
+    sdso_shared* h = nullptr;
+    dev_.check(sdso_track_export_ref(dev_.ctx(), ref_slot_, &h), "sdso_track_export_ref");
+    r.shared = Shared(h);
+    r.lastRef = lastRef_; r.lastRef_slot = lastRef_slot_; r.refFrameID = refFrameID;
+    r.ab_exposure = prm_.ref_exposure; r.lastRef_aff_g2l = lastRef_aff_g2l;
+    for (int l = 0; l < SDSO_PYR_LEVELS; l++) r.pc_n[l] = pc_n[l];
+    return r;
+  }
+  // works on a tracker built on ANOTHER Device (of the same GPU).  The kept level-0 map stays with the builder: the two debugPlot members
+  // throw on an adopting tracker as they do for a template without a map (the reference calls them on coarseTracker_forNewKF only).
+  void adoptRef(const TrackingRef& r) {
+    dev_.check(sdso_track_import_ref(dev_.ctx(), ref_slot_, r.shared.get()), "sdso_track_import_ref");
+    lastRef_aff_g2l = r.lastRef_aff_g2l;
+    newRef_(r.lastRef, r.lastRef_slot, r.refFrameID, r.ab_exposure, r.lastRef_aff_g2l);
+    adopted_ = true;
+    for (int l = 0; l < SDSO_PYR_LEVELS; l++) pc_n[l] = r.pc_n[l];
+  }
   // void debugPlotIDepthMap(float* minID_pt, float* maxID_pt, std::vector<IOWrap::Output3DWrapper*>& wraps) — CoarseTracker.cpp:1071-1176,
   // what FullSystem::makeKeyFrame calls on coarseTracker_forNewKF for every keyframe (FullSystem.cpp:1444).  The sort of :1078-1088, the
   // smoothing of :1094-1117 and the image of :1119-1163 run on the device on the map the latest template kept (sdso_track_depth_image);
@@ -231,7 +263,7 @@ template <class SE3T, class AffLightT, class Mat33T, class Vec3T> class CoarseTr
   }
   // The bookkeeping after a new template (:821-825); lastRef is null where the caller gave a slot only.  Only the frame form keeps lastRef_aff_g2l.
   void newRef_(const void* lastRef, int lastRef_slot, int refFrameID_, float ab_exposure, const AffLightT& aff_g2l) {
-    lastRef_ = lastRef; lastRef_slot_ = lastRef_slot; idepth0_ok_ = false;
+    lastRef_ = lastRef; lastRef_slot_ = lastRef_slot; idepth0_ok_ = false; adopted_ = false;
     refFrameID = refFrameID_;
     prm_.ref_exposure = ab_exposure;
     prm_.ref_aff_g2l.a = aff_g2l.a; prm_.ref_aff_g2l.b = aff_g2l.b;
@@ -243,13 +275,14 @@ template <class SE3T, class AffLightT, class Mat33T, class Vec3T> class CoarseTr
   }
   void requireMap_(const char* who) const {
     if (!publish_) throw Error(std::string(who) + ": the tracker was constructed without publishDepthImages");
-    if (lastRef_slot_ < 0) throw Error(std::string(who) + ": no template built on the device is installed");
+    if (lastRef_slot_ < 0 || adopted_) throw Error(std::string(who) + ": no template built on the device is installed");
   }
   Device& dev_;
   int ref_slot_;
   bool publish_;
   const void* lastRef_ = nullptr;
   int lastRef_slot_ = -1;
+  bool adopted_ = false;                                     // the template came through adoptRef: lastRef_slot_ is the builder's, the map too
   std::vector<float> idepth0_;                               // idepth[0] on the host, as debugPlotIDepthMapFloat wraps it
   bool idepth0_ok_ = false;
   sdso_track_params_t prm_;

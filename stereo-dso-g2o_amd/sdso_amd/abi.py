@@ -581,6 +581,14 @@ def load():
     L.sdso_map_clear.argtypes = [vp]
     L.sdso_map_cloud.argtypes = [vp, C.POINTER(MapCloud), c_float_p, c_u8_p, c_int_p, c_int_p]
     L.sdso_map_cloud_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), c_int_p]
+    L.sdso_pyramid_export.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    L.sdso_pyramid_import.argtypes = [vp, C.c_int, vp]
+    L.sdso_track_export_ref.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    L.sdso_track_import_ref.argtypes = [vp, C.c_int, vp]
+    L.sdso_shared_info.argtypes = [vp, c_int_p, c_int_p, c_int_p]
+    L.sdso_shared_release.argtypes = [vp]
+    L.sdso_shared_release.restype = None
+    L.sdso_shared_debug_buffers.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_ulonglong), c_int_p]
     _lib = L
     return L
 
@@ -616,11 +624,32 @@ EXPORTED_SYMBOLS = [
     "sdso_track_keep_depth_map", "sdso_track_depth_image", "sdso_track_depth_image_dev",
     "sdso_map_update", "sdso_map_counts", "sdso_map_get", "sdso_map_put", "sdso_map_release_keyframe", "sdso_map_clear",
     "sdso_map_cloud", "sdso_map_cloud_dev",
+    "sdso_pyramid_export", "sdso_pyramid_import", "sdso_track_export_ref", "sdso_track_import_ref", "sdso_shared_info", "sdso_shared_release",
+    "sdso_shared_debug_buffers",
 ]
 
 
 class SdsoError(RuntimeError):
     pass
+
+
+class Shared:
+    """One reference to an exported block of level buffers (sdso_shared); release() drops it."""
+
+    def __init__(self, L, h):
+        self.L, self.h = L, h
+
+    def info(self):
+        """-> (kind: 0 pyramid / 1 template, device, holders: slots + handles)"""
+        k, d, n = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+        if self.L.sdso_shared_info(self.h, C.byref(k), C.byref(d), C.byref(n)) != 0:
+            raise SdsoError("sdso_shared_info on a released handle")
+        return k.value, d.value, n.value
+
+    def release(self):
+        if self.h:
+            self.L.sdso_shared_release(self.h)
+            self.h = None
 
 
 class Context:
@@ -940,6 +969,31 @@ class Context:
         if rc != 0:
             raise SdsoError("hipMemcpy from the device failed (%d)" % rc)
         return out
+
+    def export_pyramid(self, frame_slot):
+        """sdso_pyramid_export -> Shared (one more holder of the slot's level buffers)"""
+        h = C.c_void_p()
+        self.check(self.L.sdso_pyramid_export(self.h, frame_slot, C.byref(h)))
+        return Shared(self.L, h)
+
+    def import_pyramid(self, frame_slot, shared):
+        self.check(self.L.sdso_pyramid_import(self.h, frame_slot, shared.h))
+
+    def export_ref(self, ref_slot):
+        """sdso_track_export_ref -> Shared"""
+        h = C.c_void_p()
+        self.check(self.L.sdso_track_export_ref(self.h, ref_slot, C.byref(h)))
+        return Shared(self.L, h)
+
+    def import_ref(self, ref_slot, shared):
+        self.check(self.L.sdso_track_import_ref(self.h, ref_slot, shared.h))
+
+    def slot_buffers(self, kind, slot):
+        """sdso_shared_debug_buffers -> (device addresses of the SDSO_PYR_LEVELS level buffers, is_view)"""
+        a = (C.c_ulonglong * 6)()
+        v = C.c_int(0)
+        self.check(self.L.sdso_shared_debug_buffers(self.h, kind, slot, a, C.byref(v)))
+        return list(a), bool(v.value)
 
     def upload_pyramid(self, slot, pyr):
         n = len(pyr)
