@@ -294,6 +294,44 @@ void sdso_shared_release(sdso_shared* h);
  * above) and whether they are a view of an exported block.  They stay the same across in-place rebuilds of a slot nobody exported. */
 int sdso_shared_debug_buffers(sdso_ctx* ctx, int kind, int slot, unsigned long long* addr, int* is_view /* may be NULL */);
 
+/* ------------------------------------------------------------------ device buffer pool
+ * The hand-off above makes no copy, but the slots around it free and allocate: an import into slots that were the last holders of the
+ * previous frame frees its level buffers behind host waits, the builder's next build into an exported slot allocates fresh ones, and
+ * several paths synchronise a stream only so that a hipFree is safe.  A pool takes those calls off the per-frame path: with one
+ * attached, the level buffers of pyramids, their tiled / planar level-0 copies and the levels of tracking templates are PARKED when
+ * they leave a slot and handed out again to the next slot that asks for their size, of any ctx attached to the pool.
+ *   the rule   : a parked buffer carries the events of its earlier uses (the block's export event, the event of every holder that left
+ *                with work in flight, or one event the ctx records on its stream); whoever takes it has its stream wait for them (no
+ *                host wait), and nothing is passed to hipFree before they completed (sdso_pool_trim, the cap).
+ *   sizes      : pyramid levels and their level-0 copies by exact byte size; template levels take the smallest parked template level of
+ *                1 .. 2 times what they need, and fresh ones are rounded up to four size classes per power of two.
+ *   who waits  : nobody under the cap.  A buffer that does not fit under max_parked_bytes, after every completed parked buffer was
+ *                freed, is freed behind a host wait for its events (overflow_waits); the last reference to the pool waits for what is
+ *                pending and frees everything.
+ *   lifetime   : reference-counted: the caller (until sdso_pool_release), every attached ctx, every block exported by an attached
+ *                ctx.  The pool may be released while ctxs and handles still refer to it; a handle released last
+ *                (sdso_shared_release, no ctx) parks into its block's own pool.
+ *   not pooled : the kept depth map, BA windows, immature sets, the map, staging and scratch.
+ *   default    : a ctx has no pool, and every call does exactly what it did before pools existed.
+ *   refusals   : SDSO_ERR_ARG before any device work: a null argument, a pool of another device than the ctx's; SDSO_ERR_NODEV for a
+ *                device ordinal that does not exist. */
+typedef struct sdso_pool sdso_pool;
+/* hits / misses: buffers handed out from the parked ones / allocated; frees: buffers the pool passed to hipFree; host_waits: host
+ * waits made while parking or handing out (0 under the cap); overflow_waits: parks that did not fit; parked_*: what is parked now */
+typedef struct { long long hits, misses, frees, host_waits, overflow_waits; long long parked_buffers, parked_bytes; } sdso_pool_stats_t;
+/* an empty pool for the ctxs of one device; *out is the caller's reference.  No device work. */
+int sdso_pool_create(int device_ordinal, size_t max_parked_bytes, sdso_pool** out);
+/* From now on the ctx's level buffers come from and go to `pool` (NULL: none, as before sdso_ctx_set_pool).  Any time, any number of
+ * ctxs per pool; what the ctx holds stays where it is and is parked by byte size when it leaves, whoever allocated it.  Runs on the
+ * ctx's thread. */
+int sdso_ctx_set_pool(sdso_ctx* ctx, sdso_pool* pool);
+/* a snapshot; safe from any thread */
+int sdso_pool_stats(const sdso_pool* pool, sdso_pool_stats_t* out);
+/* frees parked buffers whose events have completed, oldest first, until at most keep_bytes stay parked; no host wait; any thread */
+int sdso_pool_trim(sdso_pool* pool, size_t keep_bytes);
+/* the caller's reference goes; the handle is invalid afterwards */
+void sdso_pool_release(sdso_pool* pool);
+
 /* Host-only helper (no GPU work): fill the evaluation parameters for (level, pose, affine) the way
  * CoarseTracker::makeK (:108-136) and calcRes (:617-621) derive them; cutoffTH =
  * prm->coarseCutoffTH * levelCutoffRepeat. Declared after sdso_track_params_t below. */

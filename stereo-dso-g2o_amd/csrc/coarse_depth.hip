@@ -204,13 +204,23 @@ int track_make_ref_dev(sdso_ctx* ctx, int ref_slot, int frame_slot, int n, const
     const long long area = (long long)std::max(P.w[l] - 4, 0) * std::max(P.h[l] - 4, 0);
     need[l] = (int)std::min<long long>(area, 5LL * n);
   }
+  if (ctx->pool) {   // the levels that have to grow leave for the pool behind one event on the stream: no host wait
+    void* out[SDSO_PYR_LEVELS] = {nullptr};
+    size_t out_bytes[SDSO_PYR_LEVELS] = {0};
+    for (int l = 0; l < SDSO_PYR_LEVELS; l++)
+      if (R.cap[l] < need[l] && R.pc[l]) { out[l] = R.pc[l]; out_bytes[l] = sizeof(float4) * (size_t)R.cap[l]; R.pc[l] = nullptr; R.cap[l] = 0; }
+    dev_park(ctx, pool::ROUNDED, SDSO_PYR_LEVELS, out, out_bytes, false);
+  }
   for (int l = 0; l < SDSO_PYR_LEVELS; l++) {
     if (R.cap[l] >= need[l]) continue;
     if (R.pc[l]) { SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream)); hipFree(R.pc[l]); R.pc[l] = nullptr; R.cap[l] = 0; }
     const long long area = (long long)std::max(P.w[l] - 4, 0) * std::max(P.h[l] - 4, 0);
     const int cap = (int)std::min<long long>(area, (long long)need[l] + need[l] / 4 + 1024);
-    SDSO_HIP(ctx, hipMalloc(&R.pc[l], sizeof(float4) * (size_t)cap));
-    R.cap[l] = cap;
+    // under a pool the request is `need` itself and pool.h's size classes are the slack: the buffer holds need .. 1.25 need entries
+    // (fresh) or up to 2 need (a parked template level), which may be more than STEP5 can ever keep; `cap` is what it holds
+    size_t got = 0;
+    SDSO_HIP(ctx, dev_acquire_rounded(ctx, (void**)&R.pc[l], sizeof(float4) * (size_t)need[l], sizeof(float4) * (size_t)cap, &got));
+    R.cap[l] = (int)(got / sizeof(float4));
   }
   // the kept level-0 map (sdso_track_keep_depth_map): one block per slot, kept while the size holds
   R.map_ok = R.image_ok = false;

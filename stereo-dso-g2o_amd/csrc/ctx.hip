@@ -97,7 +97,7 @@ namespace sdso {
 int ensure_plane0(sdso_ctx* ctx, PyramidDev& P) {
   if (P.plane_ok) return SDSO_OK;
   const int npix = P.w[0] * P.h[0];
-  if (!P.plane0) SDSO_HIP(ctx, hipMalloc(&P.plane0, sizeof(float) * (size_t)npix));
+  if (!P.plane0) SDSO_HIP(ctx, dev_acquire(ctx, (void**)&P.plane0, sizeof(float) * (size_t)npix));
   hipLaunchKernelGGL(k_plane0, dim3((npix + 255) / 256), dim3(256), 0, ctx->stream, (const float4*)P.d[0], P.plane0, npix);
   SDSO_HIP(ctx, hipGetLastError());
   P.plane_ok = true;
@@ -107,7 +107,7 @@ int ensure_tiled0(sdso_ctx* ctx, PyramidDev& P) {
   if (P.tiled_ok) return SDSO_OK;
   const int w = P.w[0], h = P.h[0];
   const size_t bytes = tile0_bytes(w, h), nwords = bytes / 4;
-  if (!P.tiled0) SDSO_HIP(ctx, hipMalloc(&P.tiled0, bytes));
+  if (!P.tiled0) SDSO_HIP(ctx, dev_acquire(ctx, (void**)&P.tiled0, bytes));
   hipLaunchKernelGGL(k_tile0, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)P.d[0], (float*)P.tiled0, w, h,
                      tile0_tiles_per_row(w), nwords);
   SDSO_HIP(ctx, hipGetLastError());
@@ -133,8 +133,19 @@ extern "C" int sdso_ctx_create(int device_ordinal, sdso_ctx** out) {
   return SDSO_OK;
 }
 
-// (the caller has synchronised the stream)
-static void free_pyramid(PyramidDev& P) {
+// synced: the caller has synchronised the stream (always, without a pool).  Under a pool nothing is freed: a view drops its reference
+// (the last holder parks the block), and what the ctx alone used is parked behind one event on its stream (none if `synced`).
+static void free_pyramid(sdso_ctx* ctx, PyramidDev& P, bool synced = true) {
+  if (ctx->pool) {
+    void* own[SDSO_PYR_LEVELS + 2] = {nullptr};
+    size_t bytes[SDSO_PYR_LEVELS + 2] = {0};
+    if (P.blk) { share_drop(P.blk, synced ? nullptr : ctx->stream, !synced, ctx->pool); P.blk = nullptr; }
+    else for (int l = 0; l < P.levels; l++) { own[l] = P.d[l]; bytes[l] = sizeof(float4) * (size_t)P.w[l] * P.h[l]; }
+    own[SDSO_PYR_LEVELS] = P.tiled0; bytes[SDSO_PYR_LEVELS] = tile0_bytes(P.w[0], P.h[0]);
+    own[SDSO_PYR_LEVELS + 1] = P.plane0; bytes[SDSO_PYR_LEVELS + 1] = sizeof(float) * (size_t)P.w[0] * P.h[0];
+    dev_park(ctx, pool::EXACT, SDSO_PYR_LEVELS + 2, own, bytes, synced);
+    return;
+  }
   if (P.blk) { share_drop(P.blk, nullptr, false); P.blk = nullptr; }
   else for (int l = 0; l < P.levels; l++) hipFree(P.d[l]);
   if (P.tiled0) hipFree(P.tiled0);
@@ -154,6 +165,7 @@ void release_init_stereo(sdso_ctx* ctx);
 void release_comm(sdso_ctx* ctx);
 void release_refwin(sdso_ctx* ctx);
 void release_map(sdso_ctx* ctx);
+void release_pool(sdso_ctx* ctx);   // pool.hip
 }
 
 extern "C" void sdso_ctx_destroy(sdso_ctx* ctx) {
@@ -163,8 +175,8 @@ extern "C" void sdso_ctx_destroy(sdso_ctx* ctx) {
   if (ctx->aux) { hipStreamSynchronize(ctx->aux); hipStreamDestroy(ctx->aux); ctx->aux = nullptr; }
   if (ctx->ev_main) hipEventDestroy(ctx->ev_main);
   if (ctx->ev_aux) hipEventDestroy(ctx->ev_aux);
-  for (auto& kv : ctx->pyr) free_pyramid(kv.second);
-  for (auto& kv : ctx->refs) ref_free(kv.second);
+  for (auto& kv : ctx->pyr) free_pyramid(ctx, kv.second);
+  for (auto& kv : ctx->refs) ref_free(ctx, kv.second);
   release_all_windows(ctx);
   for (auto& b : ctx->ba_pool) hipFree(b.first);
   release_track_batch(ctx);
@@ -178,6 +190,7 @@ extern "C" void sdso_ctx_destroy(sdso_ctx* ctx) {
   release_refwin(ctx);
   release_map(ctx);
   release_comm(ctx);
+  release_pool(ctx);   // the ctx's reference: what its slots held is parked by now (the last reference frees it)
   if (ctx->gammaB) hipFree(ctx->gammaB);
   if (ctx->scratch) hipFree(ctx->scratch);
   if (ctx->lm_clusters) hipFree(ctx->lm_clusters);
@@ -272,11 +285,15 @@ extern "C" int sdso_release_pyramid(sdso_ctx* ctx, int frame_slot) {
   if (it == ctx->pyr.end()) return SDSO_OK;
   PyramidDev& P = it->second;
   // a view with no derived copy of the ctx's own has nothing to free here: the event share_drop leaves in the block stands for the wait
-  const bool wait = !P.blk || P.tiled0 || P.plane0;
+  // (under a pool the ctx's own buffers are parked behind an event on its stream instead: no wait either way)
+  const bool wait = !ctx->pool && (!P.blk || P.tiled0 || P.plane0);
   if (wait) SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   selector_forget_slot(ctx, frame_slot);
-  if (P.blk && !wait) { share_drop(P.blk, ctx->stream, true); P.blk = nullptr; P.levels = 0; }
-  free_pyramid(P);
+  if (ctx->pool) free_pyramid(ctx, P, false);
+  else {
+    if (P.blk && !wait) { share_drop(P.blk, ctx->stream, true); P.blk = nullptr; P.levels = 0; }
+    free_pyramid(ctx, P);
+  }
   ctx->pyr.erase(it);
   return SDSO_OK;
 }
@@ -293,7 +310,7 @@ static int alloc_pyramid(sdso_ctx* ctx, int frame_slot, int levels, const int* w
       if (!it->second.blk) return SDSO_OK;   // new content arrives in the same buffers
       // the levels are a view of an exported block, which is frozen: the slot detaches — it leaves the block to its other holders (no
       // host wait: share_drop records what this ctx still runs on it) and takes fresh level buffers; its own tiled0 / plane0 stay
-      share_drop(it->second.blk, ctx->stream, true);
+      share_drop(it->second.blk, ctx->stream, true, ctx->pool);
       P.tiled0 = it->second.tiled0; P.plane0 = it->second.plane0;
       ctx->pyr.erase(it);
     } else {
@@ -306,11 +323,11 @@ static int alloc_pyramid(sdso_ctx* ctx, int frame_slot, int levels, const int* w
   for (int l = 0; l < levels && !rc; l++) {
     P.w[l] = w[l]; P.h[l] = h[l];
     if (w[l] < 8 || h[l] < 8) rc = sdso::fail(ctx, SDSO_ERR_ARG, "pyramid level too small");
-    else if (hipMalloc(&P.d[l], sizeof(float4) * (size_t)w[l] * h[l]) != hipSuccess) { P.d[l] = nullptr; rc = sdso::fail(ctx, SDSO_ERR_HIP, "hipMalloc of a pyramid level failed"); }
+    else if (dev_acquire(ctx, (void**)&P.d[l], sizeof(float4) * (size_t)w[l] * h[l]) != hipSuccess) { P.d[l] = nullptr; rc = sdso::fail(ctx, SDSO_ERR_HIP, "hipMalloc of a pyramid level failed"); }
   }
   if (rc) {   // (the derived copies of a detached slot may still be read by enqueued work)
-    if (P.tiled0 || P.plane0) hipStreamSynchronize(ctx->stream);
-    free_pyramid(P);
+    if (!ctx->pool && (P.tiled0 || P.plane0)) hipStreamSynchronize(ctx->stream);
+    free_pyramid(ctx, P, false);   // (`synced` is read under a pool only)
     return rc;
   }
   ctx->pyr[frame_slot] = P;

@@ -37,6 +37,13 @@ struct HipShareBackend {   // share.h's backend
   int event_wait(Event e) { return hipEventSynchronize(e) == hipSuccess ? 0 : 1; }
   int stream_wait(Stream s, Event e) { return hipStreamWaitEvent(s, e, 0) == hipSuccess ? 0 : 1; }
   int stream_sync(Stream s) { return hipStreamSynchronize(s) == hipSuccess ? 0 : 1; }
+  // non-blocking: 1 completed (pool.h).  "Not ready" is an answer, not an error: it must not be what a later hipGetLastError() after a
+  // kernel launch on this thread reports.
+  int event_query(Event e) {
+    const hipError_t r = hipEventQuery(e);
+    if (r == hipErrorNotReady) (void)hipGetLastError();
+    return r == hipSuccess ? 1 : 0;
+  }
   int alloc(void** p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess ? 0 : 1; }
   // the last holder may be a handle released on a thread whose current device is another one
   void free(void* p, int device) {
@@ -46,9 +53,11 @@ struct HipShareBackend {   // share.h's backend
   }
 };
 typedef share::Block<HipShareBackend> ShareBlock;
+typedef pool::Pool<HipShareBackend> DevPool;   // the device buffer pool (pool.h, pool.hip), attached by sdso_ctx_set_pool
 // the slot gives up its view of `blk`; unsynced: work the ctx enqueued on it may still run on `stream` (an event is left in the block
-// for whoever frees it), false after a stream synchronisation
-void share_drop(ShareBlock* blk, hipStream_t stream, bool unsynced);
+// for whoever frees it), false after a stream synchronisation.  The last holder parks the buffers in the block's own pool, or else in
+// `fallback` (the dropping ctx's pool), with no host wait; with neither it waits and frees, as ever.
+void share_drop(ShareBlock* blk, hipStream_t stream, bool unsynced, DevPool* fallback = nullptr);
 
 // A pyramid level on the device: one float4 {I, dx, dy, 0} per pixel (16-byte taps).
 struct PyramidDev {
@@ -134,6 +143,7 @@ struct sdso_ctx {
   sdso::RefWinState* refwin = nullptr;  // STEP1 records of sdso_track_make_ref_from_window, per reference slot
   sdso::MapState* map = nullptr;        // the device-resident map: the point lists of every keyframe (sdso_map_*)
   std::shared_ptr<sdso::Comm> comm;     // shared with the contexts joined by sdso_comm_attach
+  sdso::DevPool* pool = nullptr;        // sdso_ctx_set_pool (a reference of the ctx's own): where level buffers come from and go to; null: hipMalloc / hipFree
   // generic scratch
   void* scratch = nullptr;
   size_t scratch_bytes = 0;
@@ -188,6 +198,19 @@ inline int fail(sdso_ctx* ctx, int code, const std::string& msg) {
   } while (0)
 
 int ensure_scratch(sdso_ctx* ctx, size_t bytes);
+// ---- level buffers with or without a buffer pool (pool.hip).  Without one these are hipMalloc and `false`: the caller runs the code it
+// always ran.
+// `bytes` of device memory for a pyramid level or a level-0 copy (pool.h: EXACT), or at least `need` for a template level (ROUNDED;
+// *got = what the buffer holds; without a pool: exactly `unpooled` bytes, the slack the call always allocated); from the pool the
+// buffer comes ordered behind every earlier use on ctx->stream
+hipError_t dev_acquire(sdso_ctx* ctx, void** p, size_t bytes);
+hipError_t dev_acquire_rounded(sdso_ctx* ctx, void** p, size_t need, size_t unpooled, size_t* got);
+// n buffers of one kind (pyramid levels and level-0 copies: pool::EXACT; template levels: pool::ROUNDED; null entries skipped) that this ctx alone used leave for its pool behind ONE event recorded on ctx->stream (none if
+// `synced`: the caller has synchronised the stream); no host wait.  false: the ctx has no pool, nothing was done.
+bool dev_park(sdso_ctx* ctx, pool::Match kind, int n, void* const* bufs, const size_t* bytes, bool synced);
+inline size_t share_level_bytes(int kind, int dim0, int dim1) {   // a block's level buffer: w x h float4, or cap float4
+  return sizeof(float4) * (kind == share::KIND_PYRAMID ? (size_t)dim0 * dim1 : (size_t)dim1);
+}
 // n[] of a reference whose template was enqueued without a synchronisation: waits for that template's counts only
 inline int ref_counts(sdso_ctx* ctx, RefDev& R) {
   if (!R.counts_pending) return SDSO_OK;
@@ -196,14 +219,20 @@ inline int ref_counts(sdso_ctx* ctx, RefDev& R) {
   R.counts_pending = false;
   return SDSO_OK;
 }
-// the levels of a template leave the slot: its own buffers are freed, a view drops its reference (the caller has synchronised the stream)
-inline void ref_free_levels(RefDev& R) {
-  if (R.blk) { share_drop(R.blk, nullptr, false); R.blk = nullptr; }
-  else for (int l = 0; l < SDSO_PYR_LEVELS; l++) if (R.pc[l]) hipFree(R.pc[l]);
+// the levels of a template leave the slot: its own buffers are freed, a view drops its reference.  synced: the caller has synchronised
+// the stream (always, without a pool); with a pool the buffers are parked, behind an event on the stream unless `synced`.
+inline void ref_free_levels(sdso_ctx* ctx, RefDev& R, bool synced = true) {
+  if (R.blk) { share_drop(R.blk, synced ? nullptr : ctx->stream, !synced, ctx->pool); R.blk = nullptr; }
+  else {
+    size_t bytes[SDSO_PYR_LEVELS];
+    for (int l = 0; l < SDSO_PYR_LEVELS; l++) bytes[l] = sizeof(float4) * (size_t)R.cap[l];
+    if (!dev_park(ctx, pool::ROUNDED, SDSO_PYR_LEVELS, (void* const*)R.pc, bytes, synced))
+      for (int l = 0; l < SDSO_PYR_LEVELS; l++) if (R.pc[l]) hipFree(R.pc[l]);
+  }
   for (int l = 0; l < SDSO_PYR_LEVELS; l++) { R.pc[l] = nullptr; R.n[l] = 0; R.cap[l] = 0; }
 }
-inline void ref_free(RefDev& R) {
-  ref_free_levels(R);
+inline void ref_free(sdso_ctx* ctx, RefDev& R, bool synced = true) {
+  ref_free_levels(ctx, R, synced);
   if (R.counts_host) hipHostFree(R.counts_host);
   if (R.counts_ev) hipEventDestroy(R.counts_ev);
   R.counts_host = nullptr; R.counts_ev = nullptr; R.counts_pending = false;
@@ -214,7 +243,7 @@ inline void ref_free(RefDev& R) {
 // from no buffers at all.  No host wait: what this ctx still runs on the block is covered by the event share_drop leaves in it.
 inline void ref_detach(sdso_ctx* ctx, RefDev& R) {
   if (!R.blk) return;
-  share_drop(R.blk, ctx->stream, true);
+  share_drop(R.blk, ctx->stream, true, ctx->pool);
   R.blk = nullptr;
   for (int l = 0; l < SDSO_PYR_LEVELS; l++) { R.pc[l] = nullptr; R.n[l] = 0; R.cap[l] = 0; }
 }

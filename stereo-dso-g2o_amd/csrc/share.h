@@ -2,7 +2,8 @@
 // here: the device side is a backend B, so that test_share.cpp can run the same code on a backend that only logs.
 //
 // A block is the set of level buffers of one pyramid or one template.  Its holders are the slots that view it (of any ctx on its device)
-// and the handles (sdso_shared) that were exported and not yet released; it belongs to them and to nothing else (no registry, no pool).
+// and the handles (sdso_shared) that were exported and not yet released; it belongs to them and to nothing else (no registry).  A block
+// created by a ctx with a buffer pool (pool.h) also names that pool, and holds a reference to it: drop_pooled() parks there.
 //   - exported: set by the first export and never cleared.  From then on the block is FROZEN: no holder writes into it again; a slot
 //     that is about to write asks write_in_place() and, on false, detaches (drop() + fresh buffers of its own).
 //   - ready: recorded by the first export on the exporter's stream, behind everything that wrote the block; every importer makes its
@@ -19,11 +20,13 @@
 //   int  event_record(Event, Stream);  int  event_wait(Event);                 // host wait
 //   int  stream_wait(Stream, Event);   int  stream_sync(Stream);               // enqueue a wait / host wait for a whole stream
 //   int  alloc(void**, size_t);        void free(void* p, int device);
+// (drop_pooled and pool.h also need: int event_query(Event), non-blocking)
 #pragma once
 #include <atomic>
 #include <cstddef>
 #include <mutex>
 #include <vector>
+#include "pool.h"
 
 namespace sdso {
 namespace share {
@@ -44,6 +47,7 @@ struct Block {
   typename B::Event ready{};
   std::mutex mu;                        // guards `done`
   std::vector<typename B::Event> done;
+  pool::Pool<B>* pool = nullptr;        // the creator's buffer pool (a reference of the block's own), or null; written before the first export only
 };
 
 // the block of buffers a slot owns so far; the slot is its one holder
@@ -103,6 +107,34 @@ void drop(B& be, Block<B>* b, typename B::Stream s, bool unsynced) {
   if (b->has_ready) { be.event_wait(b->ready); be.event_destroy(b->ready); }
   for (auto& e : ev) { be.event_wait(e); be.event_destroy(e); }
   for (int l = 0; l < kMaxLevels; l++) if (b->buf[l]) be.free(b->buf[l], b->device);
+  delete b;
+}
+
+// drop() for a block that may end in a buffer pool: the block's own, or else `fallback` (the pool of the ctx that drops it; may be
+// null).  The last one out does NOT wait: `ready` and the `done` events move into the pool together with the buffers (pool.h: the next
+// taker's stream waits for them; nothing is freed before they completed).  bytes(kind, dim0, dim1) is the size of a level buffer.
+// Without any pool this is drop().
+template <class B, class Bytes>
+void drop_pooled(B& be, Block<B>* b, typename B::Stream s, bool unsynced, pool::Pool<B>* fallback, Bytes bytes) {
+  pool::Pool<B>* p = b->pool ? b->pool : fallback;
+  if (!p) { drop(be, b, s, unsynced); return; }
+  if (unsynced) {
+    typename B::Event e{};
+    bool recorded = false;
+    if (be.event_create(&e) == 0) {
+      if (be.event_record(e, s) == 0) recorded = true; else be.event_destroy(e);
+    }
+    if (recorded) { std::lock_guard<std::mutex> g(b->mu); b->done.push_back(e); }
+    else { be.stream_sync(s); p->count_host_wait(); }   // no event to leave behind: wait here instead (as drop() does)
+  }
+  if (b->holders.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
+  std::vector<typename B::Event> ev;
+  { std::lock_guard<std::mutex> g(b->mu); ev.swap(b->done); }
+  if (b->has_ready) ev.push_back(b->ready);
+  size_t sz[kMaxLevels];
+  for (int l = 0; l < kMaxLevels; l++) sz[l] = b->buf[l] ? bytes(b->kind, b->dim0[l], b->dim1[l]) : 0;
+  p->park(be, b->kind == KIND_TEMPLATE ? pool::ROUNDED : pool::EXACT, kMaxLevels, b->buf, sz, std::move(ev));
+  if (b->pool) b->pool->release(be);   // the block's reference (after the park: the pool may end here)
   delete b;
 }
 

@@ -6,9 +6,9 @@
 
 namespace sdso {
 
-void share_drop(ShareBlock* blk, hipStream_t stream, bool unsynced) {
+void share_drop(ShareBlock* blk, hipStream_t stream, bool unsynced, DevPool* fallback) {
   HipShareBackend be;
-  share::drop<HipShareBackend>(be, blk, stream, unsynced);
+  share::drop_pooled(be, blk, stream, unsynced, fallback, share_level_bytes);   // (share::drop itself where there is no pool)
 }
 
 void release_g2o_ref(sdso_ctx* ctx, int ref_slot);     // g2o_factors.hip
@@ -22,11 +22,18 @@ struct sdso_shared { ShareBlock* blk; };
 
 namespace {
 
+// the block of buffers a slot of `src` owns so far; under a pool the block names it and holds a reference to it
+ShareBlock* adopt_slot(sdso_ctx* src, int kind, int levels, void* const* bufs, const int* dim0, const int* dim1) {
+  ShareBlock* b = share::adopt<HipShareBackend>(kind, src->device, levels, bufs, dim0, dim1);
+  if (src->pool) { b->pool = src->pool; b->pool->retain(); }
+  return b;
+}
+
 // one more holder (the handle) behind everything `src` has enqueued; a block made for this export goes again if it fails
 int export_common(sdso_ctx* src, ShareBlock** slot_blk, ShareBlock* b, sdso_shared** out) {
   HipShareBackend be;
   if (share::export_ref<HipShareBackend>(be, b, src->stream)) {
-    if (!*slot_blk) delete b;   // (the buffers stay the slot's own)
+    if (!*slot_blk) { if (b->pool) b->pool->release(be); delete b; }   // (the buffers stay the slot's own)
     return sdso::fail(src, SDSO_ERR_HIP, "recording the export's ready event failed");
   }
   *slot_blk = b;
@@ -51,7 +58,7 @@ extern "C" int sdso_pyramid_export(sdso_ctx* src, int frame_slot, sdso_shared** 
   SDSO_TRY(frame_pyramid(src, frame_slot, &P));
   SDSO_HIP(src, hipSetDevice(src->device));
   ShareBlock* b = P->blk;
-  if (!b) b = share::adopt<HipShareBackend>(share::KIND_PYRAMID, src->device, P->levels, (void* const*)P->d, P->w, P->h);
+  if (!b) b = adopt_slot(src, share::KIND_PYRAMID, P->levels, (void* const*)P->d, P->w, P->h);
   return export_common(src, &P->blk, b, out);
 }
 
@@ -67,7 +74,7 @@ extern "C" int sdso_pyramid_import(sdso_ctx* dst, int frame_slot, sdso_shared* h
     selector_forget_slot(dst, frame_slot);
     if (O.blk && O.w[0] == b->dim0[0] && O.h[0] == b->dim1[0]) {
       // a view of the same size goes: no host wait, and the ctx's own derived buffers stay for the new image
-      share_drop(O.blk, dst->stream, true);
+      share_drop(O.blk, dst->stream, true, dst->pool);   // (the last holder under a pool parks the levels: no free, no wait)
       N.tiled0 = O.tiled0; N.plane0 = O.plane0;
       dst->pyr.erase(it);
     } else {
@@ -76,7 +83,9 @@ extern "C" int sdso_pyramid_import(sdso_ctx* dst, int frame_slot, sdso_shared* h
   }
   HipShareBackend be;
   if (share::import_ref<HipShareBackend>(be, b, dst->stream)) {
-    if (N.tiled0 || N.plane0) { hipStreamSynchronize(dst->stream); hipFree(N.tiled0); hipFree(N.plane0); }
+    void* own[2] = {N.tiled0, N.plane0};
+    const size_t own_bytes[2] = {tile0_bytes(b->dim0[0], b->dim1[0]), sizeof(float) * (size_t)b->dim0[0] * b->dim1[0]};
+    if ((N.tiled0 || N.plane0) && !dev_park(dst, pool::EXACT, 2, own, own_bytes, false)) { hipStreamSynchronize(dst->stream); hipFree(N.tiled0); hipFree(N.plane0); }
     return sdso::fail(dst, SDSO_ERR_HIP, "hipStreamWaitEvent on the block's ready event failed");
   }
   N.levels = b->levels;
@@ -96,7 +105,7 @@ extern "C" int sdso_track_export_ref(sdso_ctx* src, int ref_slot, sdso_shared** 
   RefDev& R = ir->second;
   SDSO_TRY(ref_counts(src, R));   // the block carries final counts: a wait for this template's counts only
   ShareBlock* b = R.blk;
-  if (!b) b = share::adopt<HipShareBackend>(share::KIND_TEMPLATE, src->device, SDSO_PYR_LEVELS, (void* const*)R.pc, R.n, R.cap);
+  if (!b) b = adopt_slot(src, share::KIND_TEMPLATE, SDSO_PYR_LEVELS, (void* const*)R.pc, R.n, R.cap);
   return export_common(src, &R.blk, b, out);
 }
 
@@ -108,10 +117,12 @@ extern "C" int sdso_track_import_ref(sdso_ctx* dst, int ref_slot, sdso_shared* h
   RefDev& R = dst->refs[ref_slot];
   bool own = false;
   for (int l = 0; l < SDSO_PYR_LEVELS; l++) own = own || (!R.blk && R.pc[l]);
-  if (own || dst->g2o) {   // buffers of the slot's own (or edge sets built on its template) are freed behind a wait, as ever
+  if (own && dst->pool && !dst->g2o) {
+    ref_free_levels(dst, R, false);   // under a pool the slot's own levels are parked behind an event: no host wait
+  } else if (own || dst->g2o) {   // buffers of the slot's own (or edge sets built on its template) are freed behind a wait, as ever
     SDSO_HIP(dst, hipStreamSynchronize(dst->stream));
     release_g2o_ref(dst, ref_slot);
-    ref_free_levels(R);
+    ref_free_levels(dst, R);
   } else {
     ref_detach(dst, R);    // a view goes with no host wait
   }

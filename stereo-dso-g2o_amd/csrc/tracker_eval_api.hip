@@ -48,9 +48,13 @@ extern "C" int sdso_track_release_ref(sdso_ctx* ctx, int ref_slot) {
   if (!ctx) return SDSO_ERR_STATE;
   auto it = ctx->refs.find(ref_slot);
   if (it == ctx->refs.end()) return SDSO_OK;
-  SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  // under a pool the levels are parked behind an event on the stream, with no stream synchronisation; what is not pooled (edge sets
+  // of the g2o factors, the kept depth map) is freed behind a wait, as ever
+  const bool nowait = ctx->pool && !ctx->g2o && !it->second.dmap;
+  if (nowait) SDSO_TRY(ref_counts(ctx, it->second));   // (the pinned counts go below: their copy, and nothing else, is waited for)
+  else SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   sdso::release_g2o_ref(ctx, ref_slot);
-  ref_free(it->second);
+  ref_free(ctx, it->second, !nowait);
   ctx->refs.erase(it);
   return SDSO_OK;
 }

@@ -29,6 +29,37 @@ class Shared {
  private:
   sdso_shared* h_ = nullptr;
 };
+// A device buffer pool (sdso_pool): with one attached (Device::setPool), the level buffers of pyramids, their level-0 copies and the
+// levels of tracking templates are parked when they leave a slot and handed out again behind stream waits — the hand-off of frames and
+// templates between two Devices then makes no allocator call and no host wait in its steady state.  Move-only; this object is the
+// caller's reference: the pool lives while it, an attached Device or a block exported under it does, so the order of destruction is free.
+class Pool {
+ public:
+  Pool() = default;
+  explicit Pool(int ordinal, size_t max_parked_bytes = (size_t)1 << 30) {
+    if (sdso_pool_create(ordinal, max_parked_bytes, &p_) != SDSO_OK) throw Error("sdso_pool_create failed: no such HIP device");
+  }
+  ~Pool() { sdso_pool_release(p_); }
+  Pool(Pool&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+  Pool& operator=(Pool&& o) noexcept {
+    if (this != &o) { sdso_pool_release(p_); p_ = o.p_; o.p_ = nullptr; }
+    return *this;
+  }
+  Pool(const Pool&) = delete;
+  Pool& operator=(const Pool&) = delete;
+  sdso_pool* get() const { return p_; }
+  explicit operator bool() const { return p_ != nullptr; }
+  sdso_pool_stats_t stats() const {
+    sdso_pool_stats_t s{};
+    if (sdso_pool_stats(p_, &s) != SDSO_OK) throw Error("sdso_pool_stats: no pool");
+    return s;
+  }
+  // frees parked buffers whose work has completed until at most keep_bytes stay parked; no host wait
+  void trim(size_t keep_bytes = 0) { if (sdso_pool_trim(p_, keep_bytes) != SDSO_OK) throw Error("sdso_pool_trim: no pool"); }
+
+ private:
+  sdso_pool* p_ = nullptr;
+};
 // One GPU + stream.  The reference serialises tracking under trackMutex and mapping under mapMutex;
 // use one Device per such domain (or one shared Device and the same mutexes).
 class Device {
@@ -59,6 +90,10 @@ class Device {
     return Shared(h);
   }
   void importFrame(int slot, const Shared& s) { check(sdso_pyramid_import(ctx_, slot, s.get()), "sdso_pyramid_import"); }
+  // From now on the level buffers of this Device's frames and templates come from and go to `pool` (of the same GPU; one pool serves
+  // both Devices of the threaded binding); clearPool(): hipMalloc / hipFree, as without a pool.  On this Device's thread, at any time.
+  void setPool(Pool& pool) { check(sdso_ctx_set_pool(ctx_, pool.get()), "sdso_ctx_set_pool"); }
+  void clearPool() { check(sdso_ctx_set_pool(ctx_, nullptr), "sdso_ctx_set_pool"); }
   // Multi-GPU: one process per GPU; rank 0 makes the id (static uniqueId()), the caller ships the 128 bytes to the other ranks,
   // then every rank calls commInit (collective).  RCCL is resolved at run time; a missing librccl is an error, not a fallback.
   static void uniqueId(unsigned char id[128]) {

@@ -278,6 +278,11 @@ class G2oLba(C.Structure):
                 ("u", c_float_p), ("v", c_float_p), ("idepth", c_double_p), ("color", c_float_p), ("weights", c_float_p)]
 
 
+class PoolStats(C.Structure):
+    """sdso_pool_stats_t: the counters of a device buffer pool."""
+    _fields_ = [(k, C.c_longlong) for k in ("hits", "misses", "frees", "host_waits", "overflow_waits", "parked_buffers", "parked_bytes")]
+
+
 def fp(a):
     return a.ctypes.data_as(c_float_p)
 
@@ -589,6 +594,12 @@ def load():
     L.sdso_shared_release.argtypes = [vp]
     L.sdso_shared_release.restype = None
     L.sdso_shared_debug_buffers.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_ulonglong), c_int_p]
+    L.sdso_pool_create.argtypes = [C.c_int, C.c_size_t, C.POINTER(vp)]
+    L.sdso_ctx_set_pool.argtypes = [vp, vp]
+    L.sdso_pool_stats.argtypes = [vp, C.POINTER(PoolStats)]
+    L.sdso_pool_trim.argtypes = [vp, C.c_size_t]
+    L.sdso_pool_release.argtypes = [vp]
+    L.sdso_pool_release.restype = None
     _lib = L
     return L
 
@@ -626,6 +637,7 @@ EXPORTED_SYMBOLS = [
     "sdso_map_cloud", "sdso_map_cloud_dev",
     "sdso_pyramid_export", "sdso_pyramid_import", "sdso_track_export_ref", "sdso_track_import_ref", "sdso_shared_info", "sdso_shared_release",
     "sdso_shared_debug_buffers",
+    "sdso_pool_create", "sdso_ctx_set_pool", "sdso_pool_stats", "sdso_pool_trim", "sdso_pool_release",
 ]
 
 
@@ -649,6 +661,34 @@ class Shared:
     def release(self):
         if self.h:
             self.L.sdso_shared_release(self.h)
+            self.h = None
+
+
+class Pool:
+    """The caller's reference to a device buffer pool (sdso_pool); release() drops it.  Attach ctxs with Context.set_pool."""
+
+    def __init__(self, device=0, max_parked_bytes=1 << 30):
+        self.L = load()
+        h = C.c_void_p()
+        rc = self.L.sdso_pool_create(device, max_parked_bytes, C.byref(h))
+        if rc != 0:
+            raise SdsoError("sdso_pool_create(%d) failed with %d" % (device, rc))
+        self.h = h
+
+    def stats(self):
+        """sdso_pool_stats -> dict of the counters"""
+        st = PoolStats()
+        if self.L.sdso_pool_stats(self.h, C.byref(st)) != 0:
+            raise SdsoError("sdso_pool_stats on a released pool")
+        return {k: getattr(st, k) for k, _ in PoolStats._fields_}
+
+    def trim(self, keep_bytes=0):
+        if self.L.sdso_pool_trim(self.h, keep_bytes) != 0:
+            raise SdsoError("sdso_pool_trim on a released pool")
+
+    def release(self):
+        if self.h:
+            self.L.sdso_pool_release(self.h)
             self.h = None
 
 
@@ -987,6 +1027,10 @@ class Context:
 
     def import_ref(self, ref_slot, shared):
         self.check(self.L.sdso_track_import_ref(self.h, ref_slot, shared.h))
+
+    def set_pool(self, pool):
+        """sdso_ctx_set_pool; None detaches"""
+        self.check(self.L.sdso_ctx_set_pool(self.h, pool.h if pool is not None else None))
 
     def slot_buffers(self, kind, slot):
         """sdso_shared_debug_buffers -> (device addresses of the SDSO_PYR_LEVELS level buffers, is_view)"""
