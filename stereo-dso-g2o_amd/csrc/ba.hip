@@ -12,7 +12,7 @@
 //   ba_loop.hip    both Gauss-Newton loops: the resident one (single window and batch) and the host loop of sdso_ba_optimize
 //   ba_update.hip  sdso_ba_window_plan / _update / _update_activated / _get_order
 //   ba_flag.hip    sdso_ba_flag_points: removeOutliers / flagPointsForRemoval on the resident window (the rule itself: ba_flag.h)
-// Forward declarations cross the files only where two of them need each other: free_batch / free_optrun / free_optbufs (a window's
+// Forward declarations cross the files only where two of them need each other: free_batch / free_optrun (a window's
 // release ends the batch, the batch's end ends its loop) and launch_window_gather (the upload is the builder of an updated window).
 #include "ba_kernels.hip"
 #include "ba_solve.hip"

@@ -17,8 +17,7 @@ static void free_batch(sdso_ctx* ctx) {
     hipMemcpyAsync(W->d_self, &W->d, sizeof(BaDev), hipMemcpyHostToDevice, ctx->stream);
   }
   hipStreamSynchronize(ctx->stream);
-  hipFree(taken->d_arr); hipFree(taken->d_accum);
-  delete taken;
+  delete taken;   // (its blocks with it)
 }
 static bool batch_defers_fold(sdso_ctx* ctx, BaBatch* Bt) { (void)ctx; return tail_enabled() && !Bt->eager_fold && !Bt->L.alt; }
 }  // namespace sdso
@@ -46,11 +45,12 @@ extern "C" int sdso_ba_batch_create(sdso_ctx* ctx, int nwin, const int* wins) {
   }
   const int nf = Ws[0]->d.nf;
   const size_t af = acc_floats(nf);
-  BaDev* d_arr = nullptr; float* d_accum = nullptr;
-  SDSO_HIP(ctx, hipMalloc(&d_arr, sizeof(BaDev) * nwin));
-  if (hipMalloc(&d_accum, sizeof(float) * af * nwin) != hipSuccess) { hipFree(d_arr); return sdso::fail(ctx, SDSO_ERR_HIP, "hipMalloc of the batch accumulator block failed"); }
+  DevBuf<BaDev> d_arr;
+  DevBuf<float> d_accum;
+  SDSO_HIP(ctx, d_arr.reserve(ctx->stream, nwin, nwin));
+  SDSO_HIP(ctx, d_accum.reserve(ctx->stream, af * nwin, af * nwin));
   BaBatch* Bt = new BaBatch();
-  Bt->d_arr = d_arr; Bt->d_accum = d_accum; Bt->W = Ws;
+  Bt->d_arr = std::move(d_arr); Bt->d_accum = std::move(d_accum); Bt->W = Ws;
   Bt->wins.assign(wins, wins + nwin);
   ba_state(ctx).batch = Bt;
   hipMemsetAsync(Bt->d_accum, 0, sizeof(float) * af * nwin, ctx->stream);

@@ -12,8 +12,8 @@ struct BaLaunch {
 struct BaBatch {
   std::vector<int> wins;
   std::vector<BaWindowDev*> W;   // valid while the batch lives: releasing / re-uploading a member frees the batch first
-  BaDev* d_arr = nullptr;
-  float* d_accum = nullptr;
+  DevBuf<BaDev> d_arr;
+  DevBuf<float> d_accum;
   BaLaunch L;
   bool materialize = true;
   bool eager_fold = false;       // sdso_ba_batch_accum_dev handed the block's address out: never defer the folds

@@ -7,29 +7,6 @@ bool comm_present(sdso_ctx* ctx);                                               
 int comm_allgather_floats(sdso_ctx* ctx, const float* send, float* recv, size_t nfloats);  // comm.hip
 int comm_max_int(sdso_ctx* ctx, int* value);                                               // comm.hip
 
-// scratch of the resident loop, one set per ctx (grown on demand, freed with the ctx's windows)
-struct OptBufs {
-  float* d_sums = nullptr; size_t sums_cap = 0;
-  float* d_pack = nullptr; size_t pack_cap = 0;
-  float* d_gather = nullptr; size_t gather_cap = 0;
-  BaOptOut* d_out = nullptr; BaOptOut* h_out = nullptr; size_t out_cap = 0;
-  float* d_lpart = nullptr; size_t lpart_cap = 0;
-  float* d_solrec = nullptr; size_t solrec_cap = 0;
-};
-void free_optbufs(OptBufs* b) {
-  if (!b) return;
-  hipFree(b->d_sums); hipFree(b->d_pack); hipFree(b->d_gather); hipFree(b->d_out); hipFree(b->d_lpart); hipFree(b->d_solrec);
-  if (b->h_out) hipHostFree(b->h_out);
-  delete b;
-}
-template <class T> static int grow(sdso_ctx* ctx, T*& p, size_t& cap, size_t want) {
-  if (want <= cap) return SDSO_OK;
-  SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  hipFree(p); p = nullptr; cap = 0;
-  SDSO_HIP(ctx, hipMalloc(&p, sizeof(T) * want));
-  cap = want;
-  return SDSO_OK;
-}
 
 // one resident loop on a ctx: a batch (sdso_ba_batch_optimize*) or a single window (sdso_ba_optimize)
 struct OptRun {
@@ -78,22 +55,19 @@ static int opt_begin(sdso_ctx* ctx, OptRun& R, int stop_on_convergence) {
     R.scatter = want != 0;
   }
   R.sums_stride = 2 * (R.L.max_nblk_pts + 1);
-  OptBufs*& B = ba_state(ctx).bufs;
-  if (!B) B = new OptBufs();
-  R.B = B;
+  OptBufs* B = R.B = &ba_state(ctx).bufs;
   const size_t pf = opt_pack_floats(cap);
-  int rc;
-  if ((rc = grow(ctx, B->d_sums, B->sums_cap, (size_t)nwin * R.sums_stride))) return rc;
-  if ((rc = grow(ctx, B->d_pack, B->pack_cap, (size_t)nwin * pf))) return rc;
-  if (R.exchange && (rc = grow(ctx, B->d_gather, B->gather_cap, (size_t)R.nranks * nwin * pf))) return rc;
+  const size_t n_sums = (size_t)nwin * R.sums_stride, n_pack = (size_t)nwin * pf, n_gather = (size_t)R.nranks * n_pack;
+  SDSO_HIP(ctx, B->d_sums.reserve(ctx->stream, n_sums, n_sums));
+  SDSO_HIP(ctx, B->d_pack.reserve(ctx->stream, n_pack, n_pack));
+  if (R.exchange) SDSO_HIP(ctx, B->d_gather.reserve(ctx->stream, n_gather, n_gather));
   R.lstride = R.L.max_chunks + R.L.max_nblk_pts + 1;
-  if (R.gated && (rc = grow(ctx, B->d_lpart, B->lpart_cap, (size_t)nwin * R.lstride))) return rc;
+  if (R.gated) SDSO_HIP(ctx, B->d_lpart.reserve(ctx->stream, (size_t)nwin * R.lstride, (size_t)nwin * R.lstride));
   if ((size_t)nwin > B->out_cap) {
-    SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    hipFree(B->d_out); if (B->h_out) hipHostFree(B->h_out);
-    B->d_out = nullptr; B->h_out = nullptr; B->out_cap = 0;
-    SDSO_HIP(ctx, hipMalloc(&B->d_out, sizeof(BaOptOut) * nwin));
-    SDSO_HIP(ctx, hipHostMalloc(&B->h_out, sizeof(BaOptOut) * nwin));
+    B->out_cap = 0;
+    SDSO_HIP(ctx, devbuf::reset_all(ctx->stream, B->d_out, B->h_out));
+    SDSO_HIP(ctx, B->d_out.reserve(ctx->stream, nwin, nwin));
+    SDSO_HIP(ctx, B->h_out.reserve(ctx->stream, nwin, nwin));
     B->out_cap = nwin;
   }
   for (BaWindowDev* W : R.W) {
@@ -331,8 +305,8 @@ static int opt_solve_step(sdso_ctx* ctx, OptRun& R, double lambda, int orth, boo
     own.d_arr = R.L.d_arr + first; own.nwin = per;
     launch_tail(ctx, own, lambda, flags);
     const size_t rf = (size_t)sol_rec_floats(R.L.n, R.L.nf);
-    int rc = grow(ctx, R.B->d_solrec, R.B->solrec_cap, rf * nwin);
-    if (rc) return rc;
+    SDSO_HIP(ctx, R.B->d_solrec.reserve(ctx->stream, rf * nwin, rf * nwin));
+    int rc;
     hipLaunchKernelGGL(k_ba_sol_record, dim3(nwin), dim3(256), 0, ctx->stream, R.L.d_arr, first, per, R.B->d_solrec, 0);
     if ((rc = comm_allgather_floats(ctx, R.B->d_solrec + rf * first, R.B->d_solrec, rf * per))) return rc;
     hipLaunchKernelGGL(k_ba_sol_record, dim3(nwin), dim3(256), 0, ctx->stream, R.L.d_arr, first, per, R.B->d_solrec, 1);

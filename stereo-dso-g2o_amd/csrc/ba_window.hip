@@ -3,8 +3,7 @@
 namespace sdso {
 
 struct BaBatch;   // ba_launch.hip
-struct OptBufs;   // ba_loop.hip
-struct OptRun;
+struct OptRun;    // ba_loop.hip
 
 struct BaWindowDev {
   BaDev d;                 // host copy of the device descriptor
@@ -79,11 +78,18 @@ static int dmalloc(sdso_ctx* ctx, BaWindowDev* W, void** p, size_t bytes, bool z
   W->allocs.emplace_back(*p, got);
   return SDSO_OK;
 }
+// scratch of the resident loop (ba_loop.hip), one set per ctx, grown on demand
+struct OptBufs {
+  DevBuf<float> d_sums, d_pack, d_gather, d_lpart, d_solrec;
+  DevBuf<BaOptOut> d_out;
+  PinBuf<BaOptOut> h_out;
+  size_t out_cap = 0;   // windows d_out and h_out both hold: a group (devbuf.h)
+};
 // the BA state of a ctx besides its windows (sdso_ctx::ba): created by the first call that needs it, freed with the windows
 struct BaCtxState {
   StageBuf stage;             // pinned host staging of window uploads and table refreshes (sdso_internal.h), released with the ctx's windows
   BaBatch* batch = nullptr;   // sdso_ba_batch_create
-  OptBufs* bufs = nullptr;    // scratch of the resident GN loop
+  OptBufs bufs;               // scratch of the resident GN loop
   OptRun* run = nullptr;      // the batch loop in flight between sdso_ba_batch_optimize_begin and _end
 };
 static BaCtxState& ba_state(sdso_ctx* ctx) { if (!ctx->ba) ctx->ba = new BaCtxState(); return *ctx->ba; }
@@ -103,10 +109,9 @@ static void free_window(sdso_ctx* ctx, BaWindowDev* W) {
   delete W;
 }
 static void free_batch(sdso_ctx* ctx);   // ba_batch.hip (a released window may be a member of the ctx's batch)
-void free_optbufs(OptBufs* b);           // ba_loop.hip
 void release_all_windows(sdso_ctx* ctx) {
   free_batch(ctx);
-  if (ctx->ba) { free_optbufs(ctx->ba->bufs); stage_free(ctx->ba->stage); delete ctx->ba; ctx->ba = nullptr; }
+  if (ctx->ba) { stage_free(ctx->ba->stage); delete ctx->ba; ctx->ba = nullptr; }
   for (auto& kv : ctx->wins) free_window(ctx, kv.second);
   ctx->wins.clear();
 }

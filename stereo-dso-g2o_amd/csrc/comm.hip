@@ -124,13 +124,12 @@ int comm_max_int(sdso_ctx* ctx, int* value) {
     return SDSO_OK;
   }
   RcclApi* a = rccl_api(nullptr);
-  int* d = nullptr;
-  if (hipMalloc(&d, sizeof(int)) != hipSuccess) return sdso::fail(ctx, SDSO_ERR_HIP, "hipMalloc");
+  DevBuf<int> d;   // freed on the way out, behind the wait below
+  SDSO_HIP(ctx, d.reserve(ctx->stream, 1, 1));
   hipMemcpyAsync(d, value, sizeof(int), hipMemcpyHostToDevice, ctx->stream);
   const ncclResult_t r = a->AllReduce(d, d, 1, ncclInt32, ncclMax, c->comm, ctx->stream);
   hipMemcpyAsync(value, d, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
   const hipError_t e = hipStreamSynchronize(ctx->stream);
-  hipFree(d);
   if (r != ncclSuccess || e != hipSuccess) return sdso::fail(ctx, SDSO_ERR_HIP, "all-reduce(max) of the pack capacity failed");
   return SDSO_OK;
 }

@@ -7,19 +7,11 @@ using namespace sdso;
 
 namespace sdso {
 int ensure_scratch(sdso_ctx* ctx, size_t bytes) {
-  if (ctx->scratch_bytes >= bytes) return SDSO_OK;
-  if (ctx->scratch) { SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream)); SDSO_HIP(ctx, hipFree(ctx->scratch)); ctx->scratch = nullptr; ctx->scratch_bytes = 0; }
-  size_t want = bytes + bytes / 2 + 4096;
-  SDSO_HIP(ctx, hipMalloc(&ctx->scratch, want));
-  ctx->scratch_bytes = want;
+  SDSO_HIP(ctx, ctx->scratch.reserve(ctx->stream, bytes, bytes + bytes / 2 + 4096));
   return SDSO_OK;
 }
 int ensure_pinned(sdso_ctx* ctx, size_t bytes) {
-  if (ctx->pinned_bytes >= bytes) return SDSO_OK;
-  if (ctx->pinned) { SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream)); SDSO_HIP(ctx, hipHostFree(ctx->pinned)); ctx->pinned = nullptr; ctx->pinned_bytes = 0; }
-  size_t want = bytes + bytes / 2 + 4096;
-  SDSO_HIP(ctx, hipHostMalloc(&ctx->pinned, want, hipHostMallocDefault));
-  ctx->pinned_bytes = want;
+  SDSO_HIP(ctx, ctx->pinned.reserve(ctx->stream, bytes, bytes + bytes / 2 + 4096));
   return SDSO_OK;
 }
 }  // namespace sdso
@@ -191,12 +183,8 @@ extern "C" void sdso_ctx_destroy(sdso_ctx* ctx) {
   release_map(ctx);
   release_comm(ctx);
   release_pool(ctx);   // the ctx's reference: what its slots held is parked by now (the last reference frees it)
-  if (ctx->gammaB) hipFree(ctx->gammaB);
-  if (ctx->scratch) hipFree(ctx->scratch);
-  if (ctx->lm_clusters) hipFree(ctx->lm_clusters);
-  if (ctx->pinned) hipHostFree(ctx->pinned);
   hipStreamDestroy(ctx->stream);
-  delete ctx;
+  delete ctx;   // its own buffers (devbuf.h) go with it: the stream was synchronised above
 }
 extern "C" const char* sdso_last_error(const sdso_ctx* ctx) { return ctx ? ctx->err.c_str() : "null ctx"; }
 extern "C" void* sdso_ctx_stream(sdso_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
@@ -351,8 +339,8 @@ extern "C" int sdso_set_gamma(sdso_ctx* ctx, const float* B) {
   if (!ctx) return SDSO_ERR_STATE;
   SDSO_HIP(ctx, hipSetDevice(ctx->device));
   SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (!B) { if (ctx->gammaB) hipFree(ctx->gammaB); ctx->gammaB = nullptr; return SDSO_OK; }
-  if (!ctx->gammaB) SDSO_HIP(ctx, hipMalloc(&ctx->gammaB, 256 * sizeof(float)));
+  if (!B) { ctx->gammaB = DevBuf<float>(); return SDSO_OK; }   // (the stream is idle)
+  SDSO_HIP(ctx, ctx->gammaB.reserve(ctx->stream, 256, 256));
   SDSO_HIP(ctx, hipMemcpy(ctx->gammaB, B, 256 * sizeof(float), hipMemcpyHostToDevice));
   return SDSO_OK;
 }
@@ -473,16 +461,14 @@ extern "C" int sdso_selftest_se3(sdso_ctx* ctx, int n, const double* xi, double*
   if (!ctx) return SDSO_ERR_STATE;
   SDSO_REQUIRE(ctx, n > 0 && xi && T_exp && T_inv && T_mul_next, "bad arguments");
   SDSO_HIP(ctx, hipSetDevice(ctx->device));
-  double *d_xi = nullptr, *d_out = nullptr;
-  SDSO_HIP(ctx, hipMalloc(&d_xi, sizeof(double) * 6 * n));
-  if (hipMalloc(&d_out, sizeof(double) * 36 * n) != hipSuccess) { hipFree(d_xi); return sdso::fail(ctx, SDSO_ERR_HIP, "hipMalloc"); }
+  DevBuf<double> d_xi, d_out;   // freed on every way out, behind the wait below
+  SDSO_HIP(ctx, d_xi.reserve(ctx->stream, 6 * (size_t)n, 6 * (size_t)n));
+  SDSO_HIP(ctx, d_out.reserve(ctx->stream, 36 * (size_t)n, 36 * (size_t)n));
   hipMemcpyAsync(d_xi, xi, sizeof(double) * 6 * n, hipMemcpyHostToDevice, ctx->stream);
   hipLaunchKernelGGL(sdso::k_selftest_se3, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, n, (const double*)d_xi, d_out, d_out + 12 * n, d_out + 24 * n);
   hipMemcpyAsync(T_exp, d_out, sizeof(double) * 12 * n, hipMemcpyDeviceToHost, ctx->stream);
   hipMemcpyAsync(T_inv, d_out + 12 * n, sizeof(double) * 12 * n, hipMemcpyDeviceToHost, ctx->stream);
   hipMemcpyAsync(T_mul_next, d_out + 24 * n, sizeof(double) * 12 * n, hipMemcpyDeviceToHost, ctx->stream);
-  const hipError_t e = hipStreamSynchronize(ctx->stream);
-  hipFree(d_xi); hipFree(d_out);
-  if (e != hipSuccess) return sdso::fail(ctx, SDSO_ERR_HIP, hipGetErrorString(e));
+  SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SDSO_OK;
 }

@@ -29,17 +29,13 @@ constexpr uint8_t DM_OUTSIDE = 254;         // halo pixel outside the image: nev
 struct DistMapState {
   int w1 = 0, h1 = 0;
   bool valid = false;          // a map has been made for (w1, h1)
-  uint8_t* seed = nullptr;     // w1*h1 bytes (padded to 16): 0 at the seeds, 255 elsewhere
-  uint8_t* map = nullptr;      // w1*h1 bytes (padded to 16)
-  int* cnt = nullptr;          // numItems of sdso_distmap_make_from_window (the host route counts in the ctx scratch)
-  size_t cap = 0;
+  DevBuf<uint8_t> seed;        // w1*h1 bytes (padded to 16): 0 at the seeds, 255 elsewhere
+  DevBuf<uint8_t> map;         // w1*h1 bytes (padded to 16)
+  DevBuf<int> cnt;             // numItems of sdso_distmap_make_from_window (the host route counts in the ctx scratch)
+  size_t cap = 0;              // bytes seed and map both hold
 };
 
 void release_distmap(sdso_ctx* ctx) {
-  if (!ctx->dm) return;
-  if (ctx->dm->seed) hipFree(ctx->dm->seed);
-  if (ctx->dm->map) hipFree(ctx->dm->map);
-  if (ctx->dm->cnt) hipFree(ctx->dm->cnt);
   delete ctx->dm;
   ctx->dm = nullptr;
 }
@@ -282,16 +278,14 @@ static int dm_ensure(sdso_ctx* ctx, int w1, int h1) {
   if (!ctx->dm) ctx->dm = new DistMapState();
   DistMapState& D = *ctx->dm;
   const size_t need = (((size_t)w1 * h1 + 15) & ~(size_t)15) + 16;
-  if (D.cap < need) {
-    SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (D.seed) hipFree(D.seed);
-    if (D.map) hipFree(D.map);
-    D.seed = D.map = nullptr; D.cap = 0; D.valid = false;
-    SDSO_HIP(ctx, hipMalloc(&D.seed, need));
-    SDSO_HIP(ctx, hipMalloc(&D.map, need));
+  if (D.cap < need) {   // a group (devbuf.h)
+    D.cap = 0; D.valid = false;
+    SDSO_HIP(ctx, devbuf::reset_all(ctx->stream, D.seed, D.map));
+    SDSO_HIP(ctx, D.seed.reserve(ctx->stream, need, need));
+    SDSO_HIP(ctx, D.map.reserve(ctx->stream, need, need));
     D.cap = need;
   }
-  if (!D.cnt) SDSO_HIP(ctx, hipMalloc(&D.cnt, 16));
+  SDSO_HIP(ctx, D.cnt.reserve(ctx->stream, 4, 4));
   if (D.w1 != w1 || D.h1 != h1) D.valid = false;
   D.w1 = w1; D.h1 = h1;
   return SDSO_OK;

@@ -12,6 +12,7 @@
 #include "sdso_internal.h"
 #include "host_math.h"
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstring>
 
@@ -19,39 +20,26 @@ namespace sdso {
 
 struct G2oEdgeSet {
   int cap = 0, n = 0, n_edges = 0;
-  uint8_t* mask = nullptr;
-  float4* xref = nullptr;    // {Xref, measurement}
+  DevBuf<uint8_t> mask;
+  DevBuf<float4> xref;       // {Xref, measurement}
 };
 struct G2oState {
   std::map<std::pair<int, int>, G2oEdgeSet> sets;   // (ref_slot, level)
-  double* d_part = nullptr;                          // per-block partial systems
-  int part_blocks = 0;
-  int* d_cnt = nullptr;                              // {numTermsInE, numSaturated}
-  float* d_flow = nullptr;                           // 4 floats per 32nd level-0 point
-  int flow_cap = 0;
+  DevBuf<double> d_part;                             // per-block partial systems
+  DevBuf<int> d_cnt;                                 // {numTermsInE, numSaturated}
+  DevBuf<float> d_flow;                              // 4 floats per 32nd level-0 point
 };
 void release_g2o(sdso_ctx* ctx) {
-  G2oState* st = ctx->g2o;
-  if (!st) return;
-  for (auto& kv : st->sets) { if (kv.second.mask) hipFree(kv.second.mask); if (kv.second.xref) hipFree(kv.second.xref); }
-  if (st->d_part) hipFree(st->d_part);
-  if (st->d_cnt) hipFree(st->d_cnt);
-  if (st->d_flow) hipFree(st->d_flow);
-  delete st;
+  delete ctx->g2o;
   ctx->g2o = nullptr;
 }
 
-// sdso_track_release_ref: the edge sets built on a released template go with it
+// sdso_track_release_ref: the edge sets built on a released template go with it.  The caller has synchronised the stream: the erase
+// frees their buffers.
 void release_g2o_ref(sdso_ctx* ctx, int ref_slot) {
   if (!ctx->g2o) return;
-  G2oState& st = *ctx->g2o;
-  for (auto it = st.sets.begin(); it != st.sets.end();) {
-    if (it->first.first == ref_slot) {
-      if (it->second.mask) hipFree(it->second.mask);
-      if (it->second.xref) hipFree(it->second.xref);
-      it = st.sets.erase(it);
-    } else ++it;
-  }
+  auto& sets = ctx->g2o->sets;
+  sets.erase(sets.lower_bound({ref_slot, INT_MIN}), sets.upper_bound({ref_slot, INT_MAX}));
 }
 
 constexpr int kSysDoubles = 36 + 8 + 2;   // upper triangle of H, b, {chi2, robust chi2}
@@ -350,23 +338,17 @@ extern "C" int sdso_g2o_track_add_edges(sdso_ctx* ctx, int ref_slot, int frame_s
   if (!ctx->g2o) ctx->g2o = new G2oState();
   G2oState& st = *ctx->g2o;
   G2oEdgeSet& S = st.sets[{ref_slot, lvl}];
-  if (S.cap < n) {
-    SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (S.mask) hipFree(S.mask);
-    if (S.xref) hipFree(S.xref);
-    S.mask = nullptr; S.xref = nullptr;
-    S.cap = n + n / 4 + 64;
-    SDSO_HIP(ctx, hipMalloc(&S.mask, (size_t)S.cap));
-    SDSO_HIP(ctx, hipMalloc(&S.xref, sizeof(float4) * (size_t)S.cap));
+  if (S.cap < n) {   // a group (devbuf.h): no edges either while it has no room
+    const size_t cap = (size_t)(n + n / 4 + 64);
+    S.cap = S.n = S.n_edges = 0;
+    SDSO_HIP(ctx, devbuf::reset_all(ctx->stream, S.mask, S.xref));
+    SDSO_HIP(ctx, S.mask.reserve(ctx->stream, cap, cap));
+    SDSO_HIP(ctx, S.xref.reserve(ctx->stream, cap, cap));
+    S.cap = (int)cap;
   }
-  if (!st.d_cnt) SDSO_HIP(ctx, hipMalloc(&st.d_cnt, sizeof(int) * 2));
+  SDSO_HIP(ctx, st.d_cnt.reserve(ctx->stream, 2, 2));
   const int nflow = (n + 31) / 32;
-  if (st.flow_cap < nflow) {
-    SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (st.d_flow) hipFree(st.d_flow);
-    st.flow_cap = nflow + 64;
-    SDSO_HIP(ctx, hipMalloc(&st.d_flow, sizeof(float) * 4 * (size_t)st.flow_cap));
-  }
+  SDSO_HIP(ctx, st.d_flow.reserve(ctx->stream, 4 * (size_t)nflow, 4 * ((size_t)nflow + 64)));
   S.n = n; S.n_edges = 0;
   int cnt[2] = {0, 0};
   std::vector<float> flow((size_t)nflow * 4, 0.f);
@@ -416,7 +398,7 @@ extern "C" int sdso_g2o_track_linearize(sdso_ctx* ctx, int ref_slot, int frame_s
   const int n = S->n;
   if (n == 0) return SDSO_OK;
   G2oState& st = *ctx->g2o;   // (find_set found one of its edge sets)
-  if (!st.d_part) { SDSO_HIP(ctx, hipMalloc(&st.d_part, sizeof(double) * kSysDoubles * kMaxLinBlocks)); st.part_blocks = kMaxLinBlocks; }
+  SDSO_HIP(ctx, st.d_part.reserve(ctx->stream, kSysDoubles * kMaxLinBlocks, kSysDoubles * kMaxLinBlocks));
   const int blocks = std::min(kMaxLinBlocks, (n + 255) / 256);
   double *d_err = nullptr, *d_J = nullptr;
   if (err || J) {

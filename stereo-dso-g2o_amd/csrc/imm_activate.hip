@@ -188,18 +188,9 @@ extern "C" int sdso_imm_activate(sdso_ctx* ctx, const sdso_imm_activate_t* P, in
                o_back = take(4 * N), o_src = take(4 * N), o_seg = take(4 * (nseg + 1));
   SDSO_TRY(ensure_scratch(ctx, bytes));
   S.act_valid = false;                                    // from here on the previous activation's records (h_act, d_act) may be freed or overwritten
-  if (S.h_act_cap < res_bytes) {
-    if (S.h_act) { SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream)); hipHostFree(S.h_act); S.h_act = nullptr; S.h_act_cap = 0; }
-    const size_t want = (res_bytes * 3 / 2 + 4095) & ~(size_t)4095;
-    SDSO_HIP(ctx, hipHostMalloc((void**)&S.h_act, want));
-    S.h_act_cap = want;
-  }
-  if (S.d_act_cap < sizeof(ImmActRec) * N) {              // the records' own buffer (below): the scratch is the next call's to overwrite
-    if (S.d_act) { SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream)); hipFree(S.d_act); S.d_act = nullptr; S.d_act_cap = 0; }
-    const size_t want = (sizeof(ImmActRec) * N * 3 / 2 + 4095) & ~(size_t)4095;
-    SDSO_HIP(ctx, hipMalloc((void**)&S.d_act, want));
-    S.d_act_cap = want;
-  }
+  SDSO_HIP(ctx, S.h_act.reserve(ctx->stream, res_bytes, (res_bytes * 3 / 2 + 4095) & ~(size_t)4095));
+  // the records' own buffer (below): the scratch is the next call's to overwrite
+  SDSO_HIP(ctx, S.d_act.reserve(ctx->stream, sizeof(ImmActRec) * N, (sizeof(ImmActRec) * N * 3 / 2 + 4095) & ~(size_t)4095));
   char* dp = (char*)ctx->scratch;
   int* d_hdr = (int*)(dp + o_hdr);
   uint8_t* d_dec = (uint8_t*)(dp + o_dec);

@@ -90,26 +90,18 @@ namespace sdso {
 static int imm_match_reserve(sdso_ctx* ctx, ImmMatchKept& M, int n) {
   M.valid = false; M.have = 0;
   if (M.d && M.cap >= n) return SDSO_OK;
-  SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (M.d) hipFree(M.d);
-  if (M.h) hipHostFree(M.h);
-  M.d = M.h = nullptr; M.cap = 0;
   const int cap = n + n / 4 + 64;
-  SDSO_HIP(ctx, hipMalloc((void**)&M.d, imm_match_bytes(cap, true)));
-  SDSO_HIP(ctx, hipHostMalloc((void**)&M.h, imm_match_bytes(cap, true)));
+  M.cap = 0;   // a group (devbuf.h)
+  SDSO_HIP(ctx, devbuf::reset_all(ctx->stream, M.d, M.h));
+  SDSO_HIP(ctx, M.d.reserve(ctx->stream, imm_match_bytes(cap, true), imm_match_bytes(cap, true)));
+  SDSO_HIP(ctx, M.h.reserve(ctx->stream, imm_match_bytes(cap, true), imm_match_bytes(cap, true)));
   M.cap = cap;
   return SDSO_OK;
 }
 static int imm_match_map_reserve(sdso_ctx* ctx, ImmMatchKept& M, int w, int h) {
   M.map_valid = false;
   const size_t floats = (size_t)w * h * 3;
-  if (floats > M.map_cap) {
-    SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (M.d_map) hipFree(M.d_map);
-    M.d_map = nullptr; M.map_cap = 0;
-    SDSO_HIP(ctx, hipMalloc((void**)&M.d_map, sizeof(float) * floats));
-    M.map_cap = floats;
-  }
+  SDSO_HIP(ctx, M.d_map.reserve(ctx->stream, floats, floats));
   M.map_w = w; M.map_h = h;
   return SDSO_OK;
 }

@@ -10,23 +10,22 @@ struct ImmHostDev { float* f; uint8_t* st; int n, cap; };
 struct ImmHost {
   int w = 0, h = 0, cap = 0;
   int n = -1;                       // -1: the count of the add that made this host has not been read yet (h_n is valid after ev)
-  float* f[2] = {nullptr, nullptr}; // [0] current, [1] the target of the next removal gather
-  uint8_t* st[2] = {nullptr, nullptr};
-  int* d_n = nullptr;
-  int* h_n = nullptr;               // pinned
+  DevBuf<float> f[2];               // [0] current, [1] the target of the next removal gather
+  DevBuf<uint8_t> st[2];
+  DevBuf<int> d_n;
+  PinBuf<int> h_n;
   hipEvent_t ev = nullptr;
 };
 // the results of the latest sdso_imm_stereo_match (imm_match.hip), in buffers no other call writes: counts | idepth | accepted | status_fwd |
 // status_back on the device with a pinned mirror, and the dense map of the latest call that built one
 struct ImmMatchKept {
-  char* d = nullptr;
-  char* h = nullptr;                // pinned; its first `have` bytes hold the device's
+  DevBuf<char> d;
+  PinBuf<char> h;                   // its first `have` bytes hold the device's
   int cap = 0;                      // points both buffers hold
   bool valid = false;
   int n = 0;
   size_t have = 0;
-  float* d_map = nullptr;
-  size_t map_cap = 0;               // floats
+  DevBuf<float> d_map;
   bool map_valid = false, map_latest = false;   // a map is kept; the latest call built it
   int map_w = 0, map_h = 0;
 };
@@ -34,52 +33,42 @@ struct ImmState {
   std::map<int, ImmHost> hosts;
   ImmMatchKept match;
   TraceBatch fwd, back;             // the stereo chain of the non-key trace, over the concatenated points of the named hosts
-  int* d_counts = nullptr;          // SDSO_IMM_NCOUNTS
-  int* h_counts = nullptr;          // pinned
+  DevBuf<int> d_counts;             // SDSO_IMM_NCOUNTS
+  PinBuf<int> h_counts;
   StageBuf stage;                   // selection maps, removal orders and sdso_imm_activate's tables on their way to the device
   // the results of the latest sdso_imm_activate: header | decisions | records (pinned), for sdso_imm_activate_fetch
-  char* h_act = nullptr;
-  size_t h_act_cap = 0;
+  PinBuf<char> h_act;
   bool act_valid = false;
   int act_nf = 0, act_ntot = 0, act_nsel = 0;
   // the same records once more on the device, in a buffer no other call writes, for sdso_ba_window_update_activated: act_nsel entries of
   // ImmActRec (imm_layout.h); the w x h of that call; consumed: an update has taken them into a window (cleared by every sdso_imm_activate)
-  char* d_act = nullptr;
-  size_t d_act_cap = 0;
+  DevBuf<char> d_act;
   int act_w = 0, act_h = 0;
   bool act_consumed = false;
 };
 static ImmState& imm_state(sdso_ctx* ctx) { if (!ctx->imm) ctx->imm = new ImmState(); return *ctx->imm; }
-static void imm_free_host(ImmHost& H) {
-  for (int k = 0; k < 2; k++) { if (H.f[k]) hipFree(H.f[k]); if (H.st[k]) hipFree(H.st[k]); }
-  if (H.d_n) hipFree(H.d_n);
-  if (H.h_n) hipHostFree(H.h_n);
+static void imm_free_host(ImmHost& H) {   // (the stream is idle, or has never seen the host)
   if (H.ev) hipEventDestroy(H.ev);
   H = ImmHost();
 }
-static int imm_alloc_host(sdso_ctx* ctx, ImmHost& H) {   // the caller frees what was allocated when this fails
-  const size_t C = (size_t)H.cap;
+// a fresh host for `cap` points: a group (devbuf.h); nothing but buffers is left behind when this fails
+static int imm_alloc_host(sdso_ctx* ctx, ImmHost& H, int cap) {
+  const size_t C = (size_t)cap;
+  H.cap = 0;
   for (int k = 0; k < 2; k++) {
-    SDSO_HIP(ctx, hipMalloc(&H.f[k], sizeof(float) * kImmFloats * C));
-    SDSO_HIP(ctx, hipMalloc(&H.st[k], C));
+    SDSO_HIP(ctx, H.f[k].reserve(ctx->stream, kImmFloats * C, kImmFloats * C));
+    SDSO_HIP(ctx, H.st[k].reserve(ctx->stream, C, C));
   }
-  SDSO_HIP(ctx, hipMalloc(&H.d_n, sizeof(int)));
-  SDSO_HIP(ctx, hipHostMalloc((void**)&H.h_n, sizeof(int)));
+  SDSO_HIP(ctx, H.d_n.reserve(ctx->stream, 1, 1));
+  SDSO_HIP(ctx, H.h_n.reserve(ctx->stream, 1, 1));
   SDSO_HIP(ctx, hipEventCreateWithFlags(&H.ev, hipEventDisableTiming));
+  H.cap = cap;
   return SDSO_OK;
 }
 void release_immature(sdso_ctx* ctx) {
   ImmState* S = ctx->imm;
   if (!S) return;
-  for (auto& kv : S->hosts) imm_free_host(kv.second);
-  trace_free(S->fwd); trace_free(S->back);
-  if (S->d_counts) hipFree(S->d_counts);
-  if (S->h_counts) hipHostFree(S->h_counts);
-  if (S->h_act) hipHostFree(S->h_act);
-  if (S->d_act) hipFree(S->d_act);
-  if (S->match.d) hipFree(S->match.d);
-  if (S->match.h) hipHostFree(S->match.h);
-  if (S->match.d_map) hipFree(S->match.d_map);
+  for (auto& kv : S->hosts) if (kv.second.ev) hipEventDestroy(kv.second.ev);
   stage_free(S->stage);
   delete S;
   ctx->imm = nullptr;
@@ -245,9 +234,9 @@ extern "C" int sdso_imm_add_frame(sdso_ctx* ctx, int host_id, int frame_slot, co
   int* d_ncand = d_seg + nseg2;
 
   ImmHost H;
-  H.w = w; H.h = h; H.cap = cap;
-  int rc = imm_alloc_host(ctx, H);
-  if (rc) { imm_free_host(H); return rc; }
+  H.w = w; H.h = h;
+  int rc = imm_alloc_host(ctx, H, cap);
+  if (rc) return rc;
 
   auto enqueue = [&]() -> int {
     const int one = 0x41000000;   // 8.0f: candidates past the count (the selector's bound) sit on a harmless pixel for the constructor kernel
@@ -271,7 +260,7 @@ extern "C" int sdso_imm_add_frame(sdso_ctx* ctx, int host_id, int frame_slot, co
   rc = enqueue();
   if (rc) { hipStreamSynchronize(ctx->stream); imm_free_host(H); return rc; }   // the host is not in the set yet: nothing else owns its buffers
   ImmHost& R = S.hosts[host_id];
-  R = H;
+  R = std::move(H);
   if (n_out) {
     SDSO_TRY(imm_resolve(ctx, R));
     *n_out = R.n;
@@ -371,9 +360,9 @@ extern "C" int sdso_imm_put_host(sdso_ctx* ctx, int host_id, int w, int h, const
   ImmState& S = imm_state(ctx);
   SDSO_REQUIRE(ctx, S.hosts.find(host_id) == S.hosts.end(), "the host already has immature points");
   ImmHost H;
-  H.w = w; H.h = h; H.cap = std::max(n, 1); H.n = n;
-  int rc = imm_alloc_host(ctx, H);
-  if (rc) { imm_free_host(H); return rc; }
+  H.w = w; H.h = h; H.n = n;
+  int rc = imm_alloc_host(ctx, H, std::max(n, 1));
+  if (rc) return rc;
   auto copy = [&]() -> int {
     for (int m = 0; m < kImmMembers; m++) {
       const float* src = kImmField[m] ? P->*kImmField[m] : my_type;
@@ -388,6 +377,6 @@ extern "C" int sdso_imm_put_host(sdso_ctx* ctx, int host_id, int w, int h, const
     rc = copy();
     if (rc) { hipStreamSynchronize(ctx->stream); imm_free_host(H); return rc; }
   }
-  S.hosts[host_id] = H;
+  S.hosts[host_id] = std::move(H);
   return SDSO_OK;
 }

@@ -150,10 +150,8 @@ extern "C" int sdso_imm_trace(sdso_ctx* ctx, int frame_slot, int right_slot, int
   const int n = A.ntot;
   if (counts) for (int k = 0; k < SDSO_IMM_NCOUNTS; k++) counts[k] = 0;
   if (n == 0) return SDSO_OK;
-  if (!S.d_counts) {
-    SDSO_HIP(ctx, hipMalloc(&S.d_counts, sizeof(int) * SDSO_IMM_NCOUNTS));
-    SDSO_HIP(ctx, hipHostMalloc((void**)&S.h_counts, sizeof(int) * SDSO_IMM_NCOUNTS));
-  }
+  SDSO_HIP(ctx, S.d_counts.reserve(ctx->stream, SDSO_IMM_NCOUNTS, SDSO_IMM_NCOUNTS));
+  SDSO_HIP(ctx, S.h_counts.reserve(ctx->stream, SDSO_IMM_NCOUNTS, SDSO_IMM_NCOUNTS));
   TraceDev base = TraceDev();   // traceOn takes its geometry from the point's host: the camera is the identity
   const float K0[4] = {1, 1, 0, 0};
   SDSO_TRY(trace_set_camera(ctx, base, *PL, K0, 0.f, 1));

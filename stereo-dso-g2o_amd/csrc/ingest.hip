@@ -229,9 +229,9 @@ enum { PHOTO_LINEAR = 0, PHOTO_G = 1, PHOTO_G_VIGNETTE = 2 };   // PhotometricUn
 struct IngestCalib {
   int wOrg = 0, hOrg = 0, w = 0, h = 0, pixel_bytes = 1, mode = 0;
   bool passthrough = false, use_exposure = true;
-  float2* remap = nullptr;   // {remapX, remapY} per output pixel; x < 0 = outside
-  float* G = nullptr;        // 256 or 65536 floats; null = the reference's !valid
-  float* vinv = nullptr;     // vignetteMapInv, wOrg*hOrg
+  DevBuf<float2> remap;      // {remapX, remapY} per output pixel; x < 0 = outside
+  DevBuf<float> G;           // 256 or 65536 floats; null = the reference's !valid
+  DevBuf<float> vinv;        // vignetteMapInv, wOrg*hOrg
 };
 // Raw images wait in pinned memory for their copy: a StageBuf of this module's own (the double buffer of the window upload), so
 // sdso_ingest_frame never waits for the stream.  ctx->pinned cannot serve: the synchronous entry points write it without waiting for
@@ -239,22 +239,12 @@ struct IngestCalib {
 struct IngestState {
   std::map<int, IngestCalib> calibs;
   StageBuf stage;
-  char* raw = nullptr;       // the raw images of the ingest in flight on the device; the stream orders its reuse
-  size_t raw_cap = 0;
+  DevBuf<char> raw;          // the raw images of the ingest in flight on the device; the stream orders its reuse
 };
 
-static void free_calib(IngestCalib& c) {
-  if (c.remap) hipFree(c.remap);
-  if (c.G) hipFree(c.G);
-  if (c.vinv) hipFree(c.vinv);
-  c = IngestCalib();
-}
 void release_ingest(sdso_ctx* ctx) {
   if (!ctx->ingest) return;
-  IngestState& S = *ctx->ingest;
-  for (auto& kv : S.calibs) free_calib(kv.second);
-  stage_free(S.stage);
-  if (S.raw) hipFree(S.raw);
+  stage_free(ctx->ingest->stage);
   delete ctx->ingest;
   ctx->ingest = nullptr;
 }
@@ -350,23 +340,18 @@ extern "C" int sdso_ingest_calib_create(sdso_ctx* ctx, int calib, int wOrg, int 
       const bool inside = x >= 0 && x < (float)(wOrg - 1) && y > -1.0f && y < (float)(hOrg - 1);
       m[i] = inside ? make_float2(x, y) : make_float2(-1.f, -1.f);
     }
-    if ((e = hipMalloc(&c.remap, sizeof(float2) * npix)) == hipSuccess) e = hipMemcpy(c.remap, m.data(), sizeof(float2) * npix, hipMemcpyHostToDevice);
+    if ((e = c.remap.reserve(ctx->stream, npix, npix)) == hipSuccess) e = hipMemcpy(c.remap, m.data(), sizeof(float2) * npix, hipMemcpyHostToDevice);
   }
   if (e == hipSuccess && G) {
-    const size_t gb = sizeof(float) * (pixel_bytes == 1 ? 256 : 65536);
-    if ((e = hipMalloc(&c.G, gb)) == hipSuccess) e = hipMemcpy(c.G, G, gb, hipMemcpyHostToDevice);
+    const size_t gn = pixel_bytes == 1 ? 256 : 65536;
+    if ((e = c.G.reserve(ctx->stream, gn, gn)) == hipSuccess) e = hipMemcpy(c.G, G, sizeof(float) * gn, hipMemcpyHostToDevice);
   }
   if (e == hipSuccess && G && vignetteMapInv) {
-    if ((e = hipMalloc(&c.vinv, sizeof(float) * norg)) == hipSuccess) e = hipMemcpy(c.vinv, vignetteMapInv, sizeof(float) * norg, hipMemcpyHostToDevice);
+    if ((e = c.vinv.reserve(ctx->stream, norg, norg)) == hipSuccess) e = hipMemcpy(c.vinv, vignetteMapInv, sizeof(float) * norg, hipMemcpyHostToDevice);
   }
-  if (e != hipSuccess) { free_calib(c); return sdso::fail(ctx, SDSO_ERR_HIP, std::string("sdso_ingest_calib_create: ") + hipGetErrorString(e)); }
-  auto old = S.calibs.find(calib);
-  if (old != S.calibs.end()) {
-    e = hipStreamSynchronize(ctx->stream);   // an ingest in flight may still read the tables this call replaces
-    if (e != hipSuccess) { free_calib(c); return sdso::fail(ctx, SDSO_ERR_HIP, std::string("sdso_ingest_calib_create: ") + hipGetErrorString(e)); }
-    free_calib(old->second);
-  }
-  S.calibs[calib] = c;
+  if (e == hipSuccess && S.calibs.count(calib)) e = hipStreamSynchronize(ctx->stream);   // an ingest in flight may still read the tables this call replaces
+  if (e != hipSuccess) return sdso::fail(ctx, SDSO_ERR_HIP, std::string("sdso_ingest_calib_create: ") + hipGetErrorString(e));   // (c's tables go with it)
+  S.calibs[calib] = std::move(c);
   return SDSO_OK;
 }
 
@@ -377,7 +362,6 @@ extern "C" int sdso_ingest_calib_release(sdso_ctx* ctx, int calib) {
   if (it == ctx->ingest->calibs.end()) return SDSO_OK;
   SDSO_HIP(ctx, hipSetDevice(ctx->device));
   SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  free_calib(it->second);
   ctx->ingest->calibs.erase(it);
   return SDSO_OK;
 }
@@ -403,11 +387,7 @@ extern "C" int sdso_ingest_frame(sdso_ctx* ctx, int calib, int n_images, const i
   // staging: the next pinned buffer, once the copy enqueued from it two calls ago is through; sized for two images whatever n_images is
   char* pin = nullptr;
   { int rc = stage_reserve(ctx, S.stage, 2 * img_bytes, &pin); if (rc) return rc; }
-  if (S.raw_cap < bytes) {
-    if (S.raw) { SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream)); hipFree(S.raw); S.raw = nullptr; S.raw_cap = 0; }
-    SDSO_HIP(ctx, hipMalloc((void**)&S.raw, 2 * img_bytes));
-    S.raw_cap = 2 * img_bytes;
-  }
+  SDSO_HIP(ctx, S.raw.reserve(ctx->stream, bytes, 2 * img_bytes));
   IngestImages A;
   for (int i = 0; i < 2; i++) A.img[i] = IngestImage{nullptr, nullptr, PHOTO_LINEAR};
   for (int i = 0; i < n_images; i++) {

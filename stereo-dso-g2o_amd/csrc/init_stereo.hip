@@ -37,15 +37,15 @@ enum { INIT_R_PNT = 0, INIT_R_U, INIT_R_V, INIT_R_TYPE, INIT_R_IDEPTH, INIT_R_IM
 struct InitState {
   TraceBatch tb;                    // the Pnts as ImmaturePoints, as their traceStereo left them
   int cap = 0;                      // Pnts the buffers below hold
-  float* d_type = nullptr;          // my_type per Pnt
-  char* d_pnt = nullptr;            // InitPnts
-  float* d_rec = nullptr;           // kInitRecWords per point made
-  uint8_t *d_keep = nullptr, *d_sel = nullptr;   // the caller's flags; 1 = the Pnt becomes a point
-  int* d_seg = nullptr;             // segment counts / offsets of the compaction of STEP 3
-  int* d_counts = nullptr;          // SDSO_INIT_NCOUNTS | kInitSelCounts | candidates | points made
-  int* h_counts = nullptr;          // pinned mirror of d_counts
-  char* h_pnt = nullptr;            // pinned, cap Pnts
-  float* h_rec = nullptr;           // pinned, cap records
+  DevBuf<float> d_type;             // my_type per Pnt
+  DevBuf<char> d_pnt;               // InitPnts
+  DevBuf<float> d_rec;              // kInitRecWords per point made
+  DevBuf<uint8_t> d_keep, d_sel;    // the caller's flags; 1 = the Pnt becomes a point
+  DevBuf<int> d_seg;                // segment counts / offsets of the compaction of STEP 3
+  DevBuf<int> d_counts;             // SDSO_INIT_NCOUNTS | kInitSelCounts | candidates | points made
+  PinBuf<int> h_counts;             // mirror of d_counts
+  PinBuf<char> h_pnt;               // cap Pnts
+  PinBuf<float> h_rec;              // cap records
   hipEvent_t ev = nullptr;          // behind the latest sdso_init_from_initializer's counts on their way to h_counts
   StageBuf stage;                   // a caller's map and flags on their way to the device
   bool valid = false, pts_valid = false, pts_pending = false;
@@ -53,21 +53,9 @@ struct InitState {
 };
 constexpr int kInitCountInts = SDSO_INIT_NCOUNTS + kInitSelCounts + 2, kInitCandAt = SDSO_INIT_NCOUNTS + kInitSelCounts, kInitMadeAt = kInitCandAt + 1;
 
-static void init_free_points(InitState& S) {
-  for (void* p : {(void*)S.d_type, (void*)S.d_pnt, (void*)S.d_rec, (void*)S.d_keep, (void*)S.d_sel, (void*)S.d_seg})
-    if (p) hipFree(p);
-  if (S.h_pnt) hipHostFree(S.h_pnt);
-  if (S.h_rec) hipHostFree(S.h_rec);
-  S.d_type = nullptr; S.d_pnt = nullptr; S.d_rec = nullptr; S.d_keep = S.d_sel = nullptr; S.d_seg = nullptr; S.h_pnt = nullptr; S.h_rec = nullptr;
-  S.cap = 0;
-}
 void release_init_stereo(sdso_ctx* ctx) {
   InitState* S = ctx->init;
   if (!S) return;
-  trace_free(S->tb);
-  init_free_points(*S);
-  if (S->d_counts) hipFree(S->d_counts);
-  if (S->h_counts) hipHostFree(S->h_counts);
   if (S->ev) hipEventDestroy(S->ev);
   stage_free(S->stage);
   delete S;
@@ -75,24 +63,22 @@ void release_init_stereo(sdso_ctx* ctx) {
 }
 // the state's buffers for n Pnts; what an earlier call left in them is given up
 static int init_reserve(sdso_ctx* ctx, InitState& S, int n) {
-  if (!S.d_counts) {
-    SDSO_HIP(ctx, hipMalloc((void**)&S.d_counts, sizeof(int) * kInitCountInts));
-    SDSO_HIP(ctx, hipHostMalloc((void**)&S.h_counts, sizeof(int) * kInitCountInts));
-    SDSO_HIP(ctx, hipEventCreateWithFlags(&S.ev, hipEventDisableTiming));
-  }
+  SDSO_HIP(ctx, S.d_counts.reserve(ctx->stream, kInitCountInts, kInitCountInts));
+  SDSO_HIP(ctx, S.h_counts.reserve(ctx->stream, kInitCountInts, kInitCountInts));
+  if (!S.ev) SDSO_HIP(ctx, hipEventCreateWithFlags(&S.ev, hipEventDisableTiming));
   SDSO_TRY(trace_reserve(ctx, S.tb, n));
   if (S.cap >= n) return SDSO_OK;
-  SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  init_free_points(S);
-  const size_t C = (size_t)n + n / 4 + 64;
-  SDSO_HIP(ctx, hipMalloc((void**)&S.d_type, sizeof(float) * C));
-  SDSO_HIP(ctx, hipMalloc((void**)&S.d_pnt, kInitPntBytes * C));
-  SDSO_HIP(ctx, hipMalloc((void**)&S.d_rec, sizeof(float) * kInitRecWords * C));
-  SDSO_HIP(ctx, hipMalloc((void**)&S.d_keep, C));
-  SDSO_HIP(ctx, hipMalloc((void**)&S.d_sel, C));
-  SDSO_HIP(ctx, hipMalloc((void**)&S.d_seg, sizeof(int) * ((C + 255) / 256 + 1)));
-  SDSO_HIP(ctx, hipHostMalloc((void**)&S.h_pnt, kInitPntBytes * C));
-  SDSO_HIP(ctx, hipHostMalloc((void**)&S.h_rec, sizeof(float) * kInitRecWords * C));
+  const size_t C = (size_t)n + n / 4 + 64, nseg = (C + 255) / 256 + 1;
+  S.cap = 0;   // a group (devbuf.h)
+  SDSO_HIP(ctx, devbuf::reset_all(ctx->stream, S.d_type, S.d_pnt, S.d_rec, S.d_keep, S.d_sel, S.d_seg, S.h_pnt, S.h_rec));
+  SDSO_HIP(ctx, S.d_type.reserve(ctx->stream, C, C));
+  SDSO_HIP(ctx, S.d_pnt.reserve(ctx->stream, kInitPntBytes * C, kInitPntBytes * C));
+  SDSO_HIP(ctx, S.d_rec.reserve(ctx->stream, kInitRecWords * C, kInitRecWords * C));
+  SDSO_HIP(ctx, S.d_keep.reserve(ctx->stream, C, C));
+  SDSO_HIP(ctx, S.d_sel.reserve(ctx->stream, C, C));
+  SDSO_HIP(ctx, S.d_seg.reserve(ctx->stream, nseg, nseg));
+  SDSO_HIP(ctx, S.h_pnt.reserve(ctx->stream, kInitPntBytes * C, kInitPntBytes * C));
+  SDSO_HIP(ctx, S.h_rec.reserve(ctx->stream, kInitRecWords * C, kInitRecWords * C));
   S.cap = (int)C;
   return SDSO_OK;
 }
@@ -271,7 +257,7 @@ extern "C" int sdso_init_set_first_stereo(sdso_ctx* ctx, int frame_slot, int rig
   if (counts) {
     SDSO_HIP(ctx, hipMemcpyAsync(S.h_counts, S.d_counts, sizeof(int) * SDSO_INIT_NCOUNTS, hipMemcpyDeviceToHost, ctx->stream));
     SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::copy(S.h_counts, S.h_counts + SDSO_INIT_NCOUNTS, counts);
+    std::copy(S.h_counts.get(), S.h_counts + SDSO_INIT_NCOUNTS, counts);
   }
   return SDSO_OK;
 }

@@ -28,7 +28,11 @@ constexpr int MAP_MAX_FRAMES = 8;                    // frames of one window / o
 constexpr int MAP_MAX_SEGS = MAP_MAX_FRAMES * 4;     // cloud: immature, active, marginalised, out per frame
 constexpr int MAP_NLIST = 3;
 
-struct MapList { float* d = nullptr; int n = 0, cap = 0; };
+struct MapList {
+  DevBuf<float> d;
+  int n = 0;
+  int cap() const { return (int)(d.cap() / MAP_REC_FLOATS); }   // records
+};
 struct MapKeyframe { MapList list[MAP_NLIST]; };     // [status - 1]
 // one destination of k_map_gather: items [begin, next begin) go to dst + (item - begin) records
 struct MapGatherSeg { float* dst; int begin, pad; };
@@ -45,11 +49,11 @@ struct MapQuery {
 struct MapState {
   std::map<int, MapKeyframe> kf;
   StageBuf stage;
-  int* d_idx = nullptr; size_t idx_cap = 0;          // the staged point indices of sdso_map_update
+  DevBuf<int> d_idx;                                  // the staged point indices of sdso_map_update
   // sdso_map_cloud: [MapQuery | seg_kept MAP_MAX_SEGS ints | masks nwaves x 8 B] and the two output arrays
-  char* d_work = nullptr; size_t work_cap = 0;
-  float* d_xyz = nullptr; size_t xyz_cap = 0;        // floats
-  uint8_t* d_rgb = nullptr; size_t rgb_cap = 0;      // bytes
+  DevBuf<char> d_work;
+  DevBuf<float> d_xyz;
+  DevBuf<uint8_t> d_rgb;
   int cloud_n = -1;                                   // vertices of the latest call; -1: none yet
 };
 static MapState& map_state(sdso_ctx* ctx) { if (!ctx->map) ctx->map = new MapState(); return *ctx->map; }
@@ -58,38 +62,23 @@ static MapKeyframe* map_find(sdso_ctx* ctx, int frameID) {
   auto it = ctx->map->kf.find(frameID);
   return it == ctx->map->kf.end() ? nullptr : &it->second;
 }
-static void map_free_kf(MapKeyframe& K) { for (MapList& L : K.list) { if (L.d) hipFree(L.d); L = MapList(); } }
 void release_map(sdso_ctx* ctx) {
-  MapState* S = ctx->map;
-  if (!S) return;
-  for (auto& kv : S->kf) map_free_kf(kv.second);
-  if (S->d_idx) hipFree(S->d_idx);
-  if (S->d_work) hipFree(S->d_work);
-  if (S->d_xyz) hipFree(S->d_xyz);
-  if (S->d_rgb) hipFree(S->d_rgb);
-  stage_free(S->stage);
-  delete S;
+  if (!ctx->map) return;
+  stage_free(ctx->map->stage);
+  delete ctx->map;
   ctx->map = nullptr;
 }
 // room for `want` records, the first `keep` of them carried over.  A list that grows is allocated anew (doubling) and copied device to
-// device; the old block is freed once the stream has drained, since launches that read it may still be in flight.
+// device; the old block is freed once the stream has drained, since launches that read it may still be in flight.  The new block is `d`'s
+// until then: a failure on the way frees it.
 static int map_reserve(sdso_ctx* ctx, MapList& L, int want, int keep) {
-  if (want <= L.cap) return SDSO_OK;
-  const int cap = std::max(std::max(want, 2 * L.cap), 64);
-  float* d = nullptr;
-  SDSO_HIP(ctx, hipMalloc(&d, sizeof(float) * MAP_REC_FLOATS * (size_t)cap));
+  if (want <= L.cap()) return SDSO_OK;
+  const size_t floats = MAP_REC_FLOATS * (size_t)std::max(std::max(want, 2 * L.cap()), 64);
+  DevBuf<float> d;
+  SDSO_HIP(ctx, d.reserve(ctx->stream, floats, floats));
   if (keep) SDSO_HIP(ctx, hipMemcpyAsync(d, L.d, sizeof(float) * MAP_REC_FLOATS * (size_t)keep, hipMemcpyDeviceToDevice, ctx->stream));
-  if (L.d) { SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream)); hipFree(L.d); }
-  L.d = d; L.cap = cap;
-  return SDSO_OK;
-}
-template <class T>
-static int map_grow(sdso_ctx* ctx, T** p, size_t* cap, size_t want) {   // contents are not kept
-  if (want <= *cap) return SDSO_OK;
-  if (*p) { SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream)); hipFree(*p); *p = nullptr; *cap = 0; }
-  const size_t n = want + want / 2 + 64;
-  SDSO_HIP(ctx, hipMalloc(p, sizeof(T) * n));
-  *cap = n;
+  if (L.d) SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  L.d = std::move(d);
   return SDSO_OK;
 }
 
@@ -292,7 +281,7 @@ extern "C" int sdso_map_update(sdso_ctx* ctx, int win, const sdso_map_update_t* 
     A.n = (int)idx.size();
     A.seg[A.nseg] = MapGatherSeg{nullptr, A.n, 0};
     if (!A.n) return SDSO_OK;
-    SDSO_TRY(map_grow(ctx, &S.d_idx, &S.idx_cap, (size_t)A.n));
+    SDSO_HIP(ctx, S.d_idx.reserve(ctx->stream, (size_t)A.n, (size_t)A.n + (size_t)A.n / 2 + 64));
     char* stage = nullptr;
     SDSO_TRY(stage_reserve(ctx, S.stage, sizeof(int) * (size_t)A.n, &stage));
     std::memcpy(stage, idx.data(), sizeof(int) * (size_t)A.n);
@@ -304,7 +293,7 @@ extern "C" int sdso_map_update(sdso_ctx* ctx, int win, const sdso_map_update_t* 
   };
   const int rc = enqueue();
   if (rc) {
-    for (int id : created) { auto it = S.kf.find(id); map_free_kf(it->second); S.kf.erase(it); }
+    for (int id : created) S.kf.erase(id);
     return rc;
   }
   for (int h = 0; h < nf; h++) for (int l = 0; l < MAP_NLIST; l++) S.kf[frameID[h]].list[l].n = new_n[h][l];
@@ -356,7 +345,6 @@ extern "C" int sdso_map_release_keyframe(sdso_ctx* ctx, int frameID) {
   if (it == ctx->map->kf.end()) return SDSO_OK;
   SDSO_HIP(ctx, hipSetDevice(ctx->device));
   SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));        // launches that read its lists may still be in flight
-  map_free_kf(it->second);
   ctx->map->kf.erase(it);
   return SDSO_OK;
 }
@@ -366,7 +354,6 @@ extern "C" int sdso_map_clear(sdso_ctx* ctx) {
   if (!ctx->map) return SDSO_OK;
   SDSO_HIP(ctx, hipSetDevice(ctx->device));
   SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  for (auto& kv : ctx->map->kf) map_free_kf(kv.second);
   ctx->map->kf.clear();
   return SDSO_OK;
 }
@@ -426,10 +413,11 @@ extern "C" int sdso_map_cloud(sdso_ctx* ctx, const sdso_map_cloud_t* C, float* x
   // ---- one upload of the query, two kernels
   constexpr size_t kept_off = (sizeof(MapQuery) + 255) & ~(size_t)255, mask_off = kept_off + 256;
   static_assert(MAP_MAX_SEGS * sizeof(int) <= 256, "the per-list counters fit their block");
-  SDSO_TRY(map_grow(ctx, &S.d_work, &S.work_cap, mask_off + sizeof(unsigned long long) * (size_t)nwaves));
+  const size_t work = mask_off + sizeof(unsigned long long) * (size_t)nwaves, out = (size_t)total * MAP_PATTERN * 3;
+  SDSO_HIP(ctx, S.d_work.reserve(ctx->stream, work, work + work / 2 + 64));
   S.cloud_n = -1;
-  SDSO_TRY(map_grow(ctx, &S.d_xyz, &S.xyz_cap, (size_t)total * MAP_PATTERN * 3));
-  SDSO_TRY(map_grow(ctx, &S.d_rgb, &S.rgb_cap, (size_t)total * MAP_PATTERN * 3));
+  SDSO_HIP(ctx, S.d_xyz.reserve(ctx->stream, out, out + out / 2 + 64));
+  SDSO_HIP(ctx, S.d_rgb.reserve(ctx->stream, out, out + out / 2 + 64));
   char* stage = nullptr;
   SDSO_TRY(stage_reserve(ctx, S.stage, sizeof(MapQuery), &stage));
   std::memcpy(stage, &Q, sizeof(Q));

@@ -45,7 +45,12 @@ struct RefRecDev {
   __host__ __device__ int* counts() const { return i32 + (size_t)RW_NINT * cap; }
 };
 // stale: the slot has taken a template from elsewhere since (sdso_track_import_ref): the records are not that template's
-struct RefRecSet { RefRecDev d{nullptr, nullptr, nullptr, 0}; int n = 0; bool stale = false; };
+struct RefRecSet {
+  DevBuf<int> i32; DevBuf<float> f32; DevBuf<uint8_t> u8;   // what `d` views (reserve_records)
+  RefRecDev d{nullptr, nullptr, nullptr, 0};
+  int n = 0;
+  bool stale = false;
+};
 struct RefWinState { std::map<int, RefRecSet> sets; };
 
 void refwin_forget_slot(sdso_ctx* ctx, int ref_slot) {
@@ -55,8 +60,6 @@ void refwin_forget_slot(sdso_ctx* ctx, int ref_slot) {
 }
 
 void release_refwin(sdso_ctx* ctx) {
-  if (!ctx->refwin) return;
-  for (auto& kv : ctx->refwin->sets) { hipFree(kv.second.d.i32); hipFree(kv.second.d.f32); hipFree(kv.second.d.u8); }
   delete ctx->refwin;
   ctx->refwin = nullptr;
 }
@@ -155,15 +158,14 @@ __global__ __launch_bounds__(256) void k_ref_accept(int n, RefRecDev R, const fl
 
 int reserve_records(sdso_ctx* ctx, RefRecSet& S, int n) {
   if (S.d.cap >= n) return SDSO_OK;
-  SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  hipFree(S.d.i32); hipFree(S.d.f32); hipFree(S.d.u8);
-  S.d = RefRecDev{nullptr, nullptr, nullptr, 0};
+  S.d = RefRecDev{nullptr, nullptr, nullptr, 0};   // a group (devbuf.h): the view names no buffer until all three are there
   S.n = 0;
+  SDSO_HIP(ctx, devbuf::reset_all(ctx->stream, S.i32, S.f32, S.u8));
   const int cap = n + n / 4 + 64;
-  SDSO_HIP(ctx, hipMalloc(&S.d.i32, sizeof(int) * ((size_t)RW_NINT * cap + 4)));
-  SDSO_HIP(ctx, hipMalloc(&S.d.f32, sizeof(float) * (size_t)RW_NFLT * cap));
-  SDSO_HIP(ctx, hipMalloc(&S.d.u8, (size_t)RW_NBYTE * cap));
-  S.d.cap = cap;
+  SDSO_HIP(ctx, S.i32.reserve(ctx->stream, (size_t)RW_NINT * cap + 4, (size_t)RW_NINT * cap + 4));
+  SDSO_HIP(ctx, S.f32.reserve(ctx->stream, (size_t)RW_NFLT * cap, (size_t)RW_NFLT * cap));
+  SDSO_HIP(ctx, S.u8.reserve(ctx->stream, (size_t)RW_NBYTE * cap, (size_t)RW_NBYTE * cap));
+  S.d = RefRecDev{S.i32, S.f32, S.u8, cap};
   return SDSO_OK;
 }
 

@@ -12,6 +12,7 @@
 #include "../../include/sdso_abi.h"
 #include "tile0_layout.h"
 #include "share.h"
+#include "devbuf.h"
 
 namespace sdso {
 
@@ -52,6 +53,18 @@ struct HipShareBackend {   // share.h's backend
     else hipFree(p);
   }
 };
+struct HipBufBackend {   // devbuf.h's backend
+  typedef hipError_t Error;
+  typedef hipStream_t Stream;
+  Error dev_alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+  void dev_free(void* p) { hipFree(p); }
+  Error host_alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+  void host_free(void* p) { hipHostFree(p); }
+  Error stream_sync(Stream s) { return hipStreamSynchronize(s); }
+};
+// the work buffers a ctx owns alone (devbuf.h): device memory and pinned host memory
+template <class T> using DevBuf = devbuf::Buf<HipBufBackend, T, devbuf::DEVICE>;
+template <class T> using PinBuf = devbuf::Buf<HipBufBackend, T, devbuf::PINNED>;
 typedef share::Block<HipShareBackend> ShareBlock;
 typedef pool::Pool<HipShareBackend> DevPool;   // the device buffer pool (pool.h, pool.hip), attached by sdso_ctx_set_pool
 // the slot gives up its view of `blk`; unsynced: work the ctx enqueued on it may still run on `stream` (an event is left in the block
@@ -145,14 +158,11 @@ struct sdso_ctx {
   std::shared_ptr<sdso::Comm> comm;     // shared with the contexts joined by sdso_comm_attach
   sdso::DevPool* pool = nullptr;        // sdso_ctx_set_pool (a reference of the ctx's own): where level buffers come from and go to; null: hipMalloc / hipFree
   // generic scratch
-  void* scratch = nullptr;
-  size_t scratch_bytes = 0;
+  sdso::DevBuf<void> scratch;
   // k_track_lm's cluster records: written by that kernel only, with tags that grow from call to call (no clearing between calls)
-  void* lm_clusters = nullptr;
-  size_t lm_clusters_bytes = 0;
+  sdso::DevBuf<void> lm_clusters;
   int lm_epoch = 0;
-  void* pinned = nullptr;
-  size_t pinned_bytes = 0;
+  sdso::PinBuf<void> pinned;
   int n_cu = 256;
   // CU partition (sdso_ctx_partition_cus): `stream` is masked to the large share of the CUs, `aux` to the small one; inside a batch's
   // resident GN loop the linearisation runs on `stream`, the Schur accumulation and the fused tail kernel on `aux` — next to the
@@ -162,7 +172,7 @@ struct sdso_ctx {
   int aux_cus = 0;
   int keep_depth_map = 0;   // sdso_track_keep_depth_map: templates built by track_make_ref_dev keep their level-0 map (RefDev::dmap)
   int gn_mode = 0;   // traceStereo refinement: 0 DSO-native, 1 fork-live g2o GN (sdso_trace_set_gn_mode)
-  float* gammaB = nullptr;   // device copy of CalibHessian::B (256 floats) for the gamma-weighted absSquaredGrad; null = identity response
+  sdso::DevBuf<float> gammaB;   // device copy of CalibHessian::B (256 floats) for the gamma-weighted absSquaredGrad; null = identity response
   // device buffers of released BA windows, kept for the next upload (a window is re-uploaded for every keyframe)
   std::vector<std::pair<void*, size_t>> ba_pool;
   // optional in-library kernel timing (HIP events on ctx->stream), see sdso_prof_*
@@ -326,18 +336,19 @@ struct ProfScope {
 // the dispatch itself (the timestamps rocprofv3 reports), where a pair of hipEventRecord calls around the launch also counts the
 // dispatch latency after the first record (≈ 10 us on a 390-us kernel: bench.py's figure sat 2.5 % above rocprofv3's).
 // SDSO_PROF_BRACKET=1: the old record / launch / record bracket.
-template <typename K, typename... A>
-inline void launch_timed(sdso_ctx* ctx, const char* name, int level, K kernel, const dim3& grid, const dim3& block, A... args) {
+// The arguments convert to the kernel's parameter types P, as in a plain call (a DevBuf names its pointer).
+template <typename... P, typename... A>
+inline void launch_timed(sdso_ctx* ctx, const char* name, int level, void (*kernel)(P...), const dim3& grid, const dim3& block, const A&... args) {
   static const bool bracket = dbg_env("SDSO_PROF_BRACKET") != nullptr;
   if (ctx->prof_on >= level && !bracket) {
     hipEvent_t ea = nullptr, eb = nullptr;
     hipEventCreate(&ea); hipEventCreate(&eb);
-    hipExtLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, ea, eb, 0, args...);
+    hipExtLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, ea, eb, 0, static_cast<P>(args)...);
     ctx->prof[name].ev.emplace_back(ea, eb);
     return;
   }
   ProfScope ps(ctx, name, level);
-  hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, args...);
+  hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, static_cast<P>(args)...);
 }
 int ensure_pinned(sdso_ctx* ctx, size_t bytes);
 // Pinned host staging for the enqueue-only entry points (window uploads and table refreshes of the BA, raw images of the frame ingest),

@@ -214,11 +214,11 @@ __global__ __launch_bounds__(256) void k_ps_thin(float* __restrict__ map, int w,
 
 namespace sdso {
 struct SelState {
-  unsigned char* d_rnd = nullptr;
+  DevBuf<unsigned char> d_rnd;   // the pattern for w x h
   std::vector<unsigned char> h_rnd;
   int w = 0, h = 0;
   // the final map of the latest sdso_pixel_select, kept for sdso_imm_add_frame(selection_map == NULL)
-  float* d_final = nullptr;
+  DevBuf<float> d_final;
   int final_slot = -1, final_num = 0;
 };
 bool selector_final_map(sdso_ctx* ctx, int frame_slot, int w, int h, const float** map, int* num) {
@@ -231,9 +231,6 @@ void selector_forget_slot(sdso_ctx* ctx, int frame_slot) {
   if (ctx->sel && ctx->sel->final_slot == frame_slot) ctx->sel->final_slot = -1;
 }
 void release_selector(sdso_ctx* ctx) {
-  if (!ctx->sel) return;
-  if (ctx->sel->d_rnd) hipFree(ctx->sel->d_rnd);
-  if (ctx->sel->d_final) hipFree(ctx->sel->d_final);
   delete ctx->sel;
   ctx->sel = nullptr;
 }
@@ -262,11 +259,12 @@ extern "C" int sdso_pixel_select(sdso_ctx* ctx, int frame_slot, float density, i
   if (!ctx->sel) ctx->sel = new SelState();
   SelState& S = *ctx->sel;
   if (S.w != w || S.h != h) {
-    if (S.d_rnd) { SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream)); hipFree(S.d_rnd); S.d_rnd = nullptr; }
-    if (S.d_final) { hipFree(S.d_final); S.d_final = nullptr; }
+    S.w = S.h = 0;   // (no pattern for any size until the new one is in place)
+    SDSO_HIP(ctx, S.d_rnd.reset(ctx->stream));
+    SDSO_HIP(ctx, S.d_final.reset(ctx->stream));
     S.final_slot = -1;
     glibc_rand_bytes(3141592u, (size_t)w * h, S.h_rnd);
-    SDSO_HIP(ctx, hipMalloc(&S.d_rnd, (size_t)w * h));
+    SDSO_HIP(ctx, S.d_rnd.reserve(ctx->stream, (size_t)w * h, (size_t)w * h));
     SDSO_HIP(ctx, hipMemcpy(S.d_rnd, S.h_rnd.data(), (size_t)w * h, hipMemcpyHostToDevice));
     S.w = w; S.h = h;
   }
@@ -363,7 +361,7 @@ extern "C" int sdso_pixel_select(sdso_ctx* ctx, int frame_slot, float density, i
   }
   *potential = idealPotential;
   *num_out = numHaveSub;
-  if (!S.d_final) SDSO_HIP(ctx, hipMalloc(&S.d_final, sizeof(float) * npx));
+  SDSO_HIP(ctx, S.d_final.reserve(ctx->stream, npx, npx));
   SDSO_HIP(ctx, hipMemcpyAsync(S.d_final, d_map, sizeof(float) * npx, hipMemcpyDeviceToDevice, ctx->stream));
   S.final_slot = frame_slot; S.final_num = numHaveSub;
   if (map_out) SDSO_HIP(ctx, hipMemcpyAsync(map_out, d_map, sizeof(float) * npx, hipMemcpyDeviceToHost, ctx->stream));

@@ -29,8 +29,8 @@ static_assert(kTbMembers[3].off == kTbInOut && kTbMembers[6].off + kTbMembers[6]
 // device-resident batch used by both the host-buffer entry point and the benchmark
 struct TraceBatch {
   TraceDev T;
-  float* blob = nullptr;   // all float arrays
-  uint8_t* bytes = nullptr;
+  DevBuf<float> blob;      // all float arrays
+  DevBuf<uint8_t> bytes;
   int n = 0;               // the stride: points reserved, >= T.n
   float* col(int c) const { return blob + (size_t)c * n; }
   // the private areas, which no TraceDev member names
@@ -52,12 +52,12 @@ static TraceBatch* prepared_trace(sdso_ctx* ctx) { return ctx && ctx->stereo ? c
 
 static int trace_reserve(sdso_ctx* ctx, TraceBatch& B, int n) {
   if (B.n >= n) return SDSO_OK;
-  SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (B.blob) hipFree(B.blob);
-  if (B.bytes) hipFree(B.bytes);
-  B.n = n + n / 4 + 64;
-  SDSO_HIP(ctx, hipMalloc(&B.blob, sizeof(float) * (size_t)B.n * kTbFloats));
-  SDSO_HIP(ctx, hipMalloc(&B.bytes, (size_t)B.n * kTbBytes));
+  const size_t cap = (size_t)(n + n / 4 + 64);
+  B.n = 0;   // a group (devbuf.h)
+  SDSO_HIP(ctx, devbuf::reset_all(ctx->stream, B.blob, B.bytes));
+  SDSO_HIP(ctx, B.blob.reserve(ctx->stream, cap * kTbFloats, cap * kTbFloats));
+  SDSO_HIP(ctx, B.bytes.reserve(ctx->stream, cap * kTbBytes, cap * kTbBytes));
+  B.n = (int)cap;
   return SDSO_OK;
 }
 static void trace_bind(TraceBatch& B, int n) {
@@ -76,16 +76,9 @@ static int trace_set_camera(sdso_ctx* ctx, TraceDev& T, PyramidDev& P, const flo
   T.fx = K[0]; T.fy = K[1]; T.cx = K[2]; T.cy = K[3]; T.baseline = baseline;
   return SDSO_OK;
 }
-static void trace_free(TraceBatch& B) {
-  if (B.blob) hipFree(B.blob);
-  if (B.bytes) hipFree(B.bytes);
-}
 void release_stereo(sdso_ctx* ctx) {
-  StereoState* S = ctx->stereo;
-  if (!S) return;
-  if (S->trace) { trace_free(*S->trace); delete S->trace; }
-  for (TraceBatch& B : S->match) trace_free(B);
-  delete S;
+  if (ctx->stereo) delete ctx->stereo->trace;
+  delete ctx->stereo;
   ctx->stereo = nullptr;
 }
 }  // namespace sdso

@@ -24,21 +24,15 @@ struct TrackOut {
 
 struct TrackBatch {
   int cap = 0, nprob = 0, gx = 0;
-  TrackProb* d_probs = nullptr;
-  float* d_partF = nullptr;
-  int* d_partI = nullptr;
-  TrackOut* d_out = nullptr;
+  DevBuf<TrackProb> d_probs;
+  DevBuf<float> d_partF;
+  DevBuf<int> d_partI;
+  DevBuf<TrackOut> d_out;
   size_t part_cap = 0;
 };
 
 void release_track_batch(sdso_ctx* ctx) {
-  if (!ctx->tb) return;
-  TrackBatch* tb = ctx->tb;
-  if (tb->d_probs) hipFree(tb->d_probs);
-  if (tb->d_partF) hipFree(tb->d_partF);
-  if (tb->d_partI) hipFree(tb->d_partI);
-  if (tb->d_out) hipFree(tb->d_out);
-  delete tb;
+  delete ctx->tb;
   ctx->tb = nullptr;
 }
 

@@ -74,22 +74,22 @@ static int resolve_prob(sdso_ctx* ctx, int ref_slot, int frame_slot, const sdso_
 static int batch_reserve(sdso_ctx* ctx, int nprob, int gx) {
   if (!ctx->tb) ctx->tb = new TrackBatch();
   TrackBatch* tb = ctx->tb;
-  if (tb->cap < nprob) {
-    SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (tb->d_probs) hipFree(tb->d_probs);
-    if (tb->d_out) hipFree(tb->d_out);
-    tb->cap = nprob + nprob / 2 + 8;
-    SDSO_HIP(ctx, hipMalloc(&tb->d_probs, sizeof(TrackProb) * tb->cap));
-    SDSO_HIP(ctx, hipMalloc(&tb->d_out, sizeof(TrackOut) * tb->cap));
+  if (tb->cap < nprob) {   // two groups (devbuf.h), each with a count of its own
+    const size_t cap = (size_t)nprob + nprob / 2 + 8;
+    tb->cap = 0;
+    SDSO_HIP(ctx, devbuf::reset_all(ctx->stream, tb->d_probs, tb->d_out));
+    SDSO_HIP(ctx, tb->d_probs.reserve(ctx->stream, cap, cap));
+    SDSO_HIP(ctx, tb->d_out.reserve(ctx->stream, cap, cap));
+    tb->cap = (int)cap;
   }
-  size_t need = (size_t)nprob * gx;
+  const size_t need = (size_t)nprob * gx;
   if (tb->part_cap < need) {
-    SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (tb->d_partF) hipFree(tb->d_partF);
-    if (tb->d_partI) hipFree(tb->d_partI);
-    tb->part_cap = need + need / 2 + 64;
-    SDSO_HIP(ctx, hipMalloc(&tb->d_partF, sizeof(float) * TRK_NF * tb->part_cap));
-    SDSO_HIP(ctx, hipMalloc(&tb->d_partI, sizeof(int) * TRK_NI * tb->part_cap));
+    const size_t cap = need + need / 2 + 64;
+    tb->part_cap = 0;
+    SDSO_HIP(ctx, devbuf::reset_all(ctx->stream, tb->d_partF, tb->d_partI));
+    SDSO_HIP(ctx, tb->d_partF.reserve(ctx->stream, TRK_NF * cap, TRK_NF * cap));
+    SDSO_HIP(ctx, tb->d_partI.reserve(ctx->stream, TRK_NI * cap, TRK_NI * cap));
+    tb->part_cap = cap;
   }
   return SDSO_OK;
 }

@@ -66,16 +66,10 @@ extern "C" int sdso_track_newest_coarse_batch(sdso_ctx* ctx, int nhyp, const int
   const size_t jobs_bytes = (sizeof(LmJob) * (size_t)nhyp + 255) & ~(size_t)255;
   rc = ensure_scratch(ctx, jobs_bytes);
   if (rc) return rc;
-  if (ctx->lm_clusters_bytes < sizeof(LmCluster) * (size_t)nhyp || ctx->lm_epoch > (1 << 30)) {
+  if (ctx->lm_clusters.cap() < sizeof(LmCluster) * (size_t)nhyp || ctx->lm_epoch > (1 << 30)) {
     SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->lm_clusters_bytes < sizeof(LmCluster) * (size_t)nhyp) {
-      if (ctx->lm_clusters) SDSO_HIP(ctx, hipFree(ctx->lm_clusters));
-      ctx->lm_clusters = nullptr; ctx->lm_clusters_bytes = 0;
-      const size_t want = sizeof(LmCluster) * (size_t)std::max(nhyp, 8);
-      SDSO_HIP(ctx, hipMalloc(&ctx->lm_clusters, want));
-      ctx->lm_clusters_bytes = want;
-    }
-    SDSO_HIP(ctx, hipMemsetAsync(ctx->lm_clusters, 0, ctx->lm_clusters_bytes, ctx->stream));
+    SDSO_HIP(ctx, ctx->lm_clusters.reserve(ctx->stream, sizeof(LmCluster) * (size_t)nhyp, sizeof(LmCluster) * (size_t)std::max(nhyp, 8)));
+    SDSO_HIP(ctx, hipMemsetAsync(ctx->lm_clusters, 0, ctx->lm_clusters.cap(), ctx->stream));
     ctx->lm_epoch = 0;
   }
   LmJob* hj = (LmJob*)ctx->pinned;
