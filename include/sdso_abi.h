@@ -399,6 +399,84 @@ int sdso_track_newest_coarse_batch(sdso_ctx* ctx, int nhyp, const int* ref_slots
                                    const sdso_track_params_t* prms, sdso_se3_t* lastToNew, sdso_aff_t* aff_g2l,
                                    sdso_track_result_t* outs);
 
+/* ---- the motion tries of FullSystem::trackNewCoarse (FullSystem.cpp:436-511), with the loop's own rules.
+ * The loop calls trackNewestCoarse once per initial motion with the running achievedRes as minResForAbort (:445-449), so a later try
+ * sees bounds that earlier tries lowered.  Two facts let the tries run side by side all the same:
+ *   - the abort test (CoarseTracker.cpp:1032) runs every time a level ends, also after the first pass of a level that is then repeated
+ *     with a doubled cutoff (:1036-1040) and whose second pass overwrites lastResiduals[lvl]: the test can be replayed exactly from the
+ *     residual of each of those events — the EVENT TRACE of a try, at most six events (five levels and one repetition);
+ *   - the evaluations of a try do not depend on minResForAbort until the test fires, and achievedRes only falls (or goes from NaN to
+ *     finite): a try that ran under bounds taken at any EARLIER point of the loop recorded every event the loop's own try would have
+ *     produced, up to its abort. */
+#define SDSO_TRACK_MAX_EVENTS 6
+typedef struct {
+  int n;                                        /* events recorded, in order, <= SDSO_TRACK_MAX_EVENTS */
+  int lvl[SDSO_TRACK_MAX_EVENTS];               /* the level that ended */
+  double res[SDSO_TRACK_MAX_EVENTS];            /* lastResiduals[lvl] as written at that event (CoarseTracker.cpp:1029) */
+  double flow[SDSO_TRACK_MAX_EVENTS][3];        /* lastFlowIndicators as written at that event (:1030) */
+} sdso_track_trace_t;
+
+/* One try of the loop.  The members marked `in` are what the try produced when it ran (sdso_track_new_coarse fills them;
+ * sdso_track_tries_replay reads them); the others are what the loop saw. */
+typedef struct {
+  /* in: the try as it ran */
+  sdso_track_trace_t trace;    /* its events, up to its own end (an abort under the bounds it ran with, or the finest level) */
+  int end_good;                /* trackNewestCoarse's verdict if no abort fires (CoarseTracker.cpp:1050-1068) */
+  sdso_se3_t end_pose;         /* lastToNew_out / aff_g2l_out if no abort fires (:1044-1045, :1065-1066) */
+  sdso_aff_t end_aff;
+  /* out: the try as the loop saw it */
+  int ran;                     /* 0: the loop had stopped before this try (:499-500); nothing below is set then */
+  int good;                    /* trackingIsGood (:445) */
+  int abort_lvl;               /* the level the test of CoarseTracker.cpp:1032 fired on under the loop's bounds, -1: none */
+  int winner;                  /* 1: the try took over (FullSystem.cpp:475-484) */
+  double lastResiduals[5];     /* coarseTracker->lastResiduals after the try: NaN for every level below an abort (CoarseTracker.cpp:855) */
+  double lastFlowIndicators[3];
+  sdso_se3_t pose;             /* lastF_2_fh_this / aff_g2l_this after the try: the inputs where the try aborted */
+  sdso_aff_t aff;
+} sdso_track_try_t;
+
+typedef struct {
+  int haveOneGood;             /* FullSystem.cpp:437, :483 */
+  int winner;                  /* index of the try whose pose was kept, -1: none was good */
+  int tryIterations;           /* :438, :451 — the tries the loop ran */
+  sdso_se3_t pose;             /* lastF_2_fh (:482; tries[0] when no try was good, :507) */
+  sdso_aff_t aff;              /* aff_g2l (:481; aff_last_2_l when no try was good, :506) */
+  double flowVecs[3];          /* :480; (100,100,100) cannot remain: a winner sets it, no winner sets (0,0,0) (:505) */
+  double achievedRes[5];       /* :436, :487-496; handed out as it is, NaNs included (:511) */
+} sdso_track_tries_result_t;
+
+/* Host-only, no ctx: the rules of FullSystem.cpp:436-511 over the `in` members of recs[0..ntries-1], in list order.
+ *   - the abort test per event: res > 1.5 * achievedRes[lvl] (false for a NaN bound);
+ *   - a new winner: good && std::isfinite((float)res0) && !(res0 >= achievedRes[0]) (:475-477);
+ *   - the carry, once a try was good: !std::isfinite((float)achievedRes[i]) || achievedRes[i] > res[i] (:490-491) — a NaN residual of
+ *     a level the try did not reach never lowers a bound;
+ *   - the stop: haveOneGood && achievedRes[0] < lastCoarseRMSE[0] * reTrackThreshold (:499);
+ *   - no good try: flowVecs = 0, aff = aff_last_2_l, pose = tries[0] (:503-508).
+ * Fills the `out` members of every record (ran = 0 after the stop), *out, and lastCoarseRMSE = achievedRes (:511).
+ * SDSO_ERR_ARG, nothing written: a null argument, ntries outside 1..64, a trace with n outside 0..6 or a level outside 0..4. */
+#define SDSO_TRACK_MAX_TRIES 64
+int sdso_track_tries_replay(int ntries, const sdso_se3_t* tries, const sdso_aff_t* aff_last_2_l, sdso_track_try_t* recs,
+                            double* lastCoarseRMSE, double reTrackThreshold, sdso_track_tries_result_t* out);
+
+/* FullSystem::trackNewCoarse STEP2-4 (FullSystem.cpp:436-511) on the device, DSO-native LM.
+ *   prm              as for sdso_track_newest_coarse; coarsestLvl is the caller's pyrLevelsUsed-1 (:448); minResForAbort is ignored
+ *   ntries, tries    lastF_2_fh_tries in list order, 1..SDSO_TRACK_MAX_TRIES (the reference builds up to 53, :305-423)
+ *   aff_last_2_l     every try starts from it (:442)
+ *   lastCoarseRMSE   in: the stop rule reads [0] (:499); out: achievedRes (:511)
+ *   reTrackThreshold setting_reTrackThreshold (settings.cpp:79: 1.5; a float there, widened as the comparison of :499 widens it)
+ *   recs             optional, ntries records: every member is written
+ * Phase 1 is try 0 alone, exactly the launch of sdso_track_newest_coarse with NaN bounds; the rules follow, and where the loop stops
+ * there (nearly every frame) the call returns.  Phase 2 runs tries 1..ntries-1 in ONE launch of the batch (sdso_track_newest_coarse_batch:
+ * its grid sizing, its repetition with single workgroups), each under achievedRes as it stands after try 0 — bounds no tighter than
+ * the loop's own at any later try — and the rules then walk the event traces in list order with the tightening bounds.  The outcome is
+ * the sequential loop's on the device's own numbers.  Tries after the one the loop stops at were run for nothing: they are reported
+ * with ran = 0.  No wait between tries or phases exists on the device; the two launches are chained by the host.
+ * Refusals (SDSO_ERR_ARG, before any device work, nothing written): a null argument; ntries out of range; an unknown reference or
+ * frame slot; a frame without the level the call starts on; a level size other than the uploaded one. */
+int sdso_track_new_coarse(sdso_ctx* ctx, int ref_slot, int frame_slot, const sdso_track_params_t* prm, int ntries,
+                          const sdso_se3_t* tries, const sdso_aff_t* aff_last_2_l, double* lastCoarseRMSE, double reTrackThreshold,
+                          sdso_track_tries_result_t* out, sdso_track_try_t* recs);
+
 /* ------------------------------------------------------------------ windowed bundle adjustment
  * One "window" mirrors an EnergyFunctional (src/OptimizationBackend/EnergyFunctional.h:49-150) with
  * its frames / points / residuals flattened in EnergyFunctional::makeIDX order (:998-1018):

@@ -28,6 +28,8 @@
 //   tracker_lm_core.h     LmCore — the LM state machine of trackNewestCoarse, one text for host and device — LmJob, LM_BLOCK / LM_UNROLL
 //   tracker_lm.hip        the LM step on one wave (lm_wave_ldlt, lm_exp_se3_wave, lm_wave_step), LmCluster, k_track_lm
 //   tracker_lm_api.hip    resolve_job, the lock-step host driver, sdso_track_newest_coarse(_batch)
+//   tracker_tries.hip     the motion tries of FullSystem::trackNewCoarse (FullSystem.cpp:436-511): track_tries.h — the loop's rules over
+//                         event traces, plain C++ — sdso_track_tries_replay, sdso_track_new_coarse
 // The rules the tracker shares with g2o_factors.hip (the template level + image level lookup, the coarsestLvl range) are in
 // sdso_internal.h; the sdso_se3_t <-> Se3 conversion is in host_math.h.
 #include "sdso_internal.h"
@@ -42,3 +44,4 @@ using namespace sdso;
 #include "tracker_lm_core.h"
 #include "tracker_lm.hip"
 #include "tracker_lm_api.hip"
+#include "tracker_tries.hip"

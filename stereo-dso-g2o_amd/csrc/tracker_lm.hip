@@ -428,7 +428,7 @@ __global__ __launch_bounds__(LM_BLOCK) void k_track_lm(LmJob* __restrict__ jobs,
     if (tid < TRK_NF) F[tid] = mine; else if (tid < TRK_NF + TRK_NI) I[tid - TRK_NF] = (int)mine;
     __syncthreads();
     if (s_abort) {                              // a member never answered (every member notices): member 0 gives the call back to the host
-      if (leader && tid == 0) { J.out = core.out; J.out.evaluations = -1; }
+      if (leader && tid == 0) { J.out = core.out; J.out.evaluations = -1; J.trace.n = 0; }
       return;
     }
     LMSL(6);
@@ -440,6 +440,11 @@ __global__ __launch_bounds__(LM_BLOCK) void k_track_lm(LmJob* __restrict__ jobs,
 #undef LMSL
   if (leader && tid == 0) {
     J.out = core.out;
+    J.trace.n = core.trace.n;
+    for (int e = 0; e < core.trace.n; e++) {
+      J.trace.lvl[e] = core.trace.lvl[e]; J.trace.res[e] = core.trace.res[e];
+      for (int k = 0; k < 3; k++) J.trace.flow[e][k] = core.trace.flow[e][k];
+    }
     if (core.wrote_final) { J.T = core.T_final; J.aff = core.aff_final; }
 #ifdef SDSO_LM_STAMPS
     for (int k = 0; k < 9; k++) J.T.R[k] = (double)lm_st_acc[k];

@@ -15,7 +15,7 @@ static int resolve_job(sdso_ctx* ctx, int ref_slot, int frame_slot, const sdso_t
 
 // the lock-step host driver (A/B and fallback for SDSO_TRK_HOST_LM=1)
 static int track_newest_coarse_host(sdso_ctx* ctx, int nhyp, const int* ref_slots, const int* frame_slots, const sdso_track_params_t* prms,
-                                    sdso_se3_t* lastToNew, sdso_aff_t* aff_g2l, sdso_track_result_t* outs) {
+                                    sdso_se3_t* lastToNew, sdso_aff_t* aff_g2l, sdso_track_result_t* outs, sdso_track_trace_t* traces) {
   std::vector<LmCore> S(nhyp);
   for (int k = 0; k < nhyp; k++) S[k].init(prms[k], lastToNew[k], aff_g2l[k]);
   std::vector<TrackProb> probs;
@@ -42,13 +42,15 @@ static int track_newest_coarse_host(sdso_ctx* ctx, int nhyp, const int* ref_slot
   }
   for (int k = 0; k < nhyp; k++) {
     outs[k] = S[k].out;
+    if (traces) traces[k] = S[k].trace;
     if (S[k].wrote_final) { lastToNew[k] = S[k].T_final; aff_g2l[k] = S[k].aff_final; }
   }
   return SDSO_OK;
 }
 
-extern "C" int sdso_track_newest_coarse_batch(sdso_ctx* ctx, int nhyp, const int* ref_slots, const int* frame_slots, const sdso_track_params_t* prms,
-                                              sdso_se3_t* lastToNew, sdso_aff_t* aff_g2l, sdso_track_result_t* outs) {
+// sdso_track_newest_coarse_batch; traces (may be null): the event trace of every hypothesis, for sdso_track_new_coarse (tracker_tries.hip)
+static int track_newest_coarse_run(sdso_ctx* ctx, int nhyp, const int* ref_slots, const int* frame_slots, const sdso_track_params_t* prms,
+                                   sdso_se3_t* lastToNew, sdso_aff_t* aff_g2l, sdso_track_result_t* outs, sdso_track_trace_t* traces) {
   if (!ctx) return SDSO_ERR_STATE;
   SDSO_HIP(ctx, hipSetDevice(ctx->device));
   SDSO_REQUIRE(ctx, nhyp > 0 && ref_slots && frame_slots && prms && lastToNew && aff_g2l && outs, "null argument");
@@ -57,7 +59,7 @@ extern "C" int sdso_track_newest_coarse_batch(sdso_ctx* ctx, int nhyp, const int
     if (rc) return rc;
   }
   static const bool host_lm = dbg_env("SDSO_TRK_HOST_LM") != nullptr;
-  if (host_lm) return track_newest_coarse_host(ctx, nhyp, ref_slots, frame_slots, prms, lastToNew, aff_g2l, outs);
+  if (host_lm) return track_newest_coarse_host(ctx, nhyp, ref_slots, frame_slots, prms, lastToNew, aff_g2l, outs, traces);
   // resident driver: jobs through pinned memory, one launch, one synchronisation.  The cluster records are the library's own allocation
   // and are never cleared between calls (tags, see LmCluster).  (The kernel reading the jobs in pinned host memory directly, without
   // the two copies, measured the same 0.305 ms per call: tools/time_track.py, round 5.)
@@ -114,7 +116,13 @@ extern "C" int sdso_track_newest_coarse_batch(sdso_ctx* ctx, int nhyp, const int
     G = 1;                             // a cluster was not co-resident (shared device): the single-workgroup form needs no co-residency
   }
   for (int k = 0; k < nhyp; k++) { outs[k] = hj[k].out; lastToNew[k] = hj[k].T; aff_g2l[k] = hj[k].aff; }
+  if (traces) for (int k = 0; k < nhyp; k++) traces[k] = hj[k].trace;
   return SDSO_OK;
+}
+
+extern "C" int sdso_track_newest_coarse_batch(sdso_ctx* ctx, int nhyp, const int* ref_slots, const int* frame_slots, const sdso_track_params_t* prms,
+                                              sdso_se3_t* lastToNew, sdso_aff_t* aff_g2l, sdso_track_result_t* outs) {
+  return track_newest_coarse_run(ctx, nhyp, ref_slots, frame_slots, prms, lastToNew, aff_g2l, outs, nullptr);
 }
 
 extern "C" int sdso_track_newest_coarse(sdso_ctx* ctx, int ref_slot, int frame_slot, const sdso_track_params_t* prm,

@@ -51,6 +51,8 @@ struct LmCore {
   Se3 reqT; sdso_aff_t reqAff;                  // the evaluation this hypothesis waits for
   double wHl[64], wHs[64], wnb[8], wbs[8], wx[8], wwork[80];   // work space of solve_inc() (members: in LDS on the device)
   int wperm[8];
+  sdso_track_trace_t trace;                     // every finish_level event in order (at most six: five levels and one repetition) — what
+                                                // sdso_track_new_coarse replays the abort test of :1032 from (track_tries.h)
 
   SDSO_HD void init(const sdso_track_params_t& prm, const sdso_se3_t& T0, const sdso_aff_t& aff0) {
     p = prm;
@@ -59,6 +61,7 @@ struct LmCore {
     affCur = aff0;
     T_final = T0; aff_final = aff0; wrote_final = false;
     haveRepeated = false; done = false;
+    trace.n = 0;
     iteration = 0; lambda = 0.01f;
     lvl = p.coarsestLvl;
     for (int i = 0; i < 8; i++) inc[i] = 0;
@@ -84,6 +87,11 @@ struct LmCore {
   SDSO_HD void finish_level() {
     out.lastResiduals[lvl] = sqrtf((float)(oldres[0] / oldres[1]));
     out.lastFlowIndicators[0] = oldres[2]; out.lastFlowIndicators[1] = oldres[3]; out.lastFlowIndicators[2] = oldres[4];
+    if (trace.n < SDSO_TRACK_MAX_EVENTS) {        // the event, before the test: the second pass of a repeated level overwrites lastResiduals[lvl]
+      const int e = trace.n++;
+      trace.lvl[e] = lvl; trace.res[e] = out.lastResiduals[lvl];
+      trace.flow[e][0] = oldres[2]; trace.flow[e][1] = oldres[3]; trace.flow[e][2] = oldres[4];
+    }
     if (out.lastResiduals[lvl] > 1.5 * p.minResForAbort[lvl]) { done = true; return; }  // :1032 (good stays 0, pose untouched)
     if (levelCutoffRepeat > 1 && !haveRepeated) { lvl++; haveRepeated = true; }
     lvl--;
@@ -173,6 +181,7 @@ struct LmJob {
   sdso_se3_t T;            // in: initial lastToNew; out: the call's result (unchanged when the call aborts, like the reference's references)
   sdso_aff_t aff;
   sdso_track_result_t out;
+  sdso_track_trace_t trace;  // out: LmCore::trace (internal: no entry point but sdso_track_new_coarse reads it)
 };
 #ifndef LM_BLOCK_THREADS
 #define LM_BLOCK_THREADS 512

@@ -232,6 +232,51 @@ template <class SE3T, class AffLightT, class Mat33T, class Vec3T> class CoarseTr
     lastStats = out;
     return out.good != 0;
   }
+  // FullSystem::trackNewCoarse STEP2-4 (FullSystem.cpp:436-511) as one member: the loop over lastF_2_fh_tries — trackNewestCoarse per try
+  // under the running achievedRes, the winner, the carry, the stop at lastCoarseRMSE[0] * setting_reTrackThreshold, the ending without a
+  // good try — on the device (sdso_track_new_coarse: try 0 alone; the other tries, where the loop goes on, in one launch).  TriesT is the
+  // reference's std::vector<SE3, Eigen::aligned_allocator<SE3>>; Vec5T / Vec3FlowT its Vec5 / Vec3.
+  //   in    fh, lastF_2_fh_tries, aff_last_2_l, coarsestLvl (pyrLevelsUsed-1, :448), reTrackThreshold (setting_reTrackThreshold)
+  //   inout lastCoarseRMSE (:499, :511)
+  //   out   lastF_2_fh, aff_g2l, flowVecs, achievedRes, tryIterations; returns haveOneGood (the caller prints the BIG ERROR of :504)
+  // Afterwards lastResiduals / lastFlowIndicators are those of the last try the loop ran, as in the reference, and firstCoarseRMSE is
+  // set as :528-529 set it.  lastTries holds one record per try (ran, what the loop saw, the abort level).  DSO-native LM only: with
+  // forkLive the member throws (the fork's g2o tracker inside the loop is not built).
+  template <class FrameHessianT, class TriesT, class Vec5T, class Vec3FlowT>
+  bool trackNewCoarse(FrameHessianT* fh, const TriesT& lastF_2_fh_tries, const AffLightT& aff_last_2_l, int coarsestLvl, Vec5T& lastCoarseRMSE,
+                      float reTrackThreshold, SE3T& lastF_2_fh, AffLightT& aff_g2l, Vec3FlowT& flowVecs, Vec5T& achievedRes, int& tryIterations) {
+    if (!slot_of) throw Error("trackNewCoarse: slot_of not set");
+    return trackNewCoarse(slot_of(fh), fh->ab_exposure, lastF_2_fh_tries, aff_last_2_l, coarsestLvl, lastCoarseRMSE, reTrackThreshold, lastF_2_fh, aff_g2l,
+                          flowVecs, achievedRes, tryIterations);
+  }
+  // ... with the frame given by its pyramid slot
+  template <class TriesT, class Vec5T, class Vec3FlowT>
+  bool trackNewCoarse(int newFrame_slot, float newFrame_ab_exposure, const TriesT& lastF_2_fh_tries, const AffLightT& aff_last_2_l, int coarsestLvl,
+                      Vec5T& lastCoarseRMSE, float reTrackThreshold, SE3T& lastF_2_fh, AffLightT& aff_g2l, Vec3FlowT& flowVecs, Vec5T& achievedRes,
+                      int& tryIterations) {
+    if (forkLive) throw Error("trackNewCoarse: the fork's g2o tracker inside the loop is not built (forkLive must be false)");
+    prm_.new_exposure = newFrame_ab_exposure;
+    prm_.coarsestLvl = coarsestLvl;
+    std::vector<sdso_se3_t> tries;
+    for (const auto& T : lastF_2_fh_tries) tries.push_back(toAbi(T));
+    const sdso_aff_t aff0{aff_last_2_l.a, aff_last_2_l.b};
+    double rmse[5];
+    for (int i = 0; i < 5; i++) rmse[i] = lastCoarseRMSE[i];
+    lastTries.assign(tries.size(), sdso_track_try_t{});
+    dev_.check(sdso_track_new_coarse(dev_.ctx(), ref_slot_, newFrame_slot, &prm_, (int)tries.size(), tries.data(), &aff0, rmse, (double)reTrackThreshold,
+                                     &lastTriesResult, lastTries.data()), "sdso_track_new_coarse");
+    const sdso_track_tries_result_t& r = lastTriesResult;
+    const sdso_track_try_t& last = lastTries[r.tryIterations - 1];       // the tracker's members after the loop: the last try it ran
+    for (int i = 0; i < 5; i++) { lastResiduals[i] = last.lastResiduals[i]; achievedRes[i] = r.achievedRes[i]; lastCoarseRMSE[i] = rmse[i]; }   // :511
+    for (int i = 0; i < 3; i++) { lastFlowIndicators[i] = last.lastFlowIndicators[i]; flowVecs[i] = r.flowVecs[i]; }
+    lastF_2_fh = fromAbi<SE3T, Mat33T, Vec3T>(r.pose);
+    aff_g2l.a = r.aff.a; aff_g2l.b = r.aff.b;
+    tryIterations = r.tryIterations;
+    if (firstCoarseRMSE < 0) firstCoarseRMSE = r.achievedRes[0];         // :528-529
+    return r.haveOneGood != 0;
+  }
+  std::vector<sdso_track_try_t> lastTries;
+  sdso_track_tries_result_t lastTriesResult{};
   // calcRes + calcGSSSE for one (level, pose): what the LM loop evaluates; returns calcRes' Vec6
   void calcResAndGS(int lvl, int newFrame_slot, float newFrame_ab_exposure, const SE3T& refToNew, const AffLightT& aff_g2l, float levelCutoffRepeat,
                     double H_out[64], double b_out[8], double res6[6], int* buf_warped_n = nullptr) {

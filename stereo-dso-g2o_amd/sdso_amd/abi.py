@@ -56,6 +56,24 @@ class TrackResult(C.Structure):
                 ("iterations", C.c_int * 5), ("evaluations", C.c_int), ("point_evals", C.c_longlong)]
 
 
+class TrackTrace(C.Structure):
+    """sdso_track_trace_t: the finish_level events of one try."""
+    _fields_ = [("n", C.c_int), ("lvl", C.c_int * 6), ("res", C.c_double * 6), ("flow", (C.c_double * 3) * 6)]
+
+
+class TrackTry(C.Structure):
+    """sdso_track_try_t: one try of FullSystem::trackNewCoarse's loop — as it ran (trace, end_*) and as the loop saw it."""
+    _fields_ = [("trace", TrackTrace), ("end_good", C.c_int), ("end_pose", SE3), ("end_aff", Aff),
+                ("ran", C.c_int), ("good", C.c_int), ("abort_lvl", C.c_int), ("winner", C.c_int),
+                ("lastResiduals", C.c_double * 5), ("lastFlowIndicators", C.c_double * 3), ("pose", SE3), ("aff", Aff)]
+
+
+class TrackTriesResult(C.Structure):
+    """sdso_track_tries_result_t"""
+    _fields_ = [("haveOneGood", C.c_int), ("winner", C.c_int), ("tryIterations", C.c_int), ("pose", SE3), ("aff", Aff),
+                ("flowVecs", C.c_double * 3), ("achievedRes", C.c_double * 5)]
+
+
 class BAWindow(C.Structure):
     _fields_ = [("nf", C.c_int), ("np", C.c_int), ("nr", C.c_int), ("w", C.c_int), ("h", C.c_int),
                 ("calib_value_scaled", C.c_double * 4), ("calib_value_zero", C.c_double * 4),
@@ -600,6 +618,9 @@ def load():
     L.sdso_pool_trim.argtypes = [vp, C.c_size_t]
     L.sdso_pool_release.argtypes = [vp]
     L.sdso_pool_release.restype = None
+    L.sdso_track_tries_replay.argtypes = [C.c_int, C.POINTER(SE3), C.POINTER(Aff), C.POINTER(TrackTry), c_double_p, C.c_double, C.POINTER(TrackTriesResult)]
+    L.sdso_track_new_coarse.argtypes = [vp, C.c_int, C.c_int, C.POINTER(TrackParams), C.c_int, C.POINTER(SE3), C.POINTER(Aff), c_double_p, C.c_double,
+                                        C.POINTER(TrackTriesResult), C.POINTER(TrackTry)]
     _lib = L
     return L
 
@@ -638,6 +659,7 @@ EXPORTED_SYMBOLS = [
     "sdso_pyramid_export", "sdso_pyramid_import", "sdso_track_export_ref", "sdso_track_import_ref", "sdso_shared_info", "sdso_shared_release",
     "sdso_shared_debug_buffers",
     "sdso_pool_create", "sdso_ctx_set_pool", "sdso_pool_stats", "sdso_pool_trim", "sdso_pool_release",
+    "sdso_track_tries_replay", "sdso_track_new_coarse",
 ]
 
 
