@@ -1364,6 +1364,81 @@ typedef struct {
 int sdso_g2o_lba_eval(sdso_ctx* ctx, const sdso_g2o_lba_t* L, double* error, double* J, uint8_t* state, float* energy,
                       float* centerProjectedTo, float* idepth_hessian, uint8_t* edge_level);
 
+/* FullSystem::optimize as the fork compiles it (FullSystemOptimize.cpp:402-868): g2o's Levenberg-Marquardt with a Schur block solver
+ * over the graph of :455-542, every evaluation, linearisation, Schur complement and back-substitution on the device.  The caller
+ * flattens its graph into arrays as for sdso_g2o_lba_eval; g2o's graph plumbing is not rebuilt.  Everything g2o decides is restated
+ * from its published algorithm ("parity unpinned", above): the call is held to tests/g2o_lba_ref.py, the same algorithm in NumPy.
+ *
+ * W, the graph as :455-542 builds it (constant over the call): */
+typedef struct {
+  int nf, nr, w, h;              /* nf 1..8 frames, nr residuals (edges) in any order; the fork's is host-major (:441-453) */
+  const int* frame_slot;         /* nf level-0 images */
+  const sdso_se3_t* Ttw;         /* nf: r->target->PRE_worldToCam, read by the edge as a constant          dso_g2o_edge.cpp:23 */
+  const sdso_aff_t* target_aff;  /* nf: r->target->aff_g2l()                                               dso_g2o_edge.cpp:87 */
+  const float* ab_exposure;      /* nf: FrameHessian::ab_exposure                                          dso_g2o_edge.cpp:88-89 */
+  const double* host_b0;         /* nf: b0_ (SetB at graph build, never refreshed)                         FullSystemOptimize.cpp:535-536 */
+  const float* frameEnergyTH;    /* nf                                                                     dso_g2o_edge.cpp:119 */
+  const int* host; const int* target;        /* nr: r->host->idx, r->target->idx                           FullSystemOptimize.cpp:478-522 */
+  const float* u; const float* v;            /* nr: r->point->u, v                                         dso_g2o_edge.cpp:36-37 */
+  const float* color; const float* weights;  /* nr*8: the measurement (:524-527) and r->point->weights (dso_g2o_edge.cpp:107) */
+} sdso_g2o_lba_window_t;
+/* S, the vertex estimates: read at entry, written at exit (a refused or failed call writes nothing). */
+typedef struct {
+  sdso_se3_t* Twh;               /* nf: VertexSE3PoseDSO = r->host->PRE_camToWorld      FullSystemOptimize.cpp:485 */
+  sdso_aff_t* host_aff;          /* nf: VertexPhotometricDSO = r->host->aff_g2l()       :490-494 */
+  double cam[4];                 /* VertexCamDSO: fxl fyl cxl cyl                       :457-458 */
+  double* idepth;                /* nr: VertexInverseDepthDSO, one per RESIDUAL         :506-512 */
+} sdso_g2o_lba_state_t;
+typedef struct {
+  int max_iterations;            /* optimize(mnumOptIts): the caller applies the 10 / 7 / 3 rule of :406-418 */
+  double lambda_init;            /* setUserLambdaInit(0.1)                              :426 */
+  double gain_threshold;         /* terminateAction->setGainThreshold(1e-3)             :432 */
+  int max_trials;                /* g2o's maxTrialsAfterFailure default, 10 */
+} sdso_g2o_lba_opt_t;
+#define SDSO_G2O_LBA_MAX_RECORDED 64
+#define SDSO_G2O_LBA_STOP_ITERATIONS 0  /* the iteration cap */
+#define SDSO_G2O_LBA_STOP_GAIN 1        /* 0 <= (lastChi - chi) / chi < gain_threshold after an iteration */
+#define SDSO_G2O_LBA_STOP_TRIALS 2      /* max_trials trials in one iteration */
+#define SDSO_G2O_LBA_STOP_RHO_ZERO 3    /* a trial with rho == 0 */
+#define SDSO_G2O_LBA_STOP_LAMBDA 4      /* lambda no longer finite */
+typedef struct {
+  int iterations, stop, n_active;           /* iterations run, SDSO_G2O_LBA_STOP_*, edges with level 0 after the build-time computeError (:539) */
+  int trials[SDSO_G2O_LBA_MAX_RECORDED];    /* per iteration (the first 64 are recorded): trials, ...                          */
+  double lambda[SDSO_G2O_LBA_MAX_RECORDED]; /* ... lambda after it, ...                                                          */
+  double chi2[SDSO_G2O_LBA_MAX_RECORDED];   /* ... activeRobustChi2 of the terminate action's computeActiveErrors after it      */
+  double chi2_final;                        /* activeRobustChi2 at the returned estimates */
+  float rmse;                               /* :867: sqrtf(chi2 / (8 * nr)), nr = all edges as optimizer->edges().size(); 0 for nr = 0 */
+  /* per residual, caller-owned, from the evaluation at the returned estimates (the terminate action's is the last to run): */
+  uint8_t* state;                /* nr: state_NewState, sdso_g2o_lba_eval's convention */
+  float* energy;                 /* nr*2: state_NewEnergy, state_NewEnergyWithOutlier */
+  float* centerProjectedTo;      /* nr*3                                                                    :723 */
+  uint8_t* edge_level;           /* nr: 1 if ANY computeError of the call ran setLevel(1) on the edge (dso_g2o_edge.cpp:63: never lowered) */
+  float* idepth_hessian;         /* nr: of the LAST linearizeOplus = the start of the last iteration, what :726 reads; 0 where that one
+                                    returned early, for an inactive edge, and after zero iterations */
+  uint8_t* active;               /* nr: the edge is in g2o's active set (level 0 at initializeOptimization, :587) */
+} sdso_g2o_lba_result_t;
+/* The rules.
+ *   pair tables : R, t = (Ttw[t] * Twh[h]) rotation and translation cast to float (dso_g2o_edge.cpp:25-28); ab = fromToVecExposure(
+ *                 ab_exposure[h], ab_exposure[t], host_aff[h], target_aff[t]) cast to float (:91).  Formed on the host in double from the
+ *                 estimates before every evaluation.
+ *   active set  : fixed by the first evaluation (edge_level == 0 there); an inactive edge keeps its idepth, a host without an active
+ *                 edge keeps its pose and affine pair.  The Jacobian of an edge is zero wherever linearizeOplus returns early
+ *                 (level 1, OOB, non-finite sample: dso_g2o_edge.cpp:131, :183, :194, :204); its error is what computeError gives.
+ *   kernel      : g2o's Huber on the squared norm of the 8-vector, delta = setting_huberTH (FullSystemOptimize.cpp:529-531);
+ *                 H += J^T rho1 J, b -= rho1 J^T e.
+ *   LM          : csrc/g2o_lm.h.  lambda is added to every diagonal, the idepth ones included, BEFORE the Schur complement, and
+ *                 computeScale runs over the whole solution, idepth increments included: g2o's block solver does both.
+ *   updates     : exp(d) * Twh, a += d, b += d, idepth += d, cam += d (dso_g2o_vertex.cpp:15-18, :30-40, :56-58, :100-106).
+ *   sums        : every cross-edge sum is f64 over per-workgroup partials folded in a fixed order, no floating-point atomics: two calls
+ *                 on the same inputs agree bit for bit.
+ *   traffic     : the residual arrays go up once and the per-residual results come down once; per linearisation 8 x 91 doubles come
+ *                 down, per trial 8 x 91 + 2 doubles come down and the pair tables (<= 64 x 14 floats) and the 68 increments go up.
+ * SDSO_ERR_ARG with a message, nothing written: a null argument or array, nf outside 1..8, nr < 0, an unknown slot or one of another
+ * size than w x h, host / target out of range, a non-finite pose, affine pair, exposure, camera value, u, v or idepth,
+ * max_iterations < 0, max_trials < 1.  nr == 0 or no active edge: SDSO_OK, zero iterations, estimates untouched. */
+int sdso_g2o_lba_optimize(sdso_ctx* ctx, const sdso_g2o_lba_window_t* W, const sdso_g2o_lba_opt_t* P, sdso_g2o_lba_state_t* S,
+                          sdso_g2o_lba_result_t* out);
+
 /* ------------------------------------------------------------------ the device-resident map
  * What FullSystem::makeKeyFrame publishes through publishKeyframes (FullSystem.cpp:1467 for the whole window, FullSystemMarginalize.cpp:184
  * for a frame that leaves) and the one consumer the reference ships, KeyFrameDisplay::setFromKF / refreshPC

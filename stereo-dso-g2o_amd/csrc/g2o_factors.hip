@@ -9,6 +9,11 @@
 // version-pinned (CMakeLists.txt:47-58); it is restated from g2o's published algorithm in sdso_g2o_track_newest_coarse,
 // on the host, in double, around two kernels.  `SE3 * Vec3` is R*X + t with R = rotationMatrix() (Sophus goes through
 // Eigen's quaternion product, so3.hpp:255-257; Eigen is not in the tree either).
+//
+// One translation unit: this file (the edges, the tracker's calls, sdso_g2o_lba_eval), then
+//   g2o_lm.h          g2o's Levenberg-Marquardt control over callbacks, plain C++
+//   g2o_lba_opt.hip   sdso_g2o_lba_optimize: FullSystem::optimize as the fork compiles it (FullSystemOptimize.cpp:402-868), its kernels
+//                     over the LBA edge's pixel body below
 #include "sdso_internal.h"
 #include "host_math.h"
 #include <algorithm>
@@ -193,24 +198,26 @@ struct LbaDev {
 __constant__ int c_lba_pat[8][2] = {{0, -2}, {-1, -1}, {1, -1}, {-2, 0}, {0, 0}, {2, 0}, {-1, 1}, {0, 2}};
 
 // EdgeLBASE3PosePhotoIdepthCamDSO::computeError + linearizeOplus (dso_g2o_edge.cpp:5-282): 8 lanes per residual, lane = pattern
-// pixel; the running float sums (energy, wJI2_sum, H_idepth_idepth) are rebuilt in pattern order from the lane values.
-__global__ __launch_bounds__(256) void k_g2o_lba_eval(LbaDev L) {
-  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-  const int ri = gid >> 3, idx = gid & 7;
-  const int lane = threadIdx.x & 63, base = lane & ~7;
-  const bool live = ri < L.nr;
-  const int rr = live ? ri : 0;
-  double e = 0, X = 0, row[13];
-  float wj = 0, Ku_f = 0, Kv_f = 0, nid_f = 0;
-  bool f_neg = false, f_oob = false, f_nan = false;
+// pixel; the running float sums (energy, wJI2_sum, H_idepth_idepth) are rebuilt in pattern order from the lane values.  Stated once for
+// k_g2o_lba_eval and the window optimiser's kernels (g2o_lba_opt.hip): lba_pixel is one pattern pixel, lba_group the sequential loops'
+// control flow over the 8 lanes of a residual, lba_edge what the edge leaves behind.
+struct LbaPix {
+  double e, X, row[13];
+  float wj, Ku, Kv, nid;
+  bool f_neg, f_oob, f_nan;
+};
+// one pattern pixel of residual rr (host h, target tg) at the vertex estimate `idepth`; JAC = false leaves row[] zero
+template <bool JAC>
+__device__ __forceinline__ LbaPix lba_pixel(const LbaDev& L, int rr, int idx, int h, int tg, double idepth) {
+  LbaPix P;
+  P.e = 0; P.X = 0; P.wj = 0;
+  P.f_neg = false; P.f_oob = false; P.f_nan = false;
 #pragma unroll
-  for (int k = 0; k < 13; k++) row[k] = 0;
-  const int h = L.host[rr], tg = L.target[rr];
+  for (int k = 0; k < 13; k++) P.row[k] = 0;
   const float* R = L.pair_R + (size_t)(h * L.nf + tg) * 9;
   const float* t = L.pair_t + (size_t)(h * L.nf + tg) * 3;
   const float ab0 = L.pair_ab[(size_t)(h * L.nf + tg) * 2], ab1 = L.pair_ab[(size_t)(h * L.nf + tg) * 2 + 1];
   const double fx = L.cam[0], fy = L.cam[1], cx = L.cam[2], cy = L.cam[3];
-  const double idepth = L.idepth[rr];
   const float pu = L.u[rr], pv = L.v[rr];
   const float col = L.color[(size_t)rr * 8 + idx], wgt = L.weights[(size_t)rr * 8 + idx];
   const double u_host = pu + c_lba_pat[idx][0];
@@ -220,97 +227,135 @@ __global__ __launch_bounds__(256) void k_g2o_lba_eval(LbaDev L) {
 #pragma unroll
   for (int r = 0; r < 3; r++) ptp[r] = ((R[r * 3 + 0] * Klip0 + R[r * 3 + 1] * Klip1) + R[r * 3 + 2] * Klip2) + t[r] * (float)idepth;
   const double drescale = 1.0f / ptp[2];
-  f_neg = drescale <= 0;
+  P.f_neg = drescale <= 0;
   const double new_idepth = idepth * drescale;
   const double _u = ptp[0] * drescale, _v = ptp[1] * drescale;
   const double _Ku = _u * fx + cx, _Kv = _v * fy + cy;
-  f_oob = !f_neg && check_boundary(_Ku, _Kv, L.w - 3, L.h - 3);
-  Ku_f = (float)_Ku; Kv_f = (float)_Kv; nid_f = (float)new_idepth;
-  float3 hit = make_float3(0, 0, 0);
-  if (!f_neg && !f_oob) {
-    hit = interp33(L.img[tg], (float)_Ku, (float)_Kv, L.w);
-    if (!isfinite(hit.x)) f_nan = true;
+  P.f_oob = !P.f_neg && check_boundary(_Ku, _Kv, L.w - 3, L.h - 3);
+  P.Ku = (float)_Ku; P.Kv = (float)_Kv; P.nid = (float)new_idepth;
+  if (!P.f_neg && !P.f_oob) {
+    const float3 hit = interp33(L.img[tg], (float)_Ku, (float)_Kv, L.w);
+    if (!isfinite(hit.x)) P.f_nan = true;
     else {
-      e = hit.x - (ab0 * col + ab1);
+      const double e = hit.x - (ab0 * col + ab1);
+      P.e = e;
       float w = sqrtf(kOutlierTHSumComponent / (kOutlierTHSumComponent + (hit.y * hit.y + hit.z * hit.z)));
       w = 0.5f * (w + wgt);
       const float hw = fabsf((float)e) < kHuberTH ? 1 : kHuberTH / fabsf((float)e);
-      X = w * w * hw * e * e * (2 - hw);
-      wj = hw * hw * (hit.y * hit.y + hit.z * hit.z);
-      // linearizeOplus row
-      const double fxi = 1 / fx, fyi = 1 / fy;
-      const double p0 = hit.y, p1 = hit.z;
-      double Cm[2][4];
-      Cm[0][2] = drescale * (R[6] * _u - R[0]);
-      Cm[0][3] = fx * fyi * drescale * (R[7] * _u - R[1]);
-      Cm[0][0] = Klip0 * Cm[0][2];
-      Cm[0][1] = Klip1 * Cm[0][3];
-      Cm[1][2] = fy * fxi * drescale * (R[6] * _v - R[3]);
-      Cm[1][3] = drescale * (R[7] * _v - R[4]);
-      Cm[1][0] = Klip0 * Cm[1][2];
-      Cm[1][1] = Klip1 * Cm[1][3];
+      P.X = w * w * hw * e * e * (2 - hw);
+      P.wj = hw * hw * (hit.y * hit.y + hit.z * hit.z);
+      if constexpr (JAC) {   // linearizeOplus row
+        const double fxi = 1 / fx, fyi = 1 / fy;
+        const double p0 = hit.y, p1 = hit.z;
+        double Cm[2][4];
+        Cm[0][2] = drescale * (R[6] * _u - R[0]);
+        Cm[0][3] = fx * fyi * drescale * (R[7] * _u - R[1]);
+        Cm[0][0] = Klip0 * Cm[0][2];
+        Cm[0][1] = Klip1 * Cm[0][3];
+        Cm[1][2] = fy * fxi * drescale * (R[6] * _v - R[3]);
+        Cm[1][3] = drescale * (R[7] * _v - R[4]);
+        Cm[1][0] = Klip0 * Cm[1][2];
+        Cm[1][1] = Klip1 * Cm[1][3];
 #pragma unroll
-      for (int c = 0; c < 4; c++) row[9 + c] = p0 * Cm[0][c] + p1 * Cm[1][c];
-      const double dx = hit.y * fx, dy = hit.z * fy;
-      row[0] = new_idepth * dx;
-      row[1] = new_idepth * dy;
-      row[2] = -new_idepth * (_u * dx + _v * dy);
-      row[3] = -(_u * _v * dx + (1 + _v * _v) * dy);
-      row[4] = _u * _v * dy + (1 + _u * _u) * dx;
-      row[5] = _u * dy - _v * dx;
-      row[6] = ab0 * (L.host_b0[h] - col);
-      row[7] = -1;
-      row[8] = dx * drescale * (t[0] - t[2] * _u) + dy * drescale * (t[1] - t[2] * _v);
+        for (int c = 0; c < 4; c++) P.row[9 + c] = p0 * Cm[0][c] + p1 * Cm[1][c];
+        const double dx = hit.y * fx, dy = hit.z * fy;
+        P.row[0] = new_idepth * dx;
+        P.row[1] = new_idepth * dy;
+        P.row[2] = -new_idepth * (_u * dx + _v * dy);
+        P.row[3] = -(_u * _v * dx + (1 + _v * _v) * dy);
+        P.row[4] = _u * _v * dy + (1 + _u * _u) * dx;
+        P.row[5] = _u * dy - _v * dx;
+        P.row[6] = ab0 * (L.host_b0[h] - col);
+        P.row[7] = -1;
+        P.row[8] = dx * drescale * (t[0] - t[2] * _u) + dy * drescale * (t[1] - t[2] * _v);
+      }
     }
   }
-  // group-wide control flow of the sequential loops
-  const unsigned gm_early = (unsigned)((__ballot(f_neg || f_oob) >> base) & 0xffull);
-  const unsigned gm_neg = (unsigned)((__ballot(f_neg) >> base) & 0xffull);
-  const unsigned gm_nan = (unsigned)((__ballot(f_nan) >> base) & 0xffull);
-  const float eTH = fmaxf(L.frameEnergyTH[h], L.frameEnergyTH[tg]);
+  return P;
+}
+
+// group-wide control flow of the sequential loops; every lane of the wave calls it (ballot / shuffles), `base` = the group's first lane
+struct LbaGroup {
+  unsigned early, neg, nan;
+  float energyLeft, wJI2, Hii, c_Ku, c_Kv, c_id;
+};
+__device__ __forceinline__ LbaGroup lba_group(const LbaPix& P, int base) {
+  LbaGroup G;
+  G.early = (unsigned)((__ballot(P.f_neg || P.f_oob) >> base) & 0xffull);
+  G.neg = (unsigned)((__ballot(P.f_neg) >> base) & 0xffull);
+  G.nan = (unsigned)((__ballot(P.f_nan) >> base) & 0xffull);
   float energyLeft = 0, wJI2 = 0, Hii = 0;
 #pragma unroll
   for (int k = 0; k < 8; k++) {
-    const double Xk = __shfl(X, base + k, 64);
-    const float wk = __shfl(wj, base + k, 64);
-    const double r8 = __shfl(row[8], base + k, 64);
+    const double Xk = __shfl(P.X, base + k, 64);
+    const float wk = __shfl(P.wj, base + k, 64);
+    const double r8 = __shfl(P.row[8], base + k, 64);
     energyLeft += Xk;
     wJI2 += wk;
     Hii += r8 * r8;
   }
-  const float c_Ku = __shfl(Ku_f, base + 4, 64), c_Kv = __shfl(Kv_f, base + 4, 64), c_id = __shfl(nid_f, base + 4, 64);
+  G.energyLeft = energyLeft; G.wJI2 = wJI2; G.Hii = Hii;
+  G.c_Ku = __shfl(P.Ku, base + 4, 64); G.c_Kv = __shfl(P.Kv, base + 4, 64); G.c_id = __shfl(P.nid, base + 4, 64);
+  return G;
+}
+
+// what the edge leaves behind: state_NewState, level, the two energies, centerProjectedTo, idepth_hessian; `zero` = the error is set to
+// zero as a whole (computeError returned early), `jzero` = linearizeOplus returns early at this estimate (its Jacobians stay zero)
+struct LbaEdge {
+  uint8_t state, level;
+  float energy[2], cpt[3], ih;
+  bool zero, jzero;
+};
+__device__ __forceinline__ LbaEdge lba_edge(const LbaGroup& G, float eTH) {
+  LbaEdge E;
+  if (G.early) {
+    const int first = __ffs(G.early) - 1;
+    E.zero = true; E.jzero = true;
+    E.state = 1;
+    E.level = ((G.neg >> first) & 1u) ? 0 : 1;
+    E.energy[0] = 0; E.energy[1] = 0;
+    E.ih = 0;
+    const bool center = first > 4;
+    E.cpt[0] = center ? G.c_Ku : 2.f; E.cpt[1] = center ? G.c_Kv : 2.f; E.cpt[2] = center ? G.c_id : 0.f;
+    return E;
+  }
+  int st;
+  float eNew = G.energyLeft;
+  if (G.energyLeft > eTH || G.wJI2 < 2) { eNew = eTH; st = 2; } else st = 0;
+  const bool jearly = G.nan != 0;   // linearizeOplus returns at the first non-finite sample, leaving the Jacobians untouched (zero here)
+  E.zero = false; E.jzero = jearly;
+  E.state = jearly ? 1 : (uint8_t)st;
+  E.level = 0;
+  E.energy[0] = eNew; E.energy[1] = G.energyLeft;
+  float Hii = G.Hii;
+  if (Hii < 1e-10) Hii = 1e-10;
+  E.ih = jearly ? 0.f : Hii;
+  E.cpt[0] = G.c_Ku; E.cpt[1] = G.c_Kv; E.cpt[2] = G.c_id;
+  return E;
+}
+
+__global__ __launch_bounds__(256) void k_g2o_lba_eval(LbaDev L) {
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  const int ri = gid >> 3, idx = gid & 7;
+  const int lane = threadIdx.x & 63, base = lane & ~7;
+  const bool live = ri < L.nr;
+  const int rr = live ? ri : 0;
+  const int h = L.host[rr], tg = L.target[rr];
+  const LbaPix P = lba_pixel<true>(L, rr, idx, h, tg, L.idepth[rr]);
+  const LbaGroup G = lba_group(P, base);
   if (!live) return;
+  const LbaEdge E = lba_edge(G, fmaxf(L.frameEnergyTH[h], L.frameEnergyTH[tg]));
   double* eo = L.error + (size_t)ri * 8;
   double* Jo = L.J + (size_t)ri * 104 + idx * 13;
-  if (gm_early) {
-    const int first = __ffs(gm_early) - 1;
-    eo[idx] = 0;
+  eo[idx] = E.zero ? 0. : P.e;
 #pragma unroll
-    for (int k = 0; k < 13; k++) Jo[k] = 0;
-    if (idx == 0) {
-      L.state[ri] = 1;
-      L.edge_level[ri] = ((gm_neg >> first) & 1u) ? 0 : 1;
-      L.energy[ri * 2] = 0; L.energy[ri * 2 + 1] = 0;
-      L.idepth_hessian[ri] = 0;
-      const bool center = first > 4;
-      L.cpt[ri * 3] = center ? c_Ku : 2.f; L.cpt[ri * 3 + 1] = center ? c_Kv : 2.f; L.cpt[ri * 3 + 2] = center ? c_id : 0.f;
-    }
-    return;
-  }
-  eo[idx] = e;
-  int st;
-  float eNew = energyLeft;
-  if (energyLeft > eTH || wJI2 < 2) { eNew = eTH; st = 2; } else st = 0;
-  const bool jearly = gm_nan != 0;   // linearizeOplus returns at the first non-finite sample, leaving the Jacobians untouched (zero here)
-#pragma unroll
-  for (int k = 0; k < 13; k++) Jo[k] = jearly ? 0. : row[k];
+  for (int k = 0; k < 13; k++) Jo[k] = E.jzero ? 0. : P.row[k];
   if (idx == 0) {
-    L.state[ri] = jearly ? 1 : (uint8_t)st;
-    L.edge_level[ri] = 0;
-    L.energy[ri * 2] = eNew; L.energy[ri * 2 + 1] = energyLeft;
-    if (Hii < 1e-10) Hii = 1e-10;
-    L.idepth_hessian[ri] = jearly ? 0.f : Hii;
-    L.cpt[ri * 3] = c_Ku; L.cpt[ri * 3 + 1] = c_Kv; L.cpt[ri * 3 + 2] = c_id;
+    L.state[ri] = E.state;
+    L.edge_level[ri] = E.level;
+    L.energy[ri * 2] = E.energy[0]; L.energy[ri * 2 + 1] = E.energy[1];
+    L.idepth_hessian[ri] = E.ih;
+    L.cpt[ri * 3] = E.cpt[0]; L.cpt[ri * 3 + 1] = E.cpt[1]; L.cpt[ri * 3 + 2] = E.cpt[2];
   }
 }
 
@@ -607,3 +652,7 @@ extern "C" int sdso_g2o_lba_eval(sdso_ctx* ctx, const sdso_g2o_lba_t* Lh, double
   SDSO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SDSO_OK;
 }
+
+// FullSystem::optimize, fork-live (FullSystemOptimize.cpp:402-868): the window optimiser over the LBA edge above
+#include "g2o_lm.h"
+#include "g2o_lba_opt.hip"

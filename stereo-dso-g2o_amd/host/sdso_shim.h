@@ -34,6 +34,7 @@
 //   void CoarseInitializer::setFirstStereo(CalibHessian*, FrameHessian* newFrameHessian, FrameHessian* newFrameHessian_Right)   FullSystem/CoarseInitializer.h:108, .cpp:838-1034
 //   STEP 3 of void FullSystem::initializeFromInitializer(FrameHessian* newFrame)                                  FullSystem/FullSystem.cpp:1533-1573
 //   the swap of coarseTracker / coarseTracker_forNewKF (CoarseTracker::exportRef / adoptRef) and the frames deliverTrackedFrame queues (Device::exportFrame / importFrame)   FullSystem/FullSystem.cpp:1102-1109, :1203-1221
+//   float FullSystem::optimize(int mnumOptIts), the body the fork compiles (g2o LM over EdgeLBASE3PosePhotoIdepthCamDSO)      FullSystem/FullSystemOptimize.cpp:402-868
 #pragma once
 #include "shim/device.h"        // Error, Shared, Device.  (One part per concern; this header is the whole layer, namespace sdso_shim.)
 #include "shim/marshal.h"       // the marshalling rules the parts share, each stated once
@@ -46,3 +47,4 @@
 #include "shim/init.h"          // CoarseInitializer
 #include "shim/undistort.h"     // Undistort
 #include "shim/map.h"           // PointMap, KeyFrameDisplay
+#include "fork_live.h"          // optimizeForkLive: the fork-live FullSystem::optimize (beside the parts, see its head)

@@ -65,6 +65,12 @@ struct SE3 {                        // :42 (Sophus::SE3d): identity by default, 
     }
     return r;
   }
+  SE3 inverse() const {             // Sophus se3.hpp:169: (R^T, -R^T t)
+    SE3 r;
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) r.R(i, j) = R(j, i);
+    for (int i = 0; i < 3; i++) r.t[i] = -((r.R(i, 0) * t[0] + r.R(i, 1) * t[1]) + r.R(i, 2) * t[2]);
+    return r;
+  }
 };
 struct AffLight {                   // :152-175
   double a = 0, b = 0;
@@ -84,6 +90,8 @@ struct EFFrame; struct EFPoint; struct EFResidual;
 struct FrameFramePrecalc { Mat33f PRE_RTll; Vec2f PRE_aff_mode; Vec3f PRE_tTll; };   // :80, :85, :88
 struct CalibHessian {
   VecC value_zero, value_scaled, value, step;                       // :276-281
+  Vec_<float, 4> value_scaledf, value_scaledi;                      // :278-279 (VecCf); written by the fork-live optimize only: fxl() .. cyl() below read value_scaled
+  VecC value_minus_value_zero;                                      // :284
   CalibHessian() {}
   CalibHessian(float fx, float fy, float cx, float cy) { value_scaled[0] = fx; value_scaled[1] = fy; value_scaled[2] = cx; value_scaled[3] = cy; }   // test: floats survive the double
   void setValue(const VecC& val) {                                  // :318-333 (SCALE_F = SCALE_C = 50)
@@ -107,6 +115,7 @@ struct FrameHessian {
   std::vector<ImmaturePoint*> immaturePoints;                       // :125
   SE3 worldToCam_evalPT;                                            // :132
   Vec10 state_zero, state, step;                                    // :135-138
+  Vec10 state_scaled;                                               // :136; written by the fork-live optimize only: aff_g2l() below does not read it
   SE3 PRE_worldToCam, PRE_camToWorld;                               // :149-150
   std::vector<FrameFramePrecalc> targetPrecalc;                     // :151
   const SE3& get_worldToCam_evalPT() const { return worldToCam_evalPT; }   // :142

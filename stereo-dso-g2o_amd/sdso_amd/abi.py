@@ -296,6 +296,36 @@ class G2oLba(C.Structure):
                 ("u", c_float_p), ("v", c_float_p), ("idepth", c_double_p), ("color", c_float_p), ("weights", c_float_p)]
 
 
+class G2oLbaWindow(C.Structure):
+    """sdso_g2o_lba_window_t: the window graph of FullSystem::optimize, fork-live (FullSystemOptimize.cpp:455-542)."""
+    _fields_ = [("nf", C.c_int), ("nr", C.c_int), ("w", C.c_int), ("h", C.c_int),
+                ("frame_slot", c_int_p), ("Ttw", C.POINTER(SE3)), ("target_aff", C.POINTER(Aff)), ("ab_exposure", c_float_p),
+                ("host_b0", c_double_p), ("frameEnergyTH", c_float_p), ("host", c_int_p), ("target", c_int_p),
+                ("u", c_float_p), ("v", c_float_p), ("color", c_float_p), ("weights", c_float_p)]
+
+
+class G2oLbaState(C.Structure):
+    """sdso_g2o_lba_state_t: the vertex estimates, in and out."""
+    _fields_ = [("Twh", C.POINTER(SE3)), ("host_aff", C.POINTER(Aff)), ("cam", C.c_double * 4), ("idepth", c_double_p)]
+
+
+class G2oLbaOpt(C.Structure):
+    """sdso_g2o_lba_opt_t"""
+    _fields_ = [("max_iterations", C.c_int), ("lambda_init", C.c_double), ("gain_threshold", C.c_double), ("max_trials", C.c_int)]
+
+
+G2O_LBA_MAX_RECORDED = 64
+
+
+class G2oLbaResult(C.Structure):
+    """sdso_g2o_lba_result_t"""
+    _fields_ = [("iterations", C.c_int), ("stop", C.c_int), ("n_active", C.c_int),
+                ("trials", C.c_int * G2O_LBA_MAX_RECORDED), ("lambda_", C.c_double * G2O_LBA_MAX_RECORDED), ("chi2", C.c_double * G2O_LBA_MAX_RECORDED),
+                ("chi2_final", C.c_double), ("rmse", C.c_float),
+                ("state", c_u8_p), ("energy", c_float_p), ("centerProjectedTo", c_float_p), ("edge_level", c_u8_p),
+                ("idepth_hessian", c_float_p), ("active", c_u8_p)]
+
+
 class PoolStats(C.Structure):
     """sdso_pool_stats_t: the counters of a device buffer pool."""
     _fields_ = [(k, C.c_longlong) for k in ("hits", "misses", "frees", "host_waits", "overflow_waits", "parked_buffers", "parked_bytes")]
@@ -565,6 +595,7 @@ def load():
     L.sdso_g2o_track_linearize.argtypes = [vp, C.c_int, C.c_int, C.POINTER(G2oTrackEval), c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]
     L.sdso_g2o_track_newest_coarse.argtypes = [vp, C.c_int, C.c_int, C.POINTER(TrackParams), C.POINTER(SE3), C.POINTER(Aff), C.POINTER(TrackResult)]
     L.sdso_g2o_lba_eval.argtypes = [vp, C.POINTER(G2oLba), c_double_p, c_double_p, c_u8_p, c_float_p, c_float_p, c_float_p, c_u8_p]
+    L.sdso_g2o_lba_optimize.argtypes = [vp, C.POINTER(G2oLbaWindow), C.POINTER(G2oLbaOpt), C.POINTER(G2oLbaState), C.POINTER(G2oLbaResult)]
     L.sdso_trace_set_gn_mode.argtypes = [vp, C.c_int]
     L.sdso_distmap_make.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(DistMapGeom), C.c_int, c_int_p, c_float_p, c_float_p, c_float_p, c_int_p]
     L.sdso_distmap_make_from_window.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(DistMapGeom), c_u8_p, c_int_p]
@@ -644,7 +675,7 @@ EXPORTED_SYMBOLS = [
     "sdso_ba_window_plan", "sdso_ba_window_update", "sdso_ba_window_update_activated", "sdso_ba_window_get_order",
     "sdso_ba_batch_optimize", "sdso_ba_batch_optimize_begin", "sdso_ba_batch_step", "sdso_ba_batch_solve_step", "sdso_ba_batch_optimize_end", "sdso_ba_get_state",
     "sdso_comm_unique_id", "sdso_comm_init", "sdso_comm_init_host", "sdso_comm_attach", "sdso_comm_info", "sdso_comm_destroy", "sdso_ba_allreduce", "sdso_ba_allreduce_window",
-    "sdso_g2o_track_add_edges", "sdso_g2o_track_linearize", "sdso_g2o_track_newest_coarse", "sdso_g2o_lba_eval", "sdso_trace_set_gn_mode",
+    "sdso_g2o_track_add_edges", "sdso_g2o_track_linearize", "sdso_g2o_track_newest_coarse", "sdso_g2o_lba_eval", "sdso_g2o_lba_optimize", "sdso_trace_set_gn_mode",
     "sdso_distmap_make", "sdso_distmap_make_from_window", "sdso_distmap_add", "sdso_distmap_get", "sdso_activate_select",
     "sdso_undistort_make_remap", "sdso_ingest_calib_create", "sdso_ingest_calib_release", "sdso_ingest_frame",
     "sdso_init_set_first_stereo", "sdso_init_get_pnts", "sdso_init_from_initializer", "sdso_init_get_points", "sdso_init_release",
