@@ -12,9 +12,67 @@ import sys
 _HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(os.path.dirname(_HERE), "stereo-dso-g2o_amd"))
 from sdso_amd.abi import (G2oTrackEval, G2oLba, Activate, TraceGeom, TrackEval, SE3, Aff, TrackParams, TrackResult, BAWindow, BAOptResult, BAPostState, TracePoints,  # noqa: E402
-                          c_float_p, c_double_p, c_int_p, c_u8_p)
+                          c_float_p, c_double_p, c_int_p, c_u8_p, c_i8_p, declare)
 
 _libs = {}
+P, I, F, D, vp = C.POINTER, C.c_int, C.c_float, C.c_double, C.c_void_p
+fP, dP, iP, bP = c_float_p, c_double_p, c_int_p, c_u8_p
+# name -> argument types, or (argument types, return type) where the function does not return int; applied by sdso_amd.abi.declare
+SIGNATURES = {
+    "orc_se3_exp": ([dP, P(SE3)], None),
+    "orc_se3_log": ([P(SE3), dP], None),
+    "orc_se3_adj": ([P(SE3), dP], None),
+    "orc_se3_mul": ([P(SE3), P(SE3), P(SE3)], None),
+    "orc_se3_inv": ([P(SE3), P(SE3)], None),
+    "orc_mat3f_inv": ([fP, fP], None),
+    "orc_ldlt_solve": [I, dP, dP, dP],
+    "orc_pyramid_levels": [I, I],
+    "orc_make_images": ([fP, I, I, I, P(fP)], None),
+    "orc_track_calc_res_gs": [I, fP, fP, fP, fP, fP, P(TrackEval), dP, dP, dP, iP, bP, fP, I],
+    "orc_track_make_eval": ([P(TrackParams), I, P(SE3), P(Aff), F, P(TrackEval)], None),
+    "orc_track_newest_coarse": [iP, P(fP), P(fP), P(fP), P(fP), P(fP), P(TrackParams), P(SE3), P(Aff), P(TrackResult)],
+    "orc_make_coarse_depth": [I, iP, iP, P(fP), I, iP, iP, fP, fP, iP, P(fP), P(fP), P(fP), P(fP)],
+    "orc_ba_get_stitched": [vp] + [dP] * 6,
+    "orc_track_last_margins": ([dP], None),
+    "orc_ba_create": ([P(BAWindow)], vp),
+    "orc_ba_destroy": ([vp], None),
+    "orc_ba_set_threads": [vp, I],
+    "orc_ba_linearize": [vp, dP],
+    "orc_ba_get_linearization": [vp, fP, bP, fP, fP, fP, fP],
+    "orc_ba_apply_res": [vp],
+    "orc_ba_get_ef_jacobians": [vp, fP],
+    "orc_ba_get_residual_state": [vp, bP, bP, fP],
+    "orc_ba_accumulate": [vp],
+    "orc_ba_accum_floats": [I],
+    "orc_ba_get_accumulators": [vp, fP],
+    "orc_set_acc64": ([I], None),
+    "orc_ba_get_accumulators_f64": [vp, dP],
+    "orc_ba_get_point_terms": [vp, fP, fP, fP, fP, fP],
+    "orc_ba_solve": [vp, I, D, dP, dP, dP, dP, dP],
+    "orc_ba_get_point_steps": [vp, fP],
+    "orc_ba_optimize": [vp, I, dP, fP, bP, P(BAOptResult)],
+    "orc_ba_marginalize_points": [vp, bP, dP, dP],
+    "orc_ba_get_post_state": [vp, P(BAPostState)],
+    "orc_ba_get_x_trace": [vp, dP, I],
+    "orc_ba_get_step_trace": [vp, fP, I],
+    "orc_ba_calc_energies": [vp, dP, dP],
+    "orc_ba_get_deltas": [vp, fP, dP, dP, fP],
+    "orc_ba_get_tables": [vp, fP, dP, dP, fP],
+    "orc_immature_init_batch": [fP, I, I, I, fP, fP, fP, fP, fP, fP],
+    "orc_pixel_select": [P(fP), I, I, F, I, F, iP, fP],
+    "orc_set_gamma": ([fP], None),
+    "orc_gamma_from_binv": ([fP, fP], None),
+    "orc_selector_random_pattern": ([I, bP], None),
+    "orc_marginalize_frame": [I, I, dP, dP, dP, dP, dP, dP],
+    "orc_activate_points": [P(Activate), c_i8_p, fP, bP],
+    "orc_trace_on_batch": [fP, I, I, I, P(TraceGeom), iP, P(TracePoints), bP],
+    "orc_trace_stereo_batch": [fP, I, I, fP, F, I, P(TracePoints), bP],
+    "orc_trace_stereo_batch_gn": [fP, I, I, fP, F, I, P(TracePoints), bP, I],
+    "orc_g2o_track_add_edges": [I, fP, fP, fP, fP, fP, P(G2oTrackEval), dP, bP, fP],
+    "orc_g2o_track_linearize": [I, bP, fP, fP, fP, P(G2oTrackEval), dP, dP, dP, dP, dP],
+    "orc_g2o_track_newest_coarse": [iP, P(fP), P(fP), P(fP), P(fP), P(fP), P(TrackParams), P(SE3), P(Aff), P(TrackResult)],
+    "orc_g2o_lba_eval": [P(G2oLba), dP, dP, bP, fP, fP, fP, bP],
+}
 
 
 def build():
@@ -46,82 +104,7 @@ def load(fast=False, path=None):
     path = path or os.path.join(_HERE, name)
     if not os.path.exists(path):
         build()
-    L = C.CDLL(path)
-    vp = C.c_void_p
-    L.orc_se3_exp.argtypes = [c_double_p, C.POINTER(SE3)]
-    L.orc_se3_exp.restype = None
-    L.orc_se3_log.argtypes = [C.POINTER(SE3), c_double_p]
-    L.orc_se3_log.restype = None
-    L.orc_se3_adj.argtypes = [C.POINTER(SE3), c_double_p]
-    L.orc_se3_adj.restype = None
-    L.orc_se3_mul.argtypes = [C.POINTER(SE3), C.POINTER(SE3), C.POINTER(SE3)]
-    L.orc_se3_mul.restype = None
-    L.orc_se3_inv.argtypes = [C.POINTER(SE3), C.POINTER(SE3)]
-    L.orc_se3_inv.restype = None
-    L.orc_mat3f_inv.argtypes = [c_float_p, c_float_p]
-    L.orc_mat3f_inv.restype = None
-    L.orc_ldlt_solve.argtypes = [C.c_int, c_double_p, c_double_p, c_double_p]
-    L.orc_pyramid_levels.argtypes = [C.c_int, C.c_int]
-    L.orc_make_images.argtypes = [c_float_p, C.c_int, C.c_int, C.c_int, C.POINTER(c_float_p)]
-    L.orc_make_images.restype = None
-    L.orc_track_calc_res_gs.argtypes = [C.c_int, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, C.POINTER(TrackEval),
-                                        c_double_p, c_double_p, c_double_p, c_int_p, c_u8_p, c_float_p, C.c_int]
-    L.orc_track_make_eval.argtypes = [C.POINTER(TrackParams), C.c_int, C.POINTER(SE3), C.POINTER(Aff), C.c_float, C.POINTER(TrackEval)]
-    L.orc_track_make_eval.restype = None
-    L.orc_track_newest_coarse.argtypes = [c_int_p, C.POINTER(c_float_p), C.POINTER(c_float_p), C.POINTER(c_float_p), C.POINTER(c_float_p),
-                                          C.POINTER(c_float_p), C.POINTER(TrackParams), C.POINTER(SE3), C.POINTER(Aff), C.POINTER(TrackResult)]
-    L.orc_make_coarse_depth.argtypes = [C.c_int, c_int_p, c_int_p, C.POINTER(c_float_p), C.c_int, c_int_p, c_int_p, c_float_p, c_float_p, c_int_p,
-                                        C.POINTER(c_float_p), C.POINTER(c_float_p), C.POINTER(c_float_p), C.POINTER(c_float_p)]
-    L.orc_ba_get_stitched.argtypes = [vp] + [c_double_p] * 6
-    L.orc_track_last_margins.argtypes = [c_double_p]
-    L.orc_track_last_margins.restype = None
-    L.orc_ba_create.argtypes = [C.POINTER(BAWindow)]
-    L.orc_ba_create.restype = vp
-    L.orc_ba_destroy.argtypes = [vp]
-    L.orc_ba_destroy.restype = None
-    L.orc_ba_set_threads.argtypes = [vp, C.c_int]
-    L.orc_ba_linearize.argtypes = [vp, c_double_p]
-    L.orc_ba_get_linearization.argtypes = [vp, c_float_p, c_u8_p, c_float_p, c_float_p, c_float_p, c_float_p]
-    L.orc_ba_apply_res.argtypes = [vp]
-    L.orc_ba_get_ef_jacobians.argtypes = [vp, c_float_p]
-    L.orc_ba_get_residual_state.argtypes = [vp, c_u8_p, c_u8_p, c_float_p]
-    L.orc_ba_accumulate.argtypes = [vp]
-    L.orc_ba_accum_floats.argtypes = [C.c_int]
-    L.orc_ba_get_accumulators.argtypes = [vp, c_float_p]
-    L.orc_set_acc64.argtypes = [C.c_int]
-    L.orc_set_acc64.restype = None
-    L.orc_ba_get_accumulators_f64.argtypes = [vp, c_double_p]
-    L.orc_ba_get_point_terms.argtypes = [vp, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p]
-    L.orc_ba_solve.argtypes = [vp, C.c_int, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]
-    L.orc_ba_get_point_steps.argtypes = [vp, c_float_p]
-    L.orc_ba_optimize.argtypes = [vp, C.c_int, c_double_p, c_float_p, c_u8_p, C.POINTER(BAOptResult)]
-    L.orc_ba_marginalize_points.argtypes = [vp, c_u8_p, c_double_p, c_double_p]
-    L.orc_ba_get_post_state.argtypes = [vp, C.POINTER(BAPostState)]
-    L.orc_ba_get_x_trace.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
-    L.orc_ba_get_step_trace.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
-    L.orc_ba_calc_energies.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    L.orc_ba_get_deltas.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_float)]
-    L.orc_ba_get_tables.argtypes = [vp, c_float_p, c_double_p, c_double_p, c_float_p]
-    L.orc_immature_init_batch.argtypes = [c_float_p, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p]
-    L.orc_pixel_select.argtypes = [C.POINTER(c_float_p), C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, c_int_p, c_float_p]
-    L.orc_set_gamma.argtypes = [c_float_p]
-    L.orc_set_gamma.restype = None
-    L.orc_gamma_from_binv.argtypes = [c_float_p, c_float_p]
-    L.orc_gamma_from_binv.restype = None
-    L.orc_selector_random_pattern.argtypes = [C.c_int, c_u8_p]
-    L.orc_selector_random_pattern.restype = None
-    L.orc_marginalize_frame.argtypes = [C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]
-    L.orc_activate_points.argtypes = [C.POINTER(Activate), C.POINTER(C.c_int8), c_float_p, c_u8_p]
-    L.orc_trace_on_batch.argtypes = [c_float_p, C.c_int, C.c_int, C.c_int, C.POINTER(TraceGeom), c_int_p, C.POINTER(TracePoints), c_u8_p]
-    L.orc_trace_stereo_batch.argtypes = [c_float_p, C.c_int, C.c_int, c_float_p, C.c_float, C.c_int, C.POINTER(TracePoints), c_u8_p]
-    L.orc_trace_stereo_batch_gn.argtypes = [c_float_p, C.c_int, C.c_int, c_float_p, C.c_float, C.c_int, C.POINTER(TracePoints), c_u8_p, C.c_int]
-    L.orc_g2o_track_add_edges.argtypes = [C.c_int, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, C.POINTER(G2oTrackEval), c_double_p, c_u8_p, c_float_p]
-    L.orc_g2o_track_linearize.argtypes = [C.c_int, c_u8_p, c_float_p, c_float_p, c_float_p, C.POINTER(G2oTrackEval), c_double_p, c_double_p, c_double_p,
-                                          c_double_p, c_double_p]
-    L.orc_g2o_track_newest_coarse.argtypes = [c_int_p, C.POINTER(c_float_p), C.POINTER(c_float_p), C.POINTER(c_float_p), C.POINTER(c_float_p),
-                                              C.POINTER(c_float_p), C.POINTER(TrackParams), C.POINTER(SE3), C.POINTER(Aff), C.POINTER(TrackResult)]
-    L.orc_g2o_lba_eval.argtypes = [C.POINTER(G2oLba), c_double_p, c_double_p, c_u8_p, c_float_p, c_float_p, c_float_p, c_u8_p]
-    _libs[name] = L
+    L = _libs[name] = declare(C.CDLL(path), SIGNATURES)
     return L
 
 

@@ -69,7 +69,7 @@ def activate(orc, win, m, min_obs, min_act_dist, min_trace_quality=3.0):
         imgs = [np.ascontiguousarray(i, f32) for i in win["imgs"]]
         ptrs = (abi.c_float_p * nf)(*[abi.fp(i) for i in imgs])
         A.dI = C.cast(ptrs, C.POINTER(abi.c_float_p))
-        assert orc.orc_activate_points(C.byref(A), status.ctypes.data_as(C.POINTER(C.c_int8)), abi.fp(idepth), abi.bp(res_state)) == 0
+        assert orc.orc_activate_points(C.byref(A), abi.ptr(status), abi.fp(idepth), abi.bp(res_state)) == 0
     rec.update(status=status, idepth=idepth, res_state=res_state)
     # ---- STEP 4
     flags = (dec == D.DELETE)

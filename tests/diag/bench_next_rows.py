@@ -56,8 +56,7 @@ def main():
     K = np.array(pr["K"], np.float32); bl = float(pr["calib"]["baseline"])
     M = abi.StereoMatch(); M.n = n; M.u = abi.fp(pr["u"]); M.v = abi.fp(pr["v"])
     o = dict(status_fwd=np.zeros(n, np.uint8), status_back=np.zeros(n, np.uint8), idepth_stereo=np.zeros(n, np.float32), back_uv=np.zeros((n, 2), np.float32))
-    for k, a in o.items():
-        setattr(M, k, abi.bp(a) if a.dtype == np.uint8 else abi.fp(a))
+    abi.bind(M, o)
     g = timeit(lambda: ctx.check(ctx.L.sdso_stereo_match_batch(ctx.h, 80, 81, abi.fp(K), bl, 1, C.byref(M))), 10)
 
     def cpu_match():
@@ -94,8 +93,8 @@ def main():
     A, keep = ts._activate_struct(d, frame_slots=[60 + f for f in range(8)], dI=[p[0] for p in d["win"]["pyrs"]])
     na = A.n
     so = np.zeros(na, np.int8); io = np.zeros(na, np.float32); ro = np.zeros((na, 8), np.uint8)
-    g = timeit(lambda: ctx.check(ctx.L.sdso_activate_points_batch(ctx.h, C.byref(A), so.ctypes.data_as(C.POINTER(C.c_int8)), abi.fp(io), abi.bp(ro))), 10)
-    t0 = time.perf_counter(); orc.orc_activate_points(C.byref(A), so.ctypes.data_as(C.POINTER(C.c_int8)), abi.fp(io), abi.bp(ro)); c = (time.perf_counter() - t0) * 1e3
+    g = timeit(lambda: ctx.check(ctx.L.sdso_activate_points_batch(ctx.h, C.byref(A), abi.ptr(so), abi.fp(io), abi.bp(ro))), 10)
+    t0 = time.perf_counter(); orc.orc_activate_points(C.byref(A), abi.ptr(so), abi.fp(io), abi.bp(ro)); c = (time.perf_counter() - t0) * 1e3
     out["N3_activate_%dpts_8kf" % na] = {"gpu_ms": g, "cpu_oracle_ms": c, "activated": int((so == 1).sum())}
     # N4 pixel selector
     ctx.upload_pyramid(91, pyr)

@@ -139,7 +139,7 @@ def run_oracle(orc, case, d=None, min_obs=None):
     A, keep = TS._activate_struct(d, dI=case["imgs"][:d["nf"]], minObs=case["min_obs"] if min_obs is None else min_obs)
     n = A.n
     st, idp, rs = np.zeros(n, np.int8), np.zeros(n, f32), np.zeros((n, d["nf"]), np.uint8)
-    assert orc.orc_activate_points(C.byref(A), st.ctypes.data_as(C.POINTER(C.c_int8)), abi.fp(idp), abi.bp(rs)) == 0
+    assert orc.orc_activate_points(C.byref(A), abi.ptr(st), abi.fp(idp), abi.bp(rs)) == 0
     return st, idp, rs
 
 

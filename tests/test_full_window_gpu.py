@@ -41,7 +41,7 @@ def test_activate_points_batch_bit_exact(gpu_ctx, oracle, name):
         A, keep = TS._activate_struct(d, frame_slots=slots, dI=case["imgs"], minObs=case["min_obs"])
         n = A.n
         sg, ig, rg = np.full(n, 77, np.int8), np.full(n, -7, np.float32), np.full((n, nf), 77, np.uint8)
-        gpu_ctx.check(gpu_ctx.L.sdso_activate_points_batch(gpu_ctx.h, C.byref(A), sg.ctypes.data_as(C.POINTER(C.c_int8)), abi.fp(ig), abi.bp(rg)))
+        gpu_ctx.check(gpu_ctx.L.sdso_activate_points_batch(gpu_ctx.h, C.byref(A), abi.ptr(sg), abi.fp(ig), abi.bp(rg)))
     finally:
         for s in slots:
             gpu_ctx.L.sdso_release_pyramid(gpu_ctx.h, s)

@@ -200,14 +200,8 @@ def _lba_struct(d, frame_slots=None, dI=None):
     keep = []
     S.nf, S.nr, S.w, S.h = d["nf"], d["nr"], 640, 480
     S.cam[:] = d["cam"]
-    for k in ("pair_R", "pair_t", "pair_ab", "frameEnergyTH", "u", "v", "color", "weights"):
-        a = np.ascontiguousarray(d[k], np.float32); keep.append(a); setattr(S, k, abi.fp(a))
-    for k in ("host_b0", "idepth"):
-        a = np.ascontiguousarray(d[k], np.float64); keep.append(a); setattr(S, k, abi.dp(a))
-    for k in ("host", "target"):
-        a = np.ascontiguousarray(d[k], np.int32); keep.append(a); setattr(S, k, abi.ip(a))
-    if frame_slots is not None:
-        fs = np.ascontiguousarray(frame_slots, np.int32); keep.append(fs); S.frame_slot = abi.ip(fs)
+    arrays = {k: d[k] for k in ("pair_R", "pair_t", "pair_ab", "frameEnergyTH", "u", "v", "color", "weights", "host_b0", "idepth", "host", "target")}
+    abi.bind(S, abi.as_members(S, dict(arrays, frame_slot=frame_slots)))
     if dI is not None:
         ptrs = (abi.c_float_p * len(dI))()
         for i, a in enumerate(dI):

@@ -123,7 +123,7 @@ def _composed(ctx, win, ids, min_obs, min_act_dist, slot=SLOT):
     slots = np.arange(slot, slot + nf, dtype=np.int32)
     A.frame_slot = abi.ip(slots)
     status, idepth, res_state = np.zeros(ns, np.int8), np.zeros(ns, np.float32), np.zeros((ns, nf), np.uint8)
-    ctx.check(ctx.L.sdso_activate_points_batch(ctx.h, C.byref(A), status.ctypes.data_as(C.POINTER(C.c_int8)), abi.fp(idepth), abi.bp(res_state)))
+    ctx.check(ctx.L.sdso_activate_points_batch(ctx.h, C.byref(A), abi.ptr(status), abi.fp(idepth), abi.bp(res_state)))
     rec.update(status=status, idepth=idepth, res_state=res_state)
     flags = (dec == D.DELETE)
     flags[opt] = (status != 0) | (rec["lastTraceStatus"] == R.OOB)

@@ -49,8 +49,7 @@ def _old_entry_points(ctx, case):
     out = dict(status_fwd=np.zeros(n, np.uint8), status_back=np.zeros(n, np.uint8), idepth_stereo=np.zeros(n, np.float32), idepth_min_out=np.zeros(n, np.float32),
                idepth_max_out=np.zeros(n, np.float32), fwd_uv=np.zeros((n, 2), np.float32), back_uv=np.zeros((n, 2), np.float32))
     M.n = n; M.u = abi.fp(u); M.v = abi.fp(v)
-    for k, a in out.items():
-        setattr(M, k, abi.bp(a) if a.dtype == np.uint8 else abi.fp(a))
+    abi.bind(M, out)
     ctx.check(ctx.L.sdso_stereo_match_batch(ctx.h, SLOT_L, SLOT_R, abi.fp(case["K4"]), case["baseline"], 1, C.byref(M)))
     good = out["status_fwd"] == 0
     for k in ("idepth_stereo", "idepth_min_out", "idepth_max_out"):     # defined where the forward trace is GOOD

@@ -187,8 +187,7 @@ def test_stereo_match_at_s2(gpu_ctx, oracle):
             if imin is not None:
                 M.idepth_min_stereo = abi.fp(imin); M.idepth_max_stereo = abi.fp(imax)
                 M.back_idepth_min_stereo = abi.fp(imin); M.back_idepth_max_stereo = abi.fp(imax)
-            for k, a in out.items():
-                setattr(M, k, abi.bp(a) if a.dtype == np.uint8 else abi.fp(a))
+            abi.bind(M, out)
             gpu_ctx.check(gpu_ctx.L.sdso_stereo_match_batch(gpu_ctx.h, SLOT_L, SLOT_R, abi.fp(case["K"]), case["baseline"], 1, C.byref(M)))
             assert np.array_equal(out["status_fwd"], sf)
             assert np.array_equal(out["idepth_stereo"][good], do["idepth_stereo"][good])

@@ -156,8 +156,7 @@ def test_gpu_stereo_match_left_right_left(gpu_ctx, oracle, pair):
         if interval:
             M.idepth_min_stereo = abi.fp(imin); M.idepth_max_stereo = abi.fp(imax)
             M.back_idepth_min_stereo = abi.fp(imin); M.back_idepth_max_stereo = abi.fp(imax)
-        for k, a in out.items():
-            setattr(M, k, abi.bp(a) if a.dtype == np.uint8 else abi.fp(a))
+        abi.bind(M, out)
         gpu_ctx.check(gpu_ctx.L.sdso_stereo_match_batch(gpu_ctx.h, 80, 81, abi.fp(K), bl, 1, C.byref(M)))
         assert np.array_equal(out["status_fwd"], sf)
         assert np.array_equal(out["idepth_stereo"][good], do["idepth_stereo"][good])
@@ -277,11 +276,9 @@ def _activate_struct(d, frame_slots=None, dI=None, minObs=2):
     keep = []
     A.nf, A.w, A.h, A.n, A.minObs = d["nf"], 640, 480, len(d["u"]), minObs
     A.K[:] = [float(x) for x in d["win"]["K"]]
-    for k in ("pair_R", "pair_t", "pair_aff", "u", "v", "idepth_min", "idepth_max", "color", "weights", "energyTH"):
-        a = np.ascontiguousarray(d[k], np.float32); keep.append(a); setattr(A, k, abi.fp(a))
+    arrays = {k: d[k] for k in ("pair_R", "pair_t", "pair_aff", "u", "v", "idepth_min", "idepth_max", "color", "weights", "energyTH")}
+    abi.bind(A, abi.as_members(A, dict(arrays, frame_slot=frame_slots)))
     A.host = abi.ip(d["host"])
-    if frame_slots is not None:
-        fs = np.ascontiguousarray(frame_slots, np.int32); keep.append(fs); A.frame_slot = abi.ip(fs)
     if dI is not None:
         ptrs = (abi.c_float_p * len(dI))()
         for i, a in enumerate(dI):
@@ -295,7 +292,7 @@ def test_oracle_activation_converges_to_true_idepth(oracle):
     A, keep = _activate_struct(d, dI=[p[0] for p in d["win"]["pyrs"]])
     n = A.n
     st = np.zeros(n, np.int8); idp = np.zeros(n, np.float32); rs_ = np.zeros((n, d["nf"]), np.uint8)
-    assert oracle.orc_activate_points(C.byref(A), st.ctypes.data_as(C.POINTER(C.c_int8)), abi.fp(idp), abi.bp(rs_)) == 0
+    assert oracle.orc_activate_points(C.byref(A), abi.ptr(st), abi.fp(idp), abi.bp(rs_)) == 0
     act = st == 1
     assert act.mean() > 0.5 and (st == -1).sum() > 0                      # most points activate, some are rejected
     rel = np.abs(idp[act] - d["truth"][act]) / d["truth"][act]
@@ -315,8 +312,8 @@ def test_gpu_activation_bit_exact(gpu_ctx, oracle):
     n = A.n
     so = np.zeros(n, np.int8); io = np.zeros(n, np.float32); ro = np.zeros((n, nf), np.uint8)
     sg = np.zeros(n, np.int8); ig = np.zeros(n, np.float32); rg = np.zeros((n, nf), np.uint8)
-    assert oracle.orc_activate_points(C.byref(A), so.ctypes.data_as(C.POINTER(C.c_int8)), abi.fp(io), abi.bp(ro)) == 0
-    gpu_ctx.check(gpu_ctx.L.sdso_activate_points_batch(gpu_ctx.h, C.byref(A), sg.ctypes.data_as(C.POINTER(C.c_int8)), abi.fp(ig), abi.bp(rg)))
+    assert oracle.orc_activate_points(C.byref(A), abi.ptr(so), abi.fp(io), abi.bp(ro)) == 0
+    gpu_ctx.check(gpu_ctx.L.sdso_activate_points_batch(gpu_ctx.h, C.byref(A), abi.ptr(sg), abi.fp(ig), abi.bp(rg)))
     assert np.array_equal(so, sg) and np.array_equal(ro, rg)
     assert np.array_equal(io, ig, equal_nan=True)                          # same float operations in the same order: bit-exact
     assert set(np.unique(so)) == {-1, 0, 1}
@@ -349,8 +346,7 @@ def test_stereo_refusals(gpu_ctx, pair):
                    idepth_min_out=np.zeros(m, np.float32), idepth_max_out=np.zeros(m, np.float32), fwd_uv=np.zeros((m, 2), np.float32),
                    back_uv=np.zeros((m, 2), np.float32))
         M.n = m; M.u = abi.fp(uu); M.v = abi.fp(vv)
-        for k, a in out.items():
-            setattr(M, k, abi.bp(a) if a.dtype == np.uint8 else abi.fp(a))
+        abi.bind(M, out)
         return L.sdso_stereo_match_batch(h, sa, sb, abi.fp(K), bl, 1, C.byref(M)), out
 
     def correct():
@@ -384,10 +380,9 @@ def test_stereo_refusals(gpu_ctx, pair):
         A = abi.Activate()
         A.nf, A.w, A.h, A.n, A.minObs = nf, pr["w"], pr["h"], 1, 1
         A.K[:] = [float(x) for x in pr["K"]]
-        for k, a in one.items():
-            setattr(A, k, abi.fp(a))
+        abi.bind(A, one)
         fs = np.array(slots, np.int32); A.host = abi.ip(host0); A.frame_slot = abi.ip(fs)
-        assert L.sdso_activate_points_batch(h, C.byref(A), a_st.ctypes.data_as(C.POINTER(C.c_int8)), abi.fp(a_id), abi.bp(a_rs)) == ERR_ARG, slots
+        assert L.sdso_activate_points_batch(h, C.byref(A), abi.ptr(a_st), abi.fp(a_id), abi.bp(a_rs)) == ERR_ARG, slots
     sel_map = np.zeros((pr["h"], pr["w"]), np.float32)
     assert L.sdso_imm_add_frame(h, 7001, NONE, abi.fp(sel_map), None) == ERR_ARG
     Ki = np.eye(3, dtype=np.float32).ravel().copy()

@@ -66,8 +66,7 @@ def _match_batch(ctx, c):
                idepth_max_out=np.zeros(n, f32), fwd_uv=np.zeros((n, 2), f32), back_uv=np.zeros((n, 2), f32))
     Mb = abi.StereoMatch()
     Mb.n = n; Mb.u = abi.fp(u); Mb.v = abi.fp(v)
-    for k, a in out.items():
-        setattr(Mb, k, abi.bp(a) if a.dtype == np.uint8 else abi.fp(a))
+    abi.bind(Mb, out)
     ctx.check(ctx.L.sdso_stereo_match_batch(ctx.h, SLOT_L, SLOT_R, abi.fp(c["K4"]), c["baseline"], 1, C.byref(Mb)))
     good = out["status_fwd"] == 0
     for k in ("idepth_stereo", "idepth_min_out", "idepth_max_out"):     # defined where the forward trace is GOOD

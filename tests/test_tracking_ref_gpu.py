@@ -213,8 +213,7 @@ def device_match(c, pr, mode_first, u, v, imin, imax):
     if imin is not None:
         M.idepth_min_stereo = abi.fp(imin); M.idepth_max_stereo = abi.fp(imax)
         M.back_idepth_min_stereo = abi.fp(imin); M.back_idepth_max_stereo = abi.fp(imax)
-    for k, a in out.items():
-        setattr(M, k, abi.bp(a) if a.dtype == np.uint8 else abi.fp(a))
+    abi.bind(M, out)
     slots = (LEFT, RIGHT) if mode_first else (RIGHT, LEFT)
     c.check(c.L.sdso_stereo_match_batch(c.h, slots[0], slots[1], abi.fp(pr["K32"]), pr["bl"], mode_first, C.byref(M)))
     return out

@@ -138,7 +138,7 @@ def call_a():
         hs = np.ascontiguousarray(rec["frame"], np.int32)
         A.host = abi.ip(hs)
         A.frame_slot = abi.ip(SLOTS_A)
-        ctx.check(L.sdso_activate_points_batch(ctx.h, C.byref(A), status.ctypes.data_as(C.POINTER(C.c_int8)), abi.fp(idepth), abi.bp(res_state)))
+        ctx.check(L.sdso_activate_points_batch(ctx.h, C.byref(A), abi.ptr(status), abi.fp(idepth), abi.bp(res_state)))
     rec.update(status=status, idepth=idepth, res_state=res_state)
     flags = dec == 1
     flags[opt] = (status != 0) | (rec["lastTraceStatus"] == 1)

@@ -62,8 +62,7 @@ post = dict(idepth=np.zeros(npts, np.float32), step=np.zeros(npts, np.float32), 
             idepth_hessian=np.zeros(npts, np.float32), maxRelBaseline=np.zeros(npts, np.float32), numGoodResiduals=np.zeros(npts, np.int32),
             state_state=np.zeros(nr, np.uint8), toRemove=np.zeros(nr, np.uint8))
 P = abi.BAPostState()
-for k, a in post.items():
-    setattr(P, k, {np.dtype(np.float32): abi.fp, np.dtype(np.int32): abi.ip, np.dtype(np.uint8): abi.bp}[a.dtype](a))
+abi.bind(P, post)
 split = []
 
 

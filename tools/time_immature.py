@@ -102,8 +102,7 @@ def frame_a(S, k):
         o = dict(status_fwd=np.zeros(n, np.uint8), idepth_min_out=np.zeros(n, f32), idepth_max_out=np.zeros(n, f32), fwd_uv=np.zeros((n, 2), f32), back_uv=np.zeros((n, 2), f32))
         M.n = n; M.u = abi.fp(fu); M.v = abi.fp(fv)
         M.idepth_min_stereo = abi.fp(pmin); M.idepth_max_stereo = abi.fp(pmax); M.back_idepth_min_stereo = abi.fp(pmin); M.back_idepth_max_stereo = abi.fp(pmax)
-        for key, arr in o.items():
-            setattr(M, key, abi.bp(arr) if arr.dtype == np.uint8 else abi.fp(arr))
+        abi.bind(M, o)
         ctx.check(L.sdso_stereo_match_batch(ctx.h, 30 + 2 * k, 31 + 2 * k, abi.fp(K4), BL, 1, C.byref(M)))
         b = np.nonzero(o["status_fwd"] == 0)[0]
         with np.errstate(all="ignore"):

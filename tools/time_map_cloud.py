@@ -87,8 +87,7 @@ cap = 8 * total
 post = dict(idepth=np.zeros(npts, np.float32), step=np.zeros(npts, np.float32), HdiF=np.zeros(npts, np.float32), bdSumF=np.zeros(npts, np.float32),
             idepth_hessian=np.zeros(npts, np.float32), maxRelBaseline=np.zeros(npts, np.float32), numGoodResiduals=np.zeros(npts, np.int32))
 P = abi.BAPostState()
-for k, a in post.items():
-    setattr(P, k, {np.dtype(np.float32): abi.fp, np.dtype(np.int32): abi.ip}[a.dtype](a))
+abi.bind(P, post)
 a_rec = [np.concatenate([f["lists"][l] for l in (1, 2, 3)]) for f in frames]               # (the active part is rewritten per call)
 a_status = [np.concatenate([np.full(len(f["lists"][l]), l, np.uint8) for l in (1, 2, 3)]) for f in frames]
 a_xyz, a_rgb, a_first = np.zeros((cap, 3), np.float32), np.zeros((cap, 3), np.uint8), np.zeros(nf + 1, np.int32)

@@ -68,8 +68,7 @@ def route_a():
     t1 = time.perf_counter()
     Mb = abi.StereoMatch()
     Mb.n = n; Mb.u = abi.fp(S["u"]); Mb.v = abi.fp(S["v"])
-    for k, a in mo.items():
-        setattr(Mb, k, abi.bp(a) if a.dtype == np.uint8 else abi.fp(a))
+    abi.bind(Mb, mo)
     ctx.check(L.sdso_stereo_match_batch(ctx.h, SLOT_L, SLOT_R, abi.fp(K4), baseline, 1, C.byref(Mb)))
     t2 = time.perf_counter()
     with np.errstate(all="ignore"):
