@@ -1338,6 +1338,29 @@ int sdso_g2o_track_linearize(sdso_ctx* ctx, int ref_slot, int frame_slot, const 
  * as sdso_track_newest_coarse; prm->maxIterations is ignored (the fork hard-codes {2,2,2,2,2}, :861). */
 int sdso_g2o_track_newest_coarse(sdso_ctx* ctx, int ref_slot, int frame_slot, const sdso_track_params_t* prm,
                                  sdso_se3_t* lastToNew, sdso_aff_t* aff_g2l, sdso_track_result_t* out);
+/* The same for `nhyp` independent (reference, frame, initial pose) tries, device-resident: ONE launch, one workgroup per try, every
+ * calcRes, linearisation and Levenberg-Marquardt decision of CoarseTracker.cpp:827-1069 inside it (the single call above pays a launch
+ * and a stream wait per evaluation and stays as the A/B).  Same shape and in/out convention as sdso_track_newest_coarse_batch;
+ * prms[k].maxIterations is ignored (:861).  A try that aborts (:1032) leaves its lastToNew / aff_g2l entries untouched; one that reaches
+ * :1044-1045 has written them, whatever STEP4 (:1050-1068) then returns — as the single call.  A try's numbers do not depend on nhyp or on
+ * its place in the batch, and a repeated call gives the same bytes; they agree with the single call's to the order of its sums (not bit for
+ * bit), the flow indicators bit for bit.  The edge sets of sdso_g2o_track_add_edges are neither read nor written.  "Parity unpinned" for
+ * everything g2o decides, as above.
+ * Refusals (SDSO_ERR_ARG, before any device work, nothing written): a null argument, nhyp < 1, coarsestLvl out of range, an unknown slot,
+ * a frame without a level the try walks, a level size other than the uploaded one. */
+int sdso_g2o_track_newest_coarse_batch(sdso_ctx* ctx, int nhyp, const int* ref_slots, const int* frame_slots,
+                                       const sdso_track_params_t* prms, sdso_se3_t* lastToNew, sdso_aff_t* aff_g2l,
+                                       sdso_track_result_t* outs);
+/* FullSystem::trackNewCoarse STEP2-4 (FullSystem.cpp:436-511) with the fork-live trackNewestCoarse inside the loop: sdso_track_new_coarse
+ * with the runner swapped — its signature, its records (sdso_track_try_t), its refusals and its two phases.  Phase 1 is try 0 alone (a
+ * batch of one under NaN bounds), then the loop's rules; where the loop stops there the call returns.  Phase 2 runs tries 1..ntries-1 in
+ * ONE launch of sdso_g2o_track_newest_coarse_batch under achievedRes as try 0 left it, and the rules walk the event traces in list order.
+ * The fork-live body never repeats a level (levelCutoffRepeat stays 1, CoarseTracker.cpp:891-904): a trace has at most five events, and a
+ * try's evaluations do not depend on minResForAbort until the test of :1032 fires, so the two facts above sdso_track_trace_t hold as they
+ * stand.  Tries after the stop are reported with ran = 0.  prm->minResForAbort and prm->maxIterations are ignored. */
+int sdso_g2o_track_new_coarse(sdso_ctx* ctx, int ref_slot, int frame_slot, const sdso_track_params_t* prm, int ntries,
+                              const sdso_se3_t* tries, const sdso_aff_t* aff_last_2_l, double* lastCoarseRMSE, double reTrackThreshold,
+                              sdso_track_tries_result_t* out, sdso_track_try_t* recs);
 
 /* B13: EdgeLBASE3PosePhotoIdepthCamDSO (dso_g2o_edge.cpp:5-282) for the nr active residuals of a window, laid out as
  * FullSystem::optimize builds the graph (FullSystemOptimize.cpp:455-542): one pose + one photometric vertex per HOST frame,

@@ -12,6 +12,9 @@
 //
 // One translation unit: this file (the edges, the tracker's calls, sdso_g2o_lba_eval), then
 //   g2o_lm.h          g2o's Levenberg-Marquardt control over callbacks, plain C++
+//   g2o_track_core.h  one try of the fork-live trackNewestCoarse as a state machine over its evaluations, plain C++ for host and device
+//   g2o_track_lm.hip  k_g2o_track_lm: that state machine resident on the device, one workgroup per try; sdso_g2o_track_newest_coarse_batch,
+//                     sdso_g2o_track_new_coarse
 //   g2o_lba_opt.hip   sdso_g2o_lba_optimize: FullSystem::optimize as the fork compiles it (FullSystemOptimize.cpp:402-868), its kernels
 //                     over the LBA edge's pixel body below
 #include "sdso_internal.h"
@@ -33,6 +36,11 @@ struct G2oState {
   DevBuf<double> d_part;                             // per-block partial systems
   DevBuf<int> d_cnt;                                 // {numTermsInE, numSaturated}
   DevBuf<float> d_flow;                              // 4 floats per 32nd level-0 point
+  // k_g2o_track_lm (g2o_track_lm.hip): the jobs of a batch on both sides, and per try its private edge mask and flow terms
+  PinBuf<void> lm_jobs_host;
+  DevBuf<void> lm_jobs;
+  DevBuf<uint8_t> lm_mask;
+  DevBuf<float> lm_flow;
 };
 void release_g2o(sdso_ctx* ctx) {
   delete ctx->g2o;
@@ -89,52 +97,72 @@ __device__ __forceinline__ TrackEdgeVal track_edge(const float4 xr, const float4
   return r;
 }
 
-// CoarseTracker::calcRes, fork-live body (CoarseTracker.cpp:600-792): one pc point per lane.
+// CoarseTracker::calcRes, fork-live body (CoarseTracker.cpp:600-792) for one pc point, stated once for k_g2o_track_edges and k_g2o_track_lm
+// (g2o_track_lm.hip): the border cull, the edge's Xref, its first evaluation and the saturation test.  Returns the edge mask; xr = {Xref,
+// measurement} (Xref zero without an edge); sat = 1: the edge was dropped as saturated; flow != null: the four flow terms of a 32nd
+// level-0 point go to flow[0..3] (:662-693, summed by the caller in point order).
+__device__ __forceinline__ uint8_t track_cull(const float4 p, const float4* __restrict__ img, const sdso_g2o_track_eval_t& ev, float4& xr, int& sat,
+                                              float* __restrict__ flow) {
+  const float x = p.x, y = p.y, id = p.z;
+  float pt[3], kp[3];
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    kp[r] = (ev.Ki[r * 3 + 0] * x + ev.Ki[r * 3 + 1] * y) + ev.Ki[r * 3 + 2] * 1.0f;
+    pt[r] = ((ev.RKi[r * 3 + 0] * x + ev.RKi[r * 3 + 1] * y) + ev.RKi[r * 3 + 2] * 1.0f) + ev.t_cull[r] * id;
+  }
+  const float u = pt[0] / pt[2], v = pt[1] / pt[2];
+  const float Ku = ev.fx * u + ev.cx, Kv = ev.fy * v + ev.cy;
+  const float new_idepth = id / pt[2];
+  if (flow) {
+    float ptT[3], ptT2[3], pt3[3];
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      const float rp = (ev.RKi[r * 3 + 0] * x + ev.RKi[r * 3 + 1] * y) + ev.RKi[r * 3 + 2] * 1.0f;
+      ptT[r] = kp[r] + ev.t_cull[r] * id;
+      ptT2[r] = kp[r] - ev.t_cull[r] * id;
+      pt3[r] = rp - ev.t_cull[r] * id;
+    }
+    const float KuT = ev.fx * (ptT[0] / ptT[2]) + ev.cx, KvT = ev.fy * (ptT[1] / ptT[2]) + ev.cy;
+    const float KuT2 = ev.fx * (ptT2[0] / ptT2[2]) + ev.cx, KvT2 = ev.fy * (ptT2[1] / ptT2[2]) + ev.cy;
+    const float Ku3 = ev.fx * (pt3[0] / pt3[2]) + ev.cx, Kv3 = ev.fy * (pt3[1] / pt3[2]) + ev.cy;
+    flow[0] = (KuT - x) * (KuT - x) + (KvT - y) * (KvT - y);
+    flow[1] = (KuT2 - x) * (KuT2 - x) + (KvT2 - y) * (KvT2 - y);
+    flow[2] = (Ku - x) * (Ku - x) + (Kv - y) * (Kv - y);
+    flow[3] = (Ku3 - x) * (Ku3 - x) + (Kv3 - y) * (Kv3 - y);
+  }
+  uint8_t m = 0;
+  sat = 0;
+  xr = make_float4(0, 0, 0, p.w);
+  if (Ku > 2 && Kv > 2 && Ku < ev.w - 3 && Kv < ev.h - 3 && new_idepth > 0) {   // :696
+    xr.x = kp[0] / id; xr.y = kp[1] / id; xr.z = kp[2] / id;                     // :707
+    const TrackEdgeVal e1 = track_edge<false>(xr, img, ev);                      // :721
+    if (e1.e > ev.cutoffTH * 10) sat = 1;                                        // :724-727
+    else m = 1;
+  }
+  if (!m) xr = make_float4(0, 0, 0, p.w);
+  return m;
+}
+// the Xref of an edge once more (:707), for a caller that keeps the mask alone
+__device__ __forceinline__ float4 track_xref(const float4 p, const sdso_g2o_track_eval_t& ev) {
+  const float x = p.x, y = p.y, id = p.z;
+  float kp[3];
+#pragma unroll
+  for (int r = 0; r < 3; r++) kp[r] = (ev.Ki[r * 3 + 0] * x + ev.Ki[r * 3 + 1] * y) + ev.Ki[r * 3 + 2] * 1.0f;
+  return make_float4(kp[0] / id, kp[1] / id, kp[2] / id, p.w);
+}
+
+// one pc point per lane
 __global__ __launch_bounds__(256) void k_g2o_track_edges(int n, const float4* __restrict__ pc, const float4* __restrict__ img, sdso_g2o_track_eval_t ev,
                                                          uint8_t* __restrict__ mask, float4* __restrict__ xref, int* __restrict__ cnt,
                                                          float* __restrict__ flow) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   int term = 0, sat = 0;
   if (i < n) {
-    const float4 p = pc[i];
-    const float x = p.x, y = p.y, id = p.z;
-    float pt[3], kp[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-      kp[r] = (ev.Ki[r * 3 + 0] * x + ev.Ki[r * 3 + 1] * y) + ev.Ki[r * 3 + 2] * 1.0f;
-      pt[r] = ((ev.RKi[r * 3 + 0] * x + ev.RKi[r * 3 + 1] * y) + ev.RKi[r * 3 + 2] * 1.0f) + ev.t_cull[r] * id;
-    }
-    const float u = pt[0] / pt[2], v = pt[1] / pt[2];
-    const float Ku = ev.fx * u + ev.cx, Kv = ev.fy * v + ev.cy;
-    const float new_idepth = id / pt[2];
-    if (ev.lvl == 0 && i % 32 == 0) {   // :662-693, summed on the host in point order
-      float ptT[3], ptT2[3], pt3[3];
-#pragma unroll
-      for (int r = 0; r < 3; r++) {
-        const float rp = (ev.RKi[r * 3 + 0] * x + ev.RKi[r * 3 + 1] * y) + ev.RKi[r * 3 + 2] * 1.0f;
-        ptT[r] = kp[r] + ev.t_cull[r] * id;
-        ptT2[r] = kp[r] - ev.t_cull[r] * id;
-        pt3[r] = rp - ev.t_cull[r] * id;
-      }
-      const float KuT = ev.fx * (ptT[0] / ptT[2]) + ev.cx, KvT = ev.fy * (ptT[1] / ptT[2]) + ev.cy;
-      const float KuT2 = ev.fx * (ptT2[0] / ptT2[2]) + ev.cx, KvT2 = ev.fy * (ptT2[1] / ptT2[2]) + ev.cy;
-      const float Ku3 = ev.fx * (pt3[0] / pt3[2]) + ev.cx, Kv3 = ev.fy * (pt3[1] / pt3[2]) + ev.cy;
-      float* f = flow + (size_t)(i / 32) * 4;
-      f[0] = (KuT - x) * (KuT - x) + (KvT - y) * (KvT - y);
-      f[1] = (KuT2 - x) * (KuT2 - x) + (KvT2 - y) * (KvT2 - y);
-      f[2] = (Ku - x) * (Ku - x) + (Kv - y) * (Kv - y);
-      f[3] = (Ku3 - x) * (Ku3 - x) + (Kv3 - y) * (Kv3 - y);
-    }
-    uint8_t m = 0;
-    float4 xr = make_float4(0, 0, 0, p.w);
-    if (Ku > 2 && Kv > 2 && Ku < ev.w - 3 && Kv < ev.h - 3 && new_idepth > 0) {   // :696
-      xr.x = kp[0] / id; xr.y = kp[1] / id; xr.z = kp[2] / id;                     // :707
-      const TrackEdgeVal e1 = track_edge<false>(xr, img, ev);                      // :721
-      if (e1.e > ev.cutoffTH * 10) sat = 1;                                        // :724-727
-      else { m = 1; term = 1; }
-    }
+    float4 xr;
+    const uint8_t m = track_cull(pc[i], img, ev, xr, sat, ev.lvl == 0 && i % 32 == 0 ? flow + (size_t)(i / 32) * 4 : nullptr);
+    term = m;
     mask[i] = m;
-    xref[i] = m ? xr : make_float4(0, 0, 0, p.w);
+    xref[i] = xr;
   }
   const unsigned long long bt = __ballot(term), bs = __ballot(sat);
   if ((threadIdx.x & 63) == 0) {
@@ -143,9 +171,26 @@ __global__ __launch_bounds__(256) void k_g2o_track_edges(int n, const float4* __
   }
 }
 
-// computeActiveErrors + linearizeOplus + constructQuadraticForm (g2o: H += J^T rho1 J, b -= rho1 J^T e with the Huber
-// kernel of delta huberTH) over the edge set; one edge per lane and trip, 46 double sums per lane, wave butterfly,
-// per-block partial written to part[block][46].  err / J (optional) are indexed like the pc arrays.
+// g2o's robustified quadratic form of one edge into a lane's 46 sums: H += J^T rho1 J, b -= rho1 J^T e with the Huber kernel of delta
+// huberTH; [44] += e^2, [45] += rho0 (activeRobustChi2)
+__device__ __forceinline__ void track_lin_add(const TrackEdgeVal& v, double delta, double* acc) {
+  const double e2 = v.e * v.e, dsqr = delta * delta;
+  double rho0, rho1;
+  if (e2 <= dsqr) { rho0 = e2; rho1 = 1.; }
+  else { const double sqrte = sqrt(e2); rho0 = 2 * sqrte * delta - dsqr; rho1 = delta / sqrte; }
+  int k = 0;
+#pragma unroll
+  for (int r = 0; r < 8; r++)
+#pragma unroll
+    for (int c = r; c < 8; c++) acc[k++] += v.J[r] * rho1 * v.J[c];
+#pragma unroll
+  for (int r = 0; r < 8; r++) acc[36 + r] -= rho1 * v.J[r] * v.e;
+  acc[44] += e2;
+  acc[45] += rho0;
+}
+
+// computeActiveErrors + linearizeOplus + constructQuadraticForm over the edge set; one edge per lane and trip, 46 double sums per lane,
+// wave butterfly, per-block partial written to part[block][46].  err / J (optional) are indexed like the pc arrays.
 __global__ __launch_bounds__(256) void k_g2o_track_lin(int n, const uint8_t* __restrict__ mask, const float4* __restrict__ xref,
                                                        const float4* __restrict__ img, sdso_g2o_track_eval_t ev, double* __restrict__ part,
                                                        double* __restrict__ err, double* __restrict__ Jout) {
@@ -160,19 +205,7 @@ __global__ __launch_bounds__(256) void k_g2o_track_lin(int n, const uint8_t* __r
     if (err) err[i] = v.e;
     if (Jout) { for (int k = 0; k < 8; k++) Jout[(size_t)i * 8 + k] = v.J[k]; }
     if (!on) continue;
-    const double e2 = v.e * v.e, delta = ev.huberTH, dsqr = delta * delta;
-    double rho0, rho1;
-    if (e2 <= dsqr) { rho0 = e2; rho1 = 1.; }
-    else { const double sqrte = sqrt(e2); rho0 = 2 * sqrte * delta - dsqr; rho1 = delta / sqrte; }
-    int k = 0;
-#pragma unroll
-    for (int r = 0; r < 8; r++)
-#pragma unroll
-      for (int c = r; c < 8; c++) acc[k++] += v.J[r] * rho1 * v.J[c];
-#pragma unroll
-    for (int r = 0; r < 8; r++) acc[36 + r] -= rho1 * v.J[r] * v.e;
-    acc[44] += e2;
-    acc[45] += rho0;
+    track_lin_add(v, ev.huberTH, acc);
   }
   __shared__ double sm[4][kSysDoubles];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -656,3 +689,6 @@ extern "C" int sdso_g2o_lba_eval(sdso_ctx* ctx, const sdso_g2o_lba_t* Lh, double
 // FullSystem::optimize, fork-live (FullSystemOptimize.cpp:402-868): the window optimiser over the LBA edge above
 #include "g2o_lm.h"
 #include "g2o_lba_opt.hip"
+// CoarseTracker::trackNewestCoarse and FullSystem::trackNewCoarse, fork-live, resident on the device
+#include "g2o_track_core.h"
+#include "g2o_track_lm.hip"

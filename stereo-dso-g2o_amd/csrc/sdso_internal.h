@@ -309,6 +309,14 @@ inline int track_coarsest_level_ok(sdso_ctx* ctx, const sdso_track_params_t& p) 
   SDSO_REQUIRE(ctx, p.coarsestLvl >= 0 && p.coarsestLvl < 5 && p.coarsestLvl < p.levels, "coarsestLvl out of range");
   return SDSO_OK;
 }
+// FullSystem::trackNewCoarse STEP2-4 (tracker_tries.hip) over the runner of a batch of tries: `runner` has track_newest_coarse_run's
+// contract (tracker_lm_api.hip) — nhyp tries in one launch, in/out poses and affine pairs, results, event traces.  sdso_track_new_coarse
+// passes the DSO-native runner, sdso_g2o_track_new_coarse (g2o_track_lm.hip) the fork-live one; refusals, records and phases are one text.
+typedef int (*TrackBatchRunner)(sdso_ctx* ctx, int nhyp, const int* ref_slots, const int* frame_slots, const sdso_track_params_t* prms,
+                                sdso_se3_t* lastToNew, sdso_aff_t* aff_g2l, sdso_track_result_t* outs, sdso_track_trace_t* traces);
+int track_new_coarse_with(sdso_ctx* ctx, int ref_slot, int frame_slot, const sdso_track_params_t* prm, int ntries, const sdso_se3_t* tries,
+                          const sdso_aff_t* aff_last_2_l, double* lastCoarseRMSE, double reTrackThreshold, sdso_track_tries_result_t* out,
+                          sdso_track_try_t* recs, TrackBatchRunner runner);
 // Bracket the launches of one named kernel with HIP events when profiling is enabled.
 // The A/B and diagnostic switches of the library (SDSO_BA_*, SDSO_TRK_*, SDSO_OPT_*, SDSO_PROF_BRACKET) exist only under SDSO_DEBUG_ENV=1,
 // which is read ONCE per process: without it no environment variable changes what the library computes or launches, and no call reads

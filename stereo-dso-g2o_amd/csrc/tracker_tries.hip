@@ -1,5 +1,6 @@
 // FullSystem::trackNewCoarse STEP2-4 through the C-ABI: the ctx-free replay of the loop's rules and sdso_track_new_coarse (part of tracker.hip).
 // The rules are track_tries.h; the tries run through track_newest_coarse_run (tracker_lm_api.hip), which hands back their event traces.
+// The driver is stated once, over the runner of a batch: sdso_g2o_track_new_coarse (g2o_track_lm.hip) walks it with the fork-live runner.
 #include "track_tries.h"
 #include <vector>
 
@@ -12,9 +13,9 @@ extern "C" int sdso_track_tries_replay(int ntries, const sdso_se3_t* tries, cons
   return SDSO_OK;
 }
 
-extern "C" int sdso_track_new_coarse(sdso_ctx* ctx, int ref_slot, int frame_slot, const sdso_track_params_t* prm, int ntries,
-                                     const sdso_se3_t* tries, const sdso_aff_t* aff_last_2_l, double* lastCoarseRMSE, double reTrackThreshold,
-                                     sdso_track_tries_result_t* out, sdso_track_try_t* recs) {
+int sdso::track_new_coarse_with(sdso_ctx* ctx, int ref_slot, int frame_slot, const sdso_track_params_t* prm, int ntries, const sdso_se3_t* tries,
+                                const sdso_aff_t* aff_last_2_l, double* lastCoarseRMSE, double reTrackThreshold, sdso_track_tries_result_t* out,
+                                sdso_track_try_t* recs, TrackBatchRunner runner) {
   if (!ctx) return SDSO_ERR_STATE;
   // ---- refusals: before any device work, nothing written
   SDSO_REQUIRE(ctx, prm && tries && aff_last_2_l && lastCoarseRMSE && out, "null argument");
@@ -38,7 +39,7 @@ extern "C" int sdso_track_new_coarse(sdso_ctx* ctx, int ref_slot, int frame_slot
     std::vector<sdso_track_result_t> outs(n);
     std::vector<sdso_track_trace_t> traces(n);
     for (int k = 0; k < n; k++) for (int l = 0; l < 5; l++) prms[k].minResForAbort[l] = S.achievedRes[l];
-    SDSO_TRY(track_newest_coarse_run(ctx, n, refs.data(), frames.data(), prms.data(), T.data(), aff.data(), outs.data(), traces.data()));
+    SDSO_TRY(runner(ctx, n, refs.data(), frames.data(), prms.data(), T.data(), aff.data(), outs.data(), traces.data()));
     for (int k = 0; k < n; k++) {
       sdso_track_try_t& r = recs[i0 + k];
       r.trace.n = traces[k].n;                               // (member by member into the zeroed record: its bytes are a function of the events alone)
@@ -50,7 +51,7 @@ extern "C" int sdso_track_new_coarse(sdso_ctx* ctx, int ref_slot, int frame_slot
     }
     return SDSO_OK;
   };
-  // ---- phase 1: try 0 alone, the launch of sdso_track_newest_coarse with NaN bounds; nearly every frame ends here (:499-500)
+  // ---- phase 1: try 0 alone, the launch of the single call with NaN bounds; nearly every frame ends here (:499-500)
   SDSO_TRY(run(0, 1));
   bool stop = S.step(0, tries[0], *aff_last_2_l, lastCoarseRMSE[0], reTrackThreshold, recs[0]);
   // ---- phase 2: every other try in one launch under the bounds try 0 left (NaN where it was not good) — no tighter than the loop's own
@@ -63,4 +64,11 @@ extern "C" int sdso_track_new_coarse(sdso_ctx* ctx, int ref_slot, int frame_slot
   }
   S.finish(tries[0], *aff_last_2_l, lastCoarseRMSE, *out);
   return SDSO_OK;
+}
+
+extern "C" int sdso_track_new_coarse(sdso_ctx* ctx, int ref_slot, int frame_slot, const sdso_track_params_t* prm, int ntries,
+                                     const sdso_se3_t* tries, const sdso_aff_t* aff_last_2_l, double* lastCoarseRMSE, double reTrackThreshold,
+                                     sdso_track_tries_result_t* out, sdso_track_try_t* recs) {
+  return track_new_coarse_with(ctx, ref_slot, frame_slot, prm, ntries, tries, aff_last_2_l, lastCoarseRMSE, reTrackThreshold, out, recs,
+                               track_newest_coarse_run);
 }

@@ -240,8 +240,8 @@ template <class SE3T, class AffLightT, class Mat33T, class Vec3T> class CoarseTr
   //   inout lastCoarseRMSE (:499, :511)
   //   out   lastF_2_fh, aff_g2l, flowVecs, achievedRes, tryIterations; returns haveOneGood (the caller prints the BIG ERROR of :504)
   // Afterwards lastResiduals / lastFlowIndicators are those of the last try the loop ran, as in the reference, and firstCoarseRMSE is
-  // set as :528-529 set it.  lastTries holds one record per try (ran, what the loop saw, the abort level).  DSO-native LM only: with
-  // forkLive the member throws (the fork's g2o tracker inside the loop is not built).
+  // set as :528-529 set it.  lastTries holds one record per try (ran, what the loop saw, the abort level).  With forkLive the tries run
+  // the fork's live body (sdso_g2o_track_new_coarse: one EdgeSE3PosePhotoDSO per point, g2o's Levenberg-Marquardt), under the same rules.
   template <class FrameHessianT, class TriesT, class Vec5T, class Vec3FlowT>
   bool trackNewCoarse(FrameHessianT* fh, const TriesT& lastF_2_fh_tries, const AffLightT& aff_last_2_l, int coarsestLvl, Vec5T& lastCoarseRMSE,
                       float reTrackThreshold, SE3T& lastF_2_fh, AffLightT& aff_g2l, Vec3FlowT& flowVecs, Vec5T& achievedRes, int& tryIterations) {
@@ -254,7 +254,6 @@ template <class SE3T, class AffLightT, class Mat33T, class Vec3T> class CoarseTr
   bool trackNewCoarse(int newFrame_slot, float newFrame_ab_exposure, const TriesT& lastF_2_fh_tries, const AffLightT& aff_last_2_l, int coarsestLvl,
                       Vec5T& lastCoarseRMSE, float reTrackThreshold, SE3T& lastF_2_fh, AffLightT& aff_g2l, Vec3FlowT& flowVecs, Vec5T& achievedRes,
                       int& tryIterations) {
-    if (forkLive) throw Error("trackNewCoarse: the fork's g2o tracker inside the loop is not built (forkLive must be false)");
     prm_.new_exposure = newFrame_ab_exposure;
     prm_.coarsestLvl = coarsestLvl;
     std::vector<sdso_se3_t> tries;
@@ -263,8 +262,12 @@ template <class SE3T, class AffLightT, class Mat33T, class Vec3T> class CoarseTr
     double rmse[5];
     for (int i = 0; i < 5; i++) rmse[i] = lastCoarseRMSE[i];
     lastTries.assign(tries.size(), sdso_track_try_t{});
-    dev_.check(sdso_track_new_coarse(dev_.ctx(), ref_slot_, newFrame_slot, &prm_, (int)tries.size(), tries.data(), &aff0, rmse, (double)reTrackThreshold,
-                                     &lastTriesResult, lastTries.data()), "sdso_track_new_coarse");
+    if (forkLive)
+      dev_.check(sdso_g2o_track_new_coarse(dev_.ctx(), ref_slot_, newFrame_slot, &prm_, (int)tries.size(), tries.data(), &aff0, rmse, (double)reTrackThreshold,
+                                           &lastTriesResult, lastTries.data()), "sdso_g2o_track_new_coarse");
+    else
+      dev_.check(sdso_track_new_coarse(dev_.ctx(), ref_slot_, newFrame_slot, &prm_, (int)tries.size(), tries.data(), &aff0, rmse, (double)reTrackThreshold,
+                                       &lastTriesResult, lastTries.data()), "sdso_track_new_coarse");
     const sdso_track_tries_result_t& r = lastTriesResult;
     const sdso_track_try_t& last = lastTries[r.tryIterations - 1];       // the tracker's members after the loop: the last try it ran
     for (int i = 0; i < 5; i++) { lastResiduals[i] = last.lastResiduals[i]; achievedRes[i] = r.achievedRes[i]; lastCoarseRMSE[i] = rmse[i]; }   // :511

@@ -173,6 +173,8 @@ SIGNATURES = {
     "sdso_g2o_track_add_edges": [vp, I, I, P(G2oTrackEval), dP, iP, bP, fP],
     "sdso_g2o_track_linearize": [vp, I, I, P(G2oTrackEval), dP, dP, dP, dP, dP],
     "sdso_g2o_track_newest_coarse": [vp, I, I, P(TrackParams), P(SE3), P(Aff), P(TrackResult)],
+    "sdso_g2o_track_newest_coarse_batch": [vp, I, iP, iP, P(TrackParams), P(SE3), P(Aff), P(TrackResult)],
+    "sdso_g2o_track_new_coarse": [vp, I, I, P(TrackParams), I, P(SE3), P(Aff), dP, D, P(TrackTriesResult), P(TrackTry)],
     "sdso_g2o_lba_eval": [vp, P(G2oLba), dP, dP, bP, fP, fP, fP, bP],
     "sdso_g2o_lba_optimize": [vp, P(G2oLbaWindow), P(G2oLbaOpt), P(G2oLbaState), P(G2oLbaResult)],
     # the device-resident map
