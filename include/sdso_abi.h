@@ -1462,6 +1462,31 @@ typedef struct {
 int sdso_g2o_lba_optimize(sdso_ctx* ctx, const sdso_g2o_lba_window_t* W, const sdso_g2o_lba_opt_t* P, sdso_g2o_lba_state_t* S,
                           sdso_g2o_lba_result_t* out);
 
+/* The same optimiser with the Levenberg-Marquardt loop resident on the device, enqueue-only: the same W, P and S, "The rules." above and
+ * the same outputs, except that nothing comes down or goes up between the evaluations — the controller (csrc/g2o_lba_core.h), the
+ * block-arrow solve, the updates and the float pair tables of the tentative estimates are a single-workgroup step on the device between
+ * the wide kernels, in the operation order the host has in sdso_g2o_lba_optimize.  Between _enqueue and _fetch the host does not wait,
+ * does not copy and decides nothing.  sdso_g2o_lba_optimize keeps its body and is the A/B.
+ *
+ * _enqueue : validates (the refusals of sdso_g2o_lba_optimize, in its words, each before any device work and leaving no job behind),
+ *            sorts host-major, copies EVERY input into buffers the job owns and enqueues the whole run on the ctx's stream.  On return the
+ *            caller may overwrite or free everything W, P and S0 point to.  THE FRAMES' PYRAMID SLOTS ARE NOT COPIED: the caller keeps
+ *            the slots of W->frame_slot uploaded and unchanged until the fetch.  nr == 0: SDSO_OK, an empty job.
+ *            One job per ctx: a second _enqueue (or _resident) before the fetch is SDSO_ERR_STATE and leaves the pending job intact.
+ *            Any other call on the ctx between enqueue and fetch leaves the job's results alone (its buffers are its own);
+ *            sdso_ctx_destroy with a job pending drains the stream and frees it.
+ * _done    : 1 the job has finished, 0 it is still running, SDSO_ERR_STATE there is no job.  Never waits.
+ * _fetch   : waits for the job and writes S and out in the caller's order under the rules above (estimates untouched after zero
+ *            iterations, a host without an active edge keeps its inputs, an inactive edge its idepth).  S's and out's arrays have the
+ *            sizes the job was enqueued with.  Without a job, or a second time: SDSO_ERR_STATE, nothing written.  A null argument or
+ *            array: SDSO_ERR_ARG, nothing written, the job stays pending.
+ * _resident: _enqueue + _fetch; S is read at entry and written at exit as in sdso_g2o_lba_optimize, whose refusals it has. */
+int sdso_g2o_lba_optimize_enqueue(sdso_ctx* ctx, const sdso_g2o_lba_window_t* W, const sdso_g2o_lba_opt_t* P, const sdso_g2o_lba_state_t* S0);
+int sdso_g2o_lba_optimize_done(sdso_ctx* ctx);
+int sdso_g2o_lba_optimize_fetch(sdso_ctx* ctx, sdso_g2o_lba_state_t* S, sdso_g2o_lba_result_t* out);
+int sdso_g2o_lba_optimize_resident(sdso_ctx* ctx, const sdso_g2o_lba_window_t* W, const sdso_g2o_lba_opt_t* P, sdso_g2o_lba_state_t* S,
+                                   sdso_g2o_lba_result_t* out);
+
 /* ------------------------------------------------------------------ the device-resident map
  * What FullSystem::makeKeyFrame publishes through publishKeyframes (FullSystem.cpp:1467 for the whole window, FullSystemMarginalize.cpp:184
  * for a frame that leaves) and the one consumer the reference ships, KeyFrameDisplay::setFromKF / refreshPC

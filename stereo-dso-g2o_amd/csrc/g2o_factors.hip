@@ -17,6 +17,10 @@
 //                     sdso_g2o_track_new_coarse
 //   g2o_lba_opt.hip   sdso_g2o_lba_optimize: FullSystem::optimize as the fork compiles it (FullSystemOptimize.cpp:402-868), its kernels
 //                     over the LBA edge's pixel body below
+//   g2o_lba_core.h    what that optimiser decides between its evaluations (g2o_lm::run cut at the evaluations, the reduced system and its
+//                     solve), plain C++ for host and device
+//   g2o_lba_resident.hip  sdso_g2o_lba_optimize_enqueue / _done / _fetch / _resident: the same optimiser with that core resident on the
+//                     device, enqueue-only
 #include "sdso_internal.h"
 #include "host_math.h"
 #include <algorithm>
@@ -31,6 +35,19 @@ struct G2oEdgeSet {
   DevBuf<uint8_t> mask;
   DevBuf<float4> xref;       // {Xref, measurement}
 };
+// The pending job of sdso_g2o_lba_optimize_enqueue (g2o_lba_resident.hip).  Its buffers are its own — not ctx->scratch, which any call
+// between enqueue and fetch may take: `dev` holds the control block, the sorted inputs, the work arrays and the results; `up` and `down`
+// are the pinned sides of the one upload and the downloads.  `ev` marks the end of the job on the ctx's stream.
+struct LbaResJob {
+  DevBuf<void> dev;
+  PinBuf<void> up, down;
+  hipEvent_t ev = nullptr;
+  bool pending = false, empty = false;   // empty: nr == 0, nothing was enqueued
+  int nf = 0, nr = 0;
+  size_t d_ctl = 0, d_res = 0;           // in `down`: the control block, the per-residual results
+  std::vector<int> perm;                 // perm[sorted position] = the caller's index
+  ~LbaResJob() { if (ev) hipEventDestroy(ev); }   // (whoever destroys the state has synchronised the stream)
+};
 struct G2oState {
   std::map<std::pair<int, int>, G2oEdgeSet> sets;   // (ref_slot, level)
   DevBuf<double> d_part;                             // per-block partial systems
@@ -41,6 +58,7 @@ struct G2oState {
   DevBuf<void> lm_jobs;
   DevBuf<uint8_t> lm_mask;
   DevBuf<float> lm_flow;
+  LbaResJob lbar;
 };
 void release_g2o(sdso_ctx* ctx) {
   delete ctx->g2o;
@@ -219,14 +237,19 @@ __global__ __launch_bounds__(256) void k_g2o_track_lin(int n, const uint8_t* __r
 }
 
 // ------------------------------------------------------------------------------------------------ LBA edge (B13)
-struct LbaDev {
+// (ImgT: where the frames' level-0 images are named — an array of its own in a launch argument, or a pointer to such an array for the
+//  kernels of g2o_lba_resident.hip, whose copy of the record in registers must not hold an array that a lane indexes)
+template <class ImgT>
+struct LbaDevT {
   int nf, nr, w, h;
-  const float4* img[8];
+  ImgT img;
   const float* pair_R; const float* pair_t; const float* pair_ab; const double* host_b0; const float* frameEnergyTH;
   double cam[4];
   const int* host; const int* target; const float* u; const float* v; const double* idepth; const float* color; const float* weights;
   double* error; double* J; uint8_t* state; float* energy; float* cpt; float* idepth_hessian; uint8_t* edge_level;
 };
+typedef const float4* LbaImgs[8];
+typedef LbaDevT<LbaImgs> LbaDev;
 
 __constant__ int c_lba_pat[8][2] = {{0, -2}, {-1, -1}, {1, -1}, {-2, 0}, {0, 0}, {2, 0}, {-1, 1}, {0, 2}};
 
@@ -240,8 +263,8 @@ struct LbaPix {
   bool f_neg, f_oob, f_nan;
 };
 // one pattern pixel of residual rr (host h, target tg) at the vertex estimate `idepth`; JAC = false leaves row[] zero
-template <bool JAC>
-__device__ __forceinline__ LbaPix lba_pixel(const LbaDev& L, int rr, int idx, int h, int tg, double idepth) {
+template <bool JAC, class DevT>
+__device__ __forceinline__ LbaPix lba_pixel(const DevT& L, int rr, int idx, int h, int tg, double idepth) {
   LbaPix P;
   P.e = 0; P.X = 0; P.wj = 0;
   P.f_neg = false; P.f_oob = false; P.f_nan = false;
@@ -689,6 +712,8 @@ extern "C" int sdso_g2o_lba_eval(sdso_ctx* ctx, const sdso_g2o_lba_t* Lh, double
 // FullSystem::optimize, fork-live (FullSystemOptimize.cpp:402-868): the window optimiser over the LBA edge above
 #include "g2o_lm.h"
 #include "g2o_lba_opt.hip"
+#include "g2o_lba_core.h"
+#include "g2o_lba_resident.hip"
 // CoarseTracker::trackNewestCoarse and FullSystem::trackNewCoarse, fork-live, resident on the device
 #include "g2o_track_core.h"
 #include "g2o_track_lm.hip"

@@ -27,8 +27,9 @@ constexpr int kLbaEvalBlocks = 128;  // partials of k_lba_opt_eval
 constexpr int kLbaLinChunks = 16;    // workgroups per host in k_lba_opt_lin; each writes two partials
 constexpr int kLbaScChunks = 16;     // workgroups per host in k_lba_opt_schur
 
-struct LbaOpt {
-  LbaDev L;                    // sorted arrays; pair tables, cam and idepth of the estimate the launch evaluates
+template <class DevT>
+struct LbaOptT {
+  DevT L;                      // sorted arrays; pair tables, cam and idepth of the estimate the launch evaluates
   const int* hstart;           // nf + 1: the range of every host
   const double* idepth_cur;    // current estimate (the trial adds its increment to it)
   double* idepth_trial;        // tentative estimate, written by the trial
@@ -39,6 +40,7 @@ struct LbaOpt {
   double lambda;
   double* part;                // partial sums of the launch
 };
+typedef LbaOptT<LbaDev> LbaOpt;
 
 __device__ __forceinline__ double group_sum8(double v) {
   v += __shfl_xor(v, 1, 64);
@@ -49,9 +51,10 @@ __device__ __forceinline__ double group_sum8(double v) {
 
 // mode 0: the build-time computeError (FullSystemOptimize.cpp:539) — fixes the active set; 1: computeActiveErrors at the current estimate,
 // per-residual results written; 2: at the tentative estimate current + x, nothing but the sums and the tentative idepth written
-template <int MODE>
-__global__ __launch_bounds__(256) void k_lba_opt_eval(LbaOpt O) {
-  const LbaDev& L = O.L;
+// (the bodies are stated once: the kernels below take O as a launch argument, those of g2o_lba_resident.hip build it from the job's control block)
+template <int MODE, class OptT>
+__device__ __forceinline__ void lba_opt_eval_body(const OptT& O) {
+  const auto& L = O.L;
   const int idx = threadIdx.x & 7, lane = threadIdx.x & 63, base = lane & ~7, wv = threadIdx.x >> 6;
   double chi = 0, scale = 0;
   for (int g0 = blockIdx.x * 32; g0 < L.nr; g0 += gridDim.x * 32) {
@@ -104,6 +107,8 @@ __global__ __launch_bounds__(256) void k_lba_opt_eval(LbaOpt O) {
   __syncthreads();
   if (threadIdx.x < 2) O.part[blockIdx.x * 2 + threadIdx.x] = ((sm[0][threadIdx.x] + sm[1][threadIdx.x]) + sm[2][threadIdx.x]) + sm[3][threadIdx.x];
 }
+template <int MODE>
+__global__ __launch_bounds__(256) void k_lba_opt_eval(LbaOpt O) { lba_opt_eval_body<MODE>(O); }
 
 // entry `ent` of the upper triangle, row-major: (i, j), i <= j < 13
 __device__ __forceinline__ void lba_entry(int ent, int& i, int& j) {
@@ -114,8 +119,9 @@ __device__ __forceinline__ void lba_entry(int ent, int& i, int& j) {
 }
 
 // grid (kLbaLinChunks, nf): workgroup (c, h) takes the tiles c, c + kLbaLinChunks, ... of 32 edges of host h
-__global__ __launch_bounds__(256) void k_lba_opt_lin(LbaOpt O) {
-  const LbaDev& L = O.L;
+template <class OptT>
+__device__ __forceinline__ void lba_opt_lin_body(const OptT& O) {
+  const auto& L = O.L;
   const int h = blockIdx.y;
   const int idx = threadIdx.x & 7, lane = threadIdx.x & 63, base = lane & ~7;
   const int e0 = O.hstart[h], e1 = O.hstart[h + 1];
@@ -166,9 +172,11 @@ __global__ __launch_bounds__(256) void k_lba_opt_lin(LbaOpt O) {
   }
   if (ent < kLbaEnt) O.part[((size_t)h * (2 * kLbaLinChunks) + blockIdx.x * 2 + half) * kLbaEnt + ent] = acc;
 }
+__global__ __launch_bounds__(256) void k_lba_opt_lin(LbaOpt O) { lba_opt_lin_body(O); }
 
 // grid (kLbaScChunks, nf), 128 threads: workgroup (c, h) takes the c-th slice of host h's records
-__global__ __launch_bounds__(128) void k_lba_opt_schur(LbaOpt O) {
+template <class OptT>
+__device__ __forceinline__ void lba_opt_schur_body(const OptT& O) {
   const int h = blockIdx.y;
   const int e0 = O.hstart[h], e1 = O.hstart[h + 1];
   const int per = (e1 - e0 + kLbaScChunks - 1) / kLbaScChunks;
@@ -193,6 +201,7 @@ __global__ __launch_bounds__(128) void k_lba_opt_schur(LbaOpt O) {
   }
   if (ent < kLbaEnt) O.part[((size_t)h * kLbaScChunks + blockIdx.x) * kLbaEnt + ent] = acc;
 }
+__global__ __launch_bounds__(128) void k_lba_opt_schur(LbaOpt O) { lba_opt_schur_body(O); }
 
 // out[g][v] = part[g][0][v] + part[g][1][v] + ... in that order; grid = groups, 128 threads
 __global__ __launch_bounds__(128) void k_lba_opt_fold(const double* __restrict__ part, int nparts, int nvals, double* __restrict__ out) {
@@ -365,13 +374,16 @@ static bool finite_se3(const sdso_se3_t& T) {
   return true;
 }
 
-}  // namespace sdso
-
-extern "C" int sdso_g2o_lba_optimize(sdso_ctx* ctx, const sdso_g2o_lba_window_t* W, const sdso_g2o_lba_opt_t* P, sdso_g2o_lba_state_t* S,
-                                     sdso_g2o_lba_result_t* out) {
-  if (!ctx) return SDSO_ERR_STATE;
-  SDSO_HIP(ctx, hipSetDevice(ctx->device));
-  SDSO_REQUIRE(ctx, W && P && S && out, "null argument");
+// The refusals of the window optimiser, stated once for sdso_g2o_lba_optimize and sdso_g2o_lba_optimize_enqueue (g2o_lba_resident.hip),
+// each before any device work.  `out` is checked where the entry point takes one (want_out).  Leaves the frames' level-0 images and the
+// range of every host in the host-major order.
+struct LbaCall {
+  const float4* img[8];
+  int hstart[9];
+};
+static int lba_validate(sdso_ctx* ctx, const sdso_g2o_lba_window_t* W, const sdso_g2o_lba_opt_t* P, const sdso_g2o_lba_state_t* S,
+                        const sdso_g2o_lba_result_t* out, bool want_out, LbaCall* call) {
+  SDSO_REQUIRE(ctx, W && P && S && (out || !want_out), "null argument");
   const int nf = W->nf, nr = W->nr;
   SDSO_REQUIRE(ctx, nf >= 1 && nf <= 8, "nf must be 1..8");
   SDSO_REQUIRE(ctx, nr >= 0, "nr must not be negative");
@@ -383,55 +395,83 @@ extern "C" int sdso_g2o_lba_optimize(sdso_ctx* ctx, const sdso_g2o_lba_window_t*
   if (nr > 0) {
     SDSO_REQUIRE(ctx, W->host && W->target && W->u && W->v && W->color && W->weights, "null window array");
     SDSO_REQUIRE(ctx, S->idepth, "null estimate array");
-    SDSO_REQUIRE(ctx, out->state && out->energy && out->centerProjectedTo && out->edge_level && out->idepth_hessian && out->active, "null result array");
+    if (want_out)
+      SDSO_REQUIRE(ctx, out->state && out->energy && out->centerProjectedTo && out->edge_level && out->idepth_hessian && out->active, "null result array");
   }
+  for (int f = 0; f < nf; f++) {
+    auto ip = ctx->pyr.find(W->frame_slot[f]);
+    SDSO_REQUIRE(ctx, ip != ctx->pyr.end(), "unknown frame slot");
+    SDSO_REQUIRE(ctx, ip->second.w[0] == W->w && ip->second.h[0] == W->h, "frame size mismatch");
+    call->img[f] = ip->second.d[0];
+    SDSO_REQUIRE(ctx, finite_se3(W->Ttw[f]) && finite_se3(S->Twh[f]), "non-finite pose");
+    SDSO_REQUIRE(ctx, std::isfinite(W->target_aff[f].a) && std::isfinite(W->target_aff[f].b) && std::isfinite(S->host_aff[f].a) &&
+                          std::isfinite(S->host_aff[f].b) && std::isfinite(W->ab_exposure[f]) && std::isfinite(W->host_b0[f]), "non-finite affine parameter");
+  }
+  for (int k = 0; k < 4; k++) SDSO_REQUIRE(ctx, std::isfinite(S->cam[k]), "non-finite camera parameter");
+  for (int f = 0; f < 9; f++) call->hstart[f] = 0;
+  for (int r = 0; r < nr; r++) {
+    SDSO_REQUIRE(ctx, W->host[r] >= 0 && W->host[r] < nf && W->target[r] >= 0 && W->target[r] < nf, "host / target out of range");
+    SDSO_REQUIRE(ctx, std::isfinite(W->u[r]) && std::isfinite(W->v[r]) && std::isfinite(S->idepth[r]), "non-finite point");
+    call->hstart[W->host[r] + 1]++;
+  }
+  for (int f = 0; f < nf; f++) call->hstart[f + 1] += call->hstart[f];
+  return SDSO_OK;
+}
+
+// host-major order: a stable counting sort, perm[sorted position] = the caller's index; the residual arrays in that order
+struct LbaSorted {
+  int *host, *target;
+  float *u, *v, *color, *weights;
+  double* idepth;
+};
+static void lba_sort_host_major(const sdso_g2o_lba_window_t* W, const double* idepth, const int* hstart, int* perm, const LbaSorted& o) {
+  const int nf = W->nf, nr = W->nr;
+  int fill[8];
+  for (int f = 0; f < nf; f++) fill[f] = hstart[f];
+  for (int r = 0; r < nr; r++) perm[fill[W->host[r]]++] = r;
+  for (int i = 0; i < nr; i++) {
+    const int r = perm[i];
+    o.host[i] = W->host[r]; o.target[i] = W->target[r]; o.u[i] = W->u[r]; o.v[i] = W->v[r]; o.idepth[i] = idepth[r];
+    std::memcpy(o.color + (size_t)i * 8, W->color + (size_t)r * 8, 32);
+    std::memcpy(o.weights + (size_t)i * 8, W->weights + (size_t)r * 8, 32);
+  }
+}
+
+// what a run without iterations leaves in `out` (and what every run starts from)
+static void lba_result_reset(sdso_g2o_lba_result_t* out) {
+  out->iterations = 0; out->stop = SDSO_G2O_LBA_STOP_ITERATIONS; out->n_active = 0; out->chi2_final = 0; out->rmse = 0;
+  for (int i = 0; i < SDSO_G2O_LBA_MAX_RECORDED; i++) { out->trials[i] = 0; out->lambda[i] = 0; out->chi2[i] = 0; }
+}
+
+}  // namespace sdso
+
+extern "C" int sdso_g2o_lba_optimize(sdso_ctx* ctx, const sdso_g2o_lba_window_t* W, const sdso_g2o_lba_opt_t* P, sdso_g2o_lba_state_t* S,
+                                     sdso_g2o_lba_result_t* out) {
+  if (!ctx) return SDSO_ERR_STATE;
+  SDSO_HIP(ctx, hipSetDevice(ctx->device));
+  LbaCall call;
+  SDSO_TRY(lba_validate(ctx, W, P, S, out, true, &call));
+  const int nf = W->nf, nr = W->nr;
   LbaProblem Q;
   std::memset(&Q.O, 0, sizeof(Q.O));
   Q.ctx = ctx; Q.W = W; Q.nf = nf; Q.nr = nr;
   LbaDev& D = Q.O.L;
   D.nf = nf; D.nr = nr; D.w = W->w; D.h = W->h;
   for (int f = 0; f < nf; f++) {
-    auto ip = ctx->pyr.find(W->frame_slot[f]);
-    SDSO_REQUIRE(ctx, ip != ctx->pyr.end(), "unknown frame slot");
-    SDSO_REQUIRE(ctx, ip->second.w[0] == W->w && ip->second.h[0] == W->h, "frame size mismatch");
-    D.img[f] = ip->second.d[0];
-    SDSO_REQUIRE(ctx, finite_se3(W->Ttw[f]) && finite_se3(S->Twh[f]), "non-finite pose");
-    SDSO_REQUIRE(ctx, std::isfinite(W->target_aff[f].a) && std::isfinite(W->target_aff[f].b) && std::isfinite(S->host_aff[f].a) &&
-                          std::isfinite(S->host_aff[f].b) && std::isfinite(W->ab_exposure[f]) && std::isfinite(W->host_b0[f]), "non-finite affine parameter");
+    D.img[f] = call.img[f];
     Q.Twh[f] = se3_from_abi(S->Twh[f]);
     Q.aff[f][0] = S->host_aff[f].a; Q.aff[f][1] = S->host_aff[f].b;
     Q.n_active_host[f] = 0;
   }
-  for (int k = 0; k < 4; k++) {
-    SDSO_REQUIRE(ctx, std::isfinite(S->cam[k]), "non-finite camera parameter");
-    Q.cam[k] = S->cam[k];
-  }
-  // host-major order: a stable counting sort, perm[sorted position] = the caller's index
-  int hstart[9] = {0};
-  for (int r = 0; r < nr; r++) {
-    SDSO_REQUIRE(ctx, W->host[r] >= 0 && W->host[r] < nf && W->target[r] >= 0 && W->target[r] < nf, "host / target out of range");
-    SDSO_REQUIRE(ctx, std::isfinite(W->u[r]) && std::isfinite(W->v[r]) && std::isfinite(S->idepth[r]), "non-finite point");
-    hstart[W->host[r] + 1]++;
-  }
-  for (int f = 0; f < nf; f++) hstart[f + 1] += hstart[f];
-  out->iterations = 0; out->stop = SDSO_G2O_LBA_STOP_ITERATIONS; out->n_active = 0; out->chi2_final = 0; out->rmse = 0;
-  for (int i = 0; i < SDSO_G2O_LBA_MAX_RECORDED; i++) { out->trials[i] = 0; out->lambda[i] = 0; out->chi2[i] = 0; }
+  for (int k = 0; k < 4; k++) Q.cam[k] = S->cam[k];
+  const int* hstart = call.hstart;
+  lba_result_reset(out);
   if (nr == 0) return SDSO_OK;
   std::vector<int> perm(nr);
-  {
-    int fill[8];
-    for (int f = 0; f < nf; f++) fill[f] = hstart[f];
-    for (int r = 0; r < nr; r++) perm[fill[W->host[r]]++] = r;
-  }
   std::vector<int> s_host(nr), s_tg(nr);
   std::vector<float> s_u(nr), s_v(nr), s_col((size_t)nr * 8), s_w((size_t)nr * 8);
   std::vector<double> s_id(nr);
-  for (int i = 0; i < nr; i++) {
-    const int r = perm[i];
-    s_host[i] = W->host[r]; s_tg[i] = W->target[r]; s_u[i] = W->u[r]; s_v[i] = W->v[r]; s_id[i] = S->idepth[r];
-    std::memcpy(&s_col[(size_t)i * 8], W->color + (size_t)r * 8, 32);
-    std::memcpy(&s_w[(size_t)i * 8], W->weights + (size_t)r * 8, 32);
-  }
+  lba_sort_host_major(W, S->idepth, hstart, perm.data(), {s_host.data(), s_tg.data(), s_u.data(), s_v.data(), s_col.data(), s_w.data(), s_id.data()});
   // one device blob
   const size_t nn = (size_t)nf * nf;
   size_t off = 0;

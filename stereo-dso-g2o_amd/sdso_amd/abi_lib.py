@@ -177,6 +177,10 @@ SIGNATURES = {
     "sdso_g2o_track_new_coarse": [vp, I, I, P(TrackParams), I, P(SE3), P(Aff), dP, D, P(TrackTriesResult), P(TrackTry)],
     "sdso_g2o_lba_eval": [vp, P(G2oLba), dP, dP, bP, fP, fP, fP, bP],
     "sdso_g2o_lba_optimize": [vp, P(G2oLbaWindow), P(G2oLbaOpt), P(G2oLbaState), P(G2oLbaResult)],
+    "sdso_g2o_lba_optimize_enqueue": [vp, P(G2oLbaWindow), P(G2oLbaOpt), P(G2oLbaState)],
+    "sdso_g2o_lba_optimize_done": [vp],
+    "sdso_g2o_lba_optimize_fetch": [vp, P(G2oLbaState), P(G2oLbaResult)],
+    "sdso_g2o_lba_optimize_resident": [vp, P(G2oLbaWindow), P(G2oLbaOpt), P(G2oLbaState), P(G2oLbaResult)],
     # the device-resident map
     "sdso_map_update": [vp, I, P(MapUpdate)],
     "sdso_map_counts": [vp, I, iP],
